@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - the hot path's headline benchmark (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself as N workers (one per GPU, rendezvous on
 127.0.0.1) and still prints ONE line; under torchrun it uses the environment it is given.  `--dry-run` swaps the model for a CPU
@@ -194,6 +194,9 @@ def parse_args(argv=None):
     ap.add_argument("--same-batch", action="store_true", help="feed ONE batch to every step (rounds 1-5; the loss then falls to ~0.3 inside the run and "
                     "dlogits / gradients shrink: A/B against the rotated default in profiles/r06_batch_rotation_ab.txt)")
     ap.add_argument("--no-cfg5-extra", action="store_true", help="skip the cfg-5 (S=8192 interleave, fp8 weight path) row of the N=1 line's `extras`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (loss, a "
+                    "seeded sample of the logits rows and of the parameters the optimizer wrote) to DIR/<name>.npy, float32 / float64, "
+                    f"at most {DUMP_LIMIT_BYTES >> 20} MB in all, to compare two builds output for output (rank 0 only)")
     return ap.parse_args(argv)
 
 
@@ -245,6 +248,34 @@ class _DryEngine:
         self.arena.flat.add_(self.arena.gflat, alpha=-1e-3 * (sync.grad_scale if sync else 1.0))
         self.weight_version += 1
         return self.arena.gflat.sum()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_LOGITS_ROWS = 256       # of B * S positions, every vocabulary column
+DUMP_PARAM_ELEMS = 1 << 20   # of the flat parameter arena
+
+
+def dump_outputs(path, loss, logits, params, seed=0):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  loss.npy = the step's loss (float64); logits.npy = DUMP_LOGITS_ROWS
+    positions of the [B, S, V] logits drawn with `seed`, in position order, all V columns (float32); params.npy = DUMP_PARAM_ELEMS elements of the
+    flat parameter arena drawn with `seed` (float32), i.e. the weights after the step's optimizer update.  The samples depend only on the shapes
+    and `seed`, and bench's inputs are seeded, so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float64)}
+    if logits is not None:
+        B, S, V = logits.shape
+        rows = torch.randperm(B * S, generator=g)[:DUMP_LOGITS_ROWS].sort().values.to(logits.device)
+        arrays["logits"] = logits[rows // S, rows % S].float().cpu().numpy()
+    idx = torch.randint(params.numel(), (min(DUMP_PARAM_ELEMS, params.numel()),), generator=g).sort().values.to(params.device)
+    arrays["params"] = params[idx].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def kernel_source_stamp():
@@ -334,6 +365,12 @@ def main(argv=None):
                 os.environ.update(NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="TUNING", NCCL_DEBUG_FILE=rccl_log)
             dist.init_process_group("nccl", device_id=dev)
 
+    def barrier():
+        if dry:  # gloo's dist.barrier() probes the host's accelerator, which opens the GPU: a CPU all-reduce holds the ranks together instead
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
+
     def all_max(x):
         if not dp:
             return float(x)
@@ -356,6 +393,7 @@ def main(argv=None):
 
     O = None
     model = None
+    last = {}  # --dump-outputs: the model output of the last timed step (kept for that step only)
     emu = None
     recompute_fallback = False
     hbm_info = {}
@@ -365,7 +403,7 @@ def main(argv=None):
         workload = "DRY RUN: CPU stand-in over gloo (launcher / GradSync / timing protocol only)"
         sync = GradSync(eng, force=args.force_dp) if dp else None
 
-        def step():
+        def step(keep=False):
             return eng.step(sync)
     else:
         from merlin_amd import ops as O
@@ -466,24 +504,29 @@ def main(argv=None):
 
             eng.on_grads_ready = _emu_ready
 
-        def train_step(db):
+        def train_step(db, keep=False):
             out = model(**db)
             out.loss.backward()
             # (GradSync joins the communication stream at the end of backward: the clip sees the all-reduced gradients)
             opt.step(grad_scale=(sync.grad_scale if sync else 1.0), max_grad_norm=1.0, lr_mult=cosine_with_warmup(it[0] + 10, 1000, 0.01))
             it[0] += 1
             opt.zero_grad()
+            if keep:
+                last["out"] = out
             return out.loss
 
         calls = [0]
 
-        def step():
+        def step(keep=False):
             if args.fwd_only:
                 with torch.no_grad():
-                    return model(**dbatch).loss
+                    out = model(**dbatch)
+                if keep:
+                    last["out"] = out
+                return out.loss
             db = dbatches[calls[0] % len(dbatches)]
             calls[0] += 1
-            return train_step(db)
+            return train_step(db, keep)
 
     loss_first = None
     for wi in range(args.warmup):
@@ -516,7 +559,7 @@ def main(argv=None):
             hbm_info["mem_level"] = eng.mem_level
     dev_sync()
     if dp:
-        dist.barrier()
+        barrier()
     dev_sync()
     if O is not None:
         O.profile_start()
@@ -526,11 +569,11 @@ def main(argv=None):
     if not dry:
         torch.cuda.reset_peak_memory_stats(dev)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     dev_sync()
     if dp:
-        dist.barrier()
+        barrier()
     dev_sync()
     dt = time.perf_counter() - t0
     prof = O.profile_stop() if O is not None else {}
@@ -541,6 +584,10 @@ def main(argv=None):
         sync.timing = False
     loss_val = float(loss.detach())
     peak_gb = 0.0 if dry else torch.cuda.max_memory_allocated(dev) / 1e9
+    out_last = last.pop("out", None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, loss, None if out_last is None else out_last.logits, eng.arena.flat)
+    del out_last
     # ---- forward-only leg (same batch, same weights; not part of `value`) ----
     fwd_ms = None
     if not dry and not args.fwd_only and not args.no_forward_leg:

@@ -83,6 +83,60 @@ def test_bench_single_process_dry_run_and_mismatch_is_an_error():
     assert p.returncode != 0 and "nproc-per-node" in (p.stderr + p.stdout)
 
 
+def test_bench_dump_outputs_is_float_bounded_and_repeatable(tmp_path):
+    """--dump-outputs DIR: after the timed steps the last step's results land in DIR/<name>.npy, float32 / float64, at most 64 MB in all, and
+    two runs with the same arguments write the same arrays (the dry run's stand-in engine: loss and the updated parameter arena)."""
+    import numpy as np
+
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dry-run", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        _check(_json_lines(p.stdout), 1)
+        files = sorted(os.listdir(d))
+        assert files == ["loss.npy", "params.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert abs(float(arrays["loss.npy"]) - _json_lines(p.stdout)[0]["config"]["loss"]) < 1e-3 * max(1.0, abs(float(arrays["loss.npy"])))
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_dump_outputs_samples_logits_rows_within_the_size_limit(tmp_path):
+    """bench.dump_outputs at the headline shapes' vocabulary width: a fixed seeded sample of logits rows (every column) and of the parameters,
+    the same sample every call, under 64 MB in all."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    B, S, V, Vpad = 2, 700, 32003, 32128
+    logits = torch.randn(B, S, Vpad, generator=torch.Generator().manual_seed(1))[:, :, :V]  # the engine's padded-row view
+    params = torch.randn(3 << 20, generator=torch.Generator().manual_seed(2)).to(torch.bfloat16)
+    loss = torch.tensor(4.25)
+    assert bench.dump_outputs(str(tmp_path / "a"), loss, logits, params) == ["logits", "loss", "params"]
+    bench.dump_outputs(str(tmp_path / "b"), loss, logits, params)
+    total = 0
+    for f in ("logits.npy", "loss.npy", "params.npy"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total <= 64 << 20
+    lg = np.load(tmp_path / "a" / "logits.npy")
+    assert lg.shape == (bench.DUMP_LOGITS_ROWS, V)
+    flat = logits.reshape(B * S, V).numpy()
+    assert all(any(np.array_equal(r, flat[j]) for j in range(B * S)) for r in lg[:4])  # rows are whole logits rows
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 4.25
+    assert np.load(tmp_path / "a" / "params.npy").shape == (bench.DUMP_PARAM_ELEMS,)
+
+
 def test_committed_pmc_traffic_summary_was_taken_on_the_committed_gemm_sources():
     """the driver's bench line carried `roofline.traffic: null` because a GEMM source changed after the PMC passes.  The
     newest profiles/rNN_gemm_traffic.json must carry the hash of the GEMM kernel sources as committed: the PMC pass
