@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - the hot path's headline benchmark (BASELINE.json metric) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself as N workers (one per GPU, rendezvous on
 127.0.0.1) and still prints ONE line; under torchrun it uses the environment it is given.  `--dry-run` swaps the model for a CPU
@@ -16,11 +16,18 @@ projector + Llama-7B, random-init weights from the build's generator, bf16):
     + [N>1] bucketed RCCL all-reduce of the 14 GB gradient arena, overlapped with the backward
     + global-norm clipping + fused AdamW (LLRD groups, cosine schedule) over the parameter arena.
 Inputs are resident in HBM before the timed region.  value = N * B * S / (max-over-ranks step time).
-After the timed training steps the same batch is also timed FORWARD-ONLY (`forward_only` in the JSON line: the north star's
-">= 40 % of the bf16 MFMA roofline on the fused ViT+LLM forward" is quoted on that leg).
 One JSON line is printed by rank 0, with `roofline` (dominant kernel = the MFMA GEMM, timed per launch with
-HIP events on the launch stream inside the timed steps) and `cpu_baseline` (the CPU oracle = a port of the
-reference's CPU forward, timed on this box's host cores on a bounded sample).
+HIP events on the launch stream inside the timed steps).
+
+A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.  `--full` adds, after the timed steps, what
+else the benchmark measures (each leg can be left out of a full run with its --no-* switch):
+    `forward_only`: the same batch timed FORWARD-ONLY (the north star's ">= 40 % of the bf16 MFMA roofline on the fused
+      ViT+LLM forward" is quoted on that leg; --no-forward-leg);
+    `extras` (N = 1, cfg 3): BASELINE cfg 2 (S = 613) and cfg 5 (S = 8192, fp8 weight path) on the same model (--no-extras,
+      --no-cfg5-extra);
+    `roofline.sustained_mfma_probe`: the register-only MFMA loop's rate on this GPU, just after the steps;
+    `cpu_baseline` (N = 1): the CPU oracle = a port of the reference's CPU forward, timed on this box's host cores on a bounded
+      sample (--no-cpu-baseline).
 """
 from __future__ import annotations
 
@@ -165,12 +172,15 @@ def parse_args(argv=None):
                          "fp8 MFMA weight path; cfg5-bf16 = the same shape with bf16 weights")
     ap.add_argument("--fp8-train", action="store_true", help="run the chosen config with the fp8 training step (cfg5 implies it)")
     ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run what the headline figure does not need: the "
+                    "forward-only leg, the N=1 line's `extras` (cfg 2, cfg 5), the sustained-MFMA probe beside `roofline` and the CPU baseline "
+                    "(the --no-* switches below leave single legs out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--recompute", action="store_true", help="recompute each layer's forward in backward (the reference's "
                     "gradient checkpointing) instead of keeping activations resident in the 288 GB of HBM")
     ap.add_argument("--fwd-only", action="store_true")
-    ap.add_argument("--no-forward-leg", action="store_true", help="skip the extra forward-only timing after the training steps")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg-2 (S=613) row of the N=1 line's `extras`")
+    ap.add_argument("--no-forward-leg", action="store_true", help="with --full: skip the extra forward-only timing after the training steps")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cfg-2 (S=613) row of the N=1 line's `extras`")
     ap.add_argument("--fp8-forward", action="store_true", help="with --fwd-only: decoder Linears on the scaled-fp8 MFMA (e4m3 operands, "
                     "per-row scales); NOT the headline configuration (dtype field says so)")
     ap.add_argument("--fp32-residual", action="store_true", help="(default since round 4, kept for old command lines) both towers' residual "
@@ -193,7 +203,8 @@ def parse_args(argv=None):
                     "step sees other token ids and images than the step before, as in training; all of them resident in HBM before the timed region)")
     ap.add_argument("--same-batch", action="store_true", help="feed ONE batch to every step (rounds 1-5; the loss then falls to ~0.3 inside the run and "
                     "dlogits / gradients shrink: A/B against the rotated default in profiles/r06_batch_rotation_ab.txt)")
-    ap.add_argument("--no-cfg5-extra", action="store_true", help="skip the cfg-5 (S=8192 interleave, fp8 weight path) row of the N=1 line's `extras`")
+    ap.add_argument("--no-cfg5-extra", action="store_true", help="with --full: skip the cfg-5 (S=8192 interleave, fp8 weight path) row of the N=1 "
+                    "line's `extras`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (loss, a "
                     "seeded sample of the logits rows and of the parameters the optimizer wrote) to DIR/<name>.npy, float32 / float64, "
                     f"at most {DUMP_LIMIT_BYTES >> 20} MB in all, to compare two builds output for output (rank 0 only)")
@@ -590,7 +601,7 @@ def main(argv=None):
     del out_last
     # ---- forward-only leg (same batch, same weights; not part of `value`) ----
     fwd_ms = None
-    if not dry and not args.fwd_only and not args.no_forward_leg:
+    if args.full and not dry and not args.fwd_only and not args.no_forward_leg:
         nf = max(3, min(10, args.steps))
         with torch.no_grad():
             for _ in range(2):
@@ -701,7 +712,7 @@ def main(argv=None):
         line["per_rank"] = [{"rank": i, "peak_hbm_gb": r[0], "comm_ms_total": r[1], "comm_ms_exposed": r[2]} for i, r in enumerate(per_rank)]
         line["recompute_fallback"] = recompute_fallback
         line.update(hbm_info)
-    if not fp8_dom and not dry:
+    if args.full and not fp8_dom and not dry:
         sustained = sustained_mfma_tflops()
         if sustained:
             line["roofline"]["sustained_mfma_probe"] = {"tflops": round(sustained, 1), "frac_of_it": round(ach / sustained, 4),
@@ -711,7 +722,7 @@ def main(argv=None):
         line["forward_only"] = {"ms_per_step": round(fwd_ms, 2), "tokens_per_s_per_gpu": round(n_tok / (fwd_ms * 1e-3), 1),
                                 "useful_tflops_per_gpu": round(fwd / (fwd_ms * 1e-3) / 1e12, 1),
                                 "mfma_roofline_frac": round(fwd / (fwd_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)}
-    if world == 1 and not dry and not args.no_extras and args.config == "cfg3" and not args.fwd_only and not args.fp8_train:
+    if args.full and world == 1 and not dry and not args.no_extras and args.config == "cfg3" and not args.fwd_only and not args.fp8_train:
         try:  # BASELINE cfg 2 (single image + caption, S = 613, B = 1) on the same model: a few training steps + forwards
             b2 = synth.single_image_batch()
             d2 = to_dev(b2)
@@ -757,7 +768,7 @@ def main(argv=None):
                                   "compute_stream_wait_ms_per_step": round(sum(ws) / max(1, len(ws)), 3),
                                   "what": "every gradient bucket read twice by a side-stream kernel of BLOCKS workgroups while the backward runs (stand-in for a ring all-reduce's kernels)"}
         eng.on_grads_ready = None
-    if not args.no_cpu_baseline and world == 1 and not dry:  # (the reported CPU baseline belongs to the N = 1 line only)
+    if args.full and not args.no_cpu_baseline and world == 1 and not dry:  # (the reported CPU baseline belongs to the N = 1 line only)
         try:
             line["cpu_baseline"] = cpu_baseline()
         except Exception as e:  # the baseline leg must never take the GPU number down

@@ -83,6 +83,25 @@ def test_bench_single_process_dry_run_and_mismatch_is_an_error():
     assert p.returncode != 0 and "nproc-per-node" in (p.stderr + p.stdout)
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """A plain `bench.py --steps K --warmup W` runs only what its headline figure needs; the forward-only leg, the `extras`, the MFMA probe
+    and the CPU baseline run only under --full, where the --no-* switches leave single legs out.  The switch also reaches the workers."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert not plain.full
+    full = bench.parse_args(["--full", "--no-cpu-baseline"])
+    assert full.full and full.no_cpu_baseline and not full.no_extras
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run", "--full"],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    _check(_json_lines(p.stdout), 2)
+
+
 def test_bench_dump_outputs_is_float_bounded_and_repeatable(tmp_path):
     """--dump-outputs DIR: after the timed steps the last step's results land in DIR/<name>.npy, float32 / float64, at most 64 MB in all, and
     two runs with the same arguments write the same arrays (the dry run's stand-in engine: loss and the updated parameter arena)."""

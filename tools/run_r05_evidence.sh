@@ -2,8 +2,8 @@
 # Round-5 evidence bundle (GPU box, from the repo root; LAST GPU action after any kernel change).  Everything lands in gpurun_out/r05ev/ and is
 # copied into profiles/ by hand (profiles/README.md says which file backs which claim).
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r05ev; mkdir -p $O; cd $R
-# 1. the driver's own command
-timeout 900 python bench.py > $O/bench_r05_default.json 2> $O/bench_r05_default.err
+# 1. the driver's command with --full (forward-only leg, extras, MFMA probe, CPU baseline)
+timeout 900 python bench.py --full > $O/bench_r05_default.json 2> $O/bench_r05_default.err
 # 2. rocprofv3 --kernel-trace --stats of the cfg-3 step and of the cfg-5 fp8 step (6 steps each)
 tools/run_prof.sh r05ev/r05_step_cfg3_kernel_stats python $R/bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-extras --no-cfg5-extra --no-forward-leg
 tools/run_prof.sh r05ev/r05_step_cfg5_fp8_kernel_stats python $R/bench.py --config cfg5 --steps 3 --warmup 3 --no-cpu-baseline --no-forward-leg --no-cfg5-extra

@@ -6,7 +6,7 @@ timeout 1500 python -m pytest tests/test_headline_gpu.py "tests/test_model_gpu.p
   "tests/test_model_gpu.py::test_lm_head_backward_over_the_scored_rows_only" "tests/test_dropin_gpu.py::test_released_geometry_448px_conv_stride2_vs_reference_golden" \
   "tests/test_geometry_gpu.py::test_packed_sequence_at_benchmark_length_vs_oracle" -x -q -s -m gpu > $O/tests.log 2>&1; echo "tests rc=$?" | tee -a $O/tests.log
 tail -5 $O/tests.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 for arm in same rot same2 rot2; do
   flag=""; case $arm in same*) flag="--same-batch";; esac
   timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-forward-leg $flag > $O/bench_$arm.json 2> $O/bench_$arm.err
