@@ -133,6 +133,15 @@ __device__ __forceinline__ void mfma32a(f32x16_t& acc, const u32x4_t& x, const u
   else
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(x), "v"(y));
 }
+// mfma32a for accumulators that hipcc may itself write right in front of the MFMA (attn_bwd2_kv_k's diagonal tiles: it restores them
+// from VGPRs with v_accvgpr_write): the s_nop 1 is the 2 wait states between that write and the MFMA reading it as C.
+template <int DT>
+__device__ __forceinline__ void mfma32a_w(f32x16_t& acc, const u32x4_t& x, const u32x4_t& y) {
+  if constexpr (DT == MH_BF16)
+    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(x), "v"(y));
+  else
+    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(x), "v"(y));
+}
 // MFMA with the accumulator in VGPRs and the B operand in AccVGPRs (the wave's resident K / V fragments).  hipcc cannot see that
 // these asm statements are MFMAs, so the wait states it would insert are written out: mfma_settle() between the last MFMA of a chain
 // and the first VALU read of its accumulator (19 wait states cover the longest XDL write -> VALU read rule), mfma_ready() between
@@ -602,7 +611,7 @@ __global__ __launch_bounds__(256, MODE == 3 ? 1 : 2) void attn_bwd2_kv_k(Bwd2Arg
         const u32x4_t pf[2] = {pack8v<DT>(pv), pack8v<DT>(pv + 8)};
         stream_tr_frags<RB, hf * 32, 2 * DBLK>(atdo, [&](auto I, const u32x4_t& fr) {
           constexpr int f = decltype(I)::value;
-          if constexpr (ASM) mfma32a<DT>(accv[f / 2], fr, pf[f % 2]);
+          if constexpr (ASM) mfma32a_w<DT>(accv[f / 2], fr, pf[f % 2]);
           else accv[f / 2] = mfma32v<DT>(fr, pf[f % 2], accv[f / 2]);
         });
       }
@@ -612,7 +621,7 @@ __global__ __launch_bounds__(256, MODE == 3 ? 1 : 2) void attn_bwd2_kv_k(Bwd2Arg
         const u32x4_t dsf[2] = {pack8v<DT>(pv), pack8v<DT>(pv + 8)};
         stream_tr_frags<RB, hf * 32, 2 * DBLK>(atq, [&](auto I, const u32x4_t& fr) {
           constexpr int f = decltype(I)::value;
-          if constexpr (ASM) mfma32a<DT>(acck[f / 2], fr, dsf[f % 2]);
+          if constexpr (ASM) mfma32a_w<DT>(acck[f / 2], fr, dsf[f % 2]);
           else acck[f / 2] = mfma32v<DT>(fr, dsf[f % 2], acck[f / 2]);
         });
       }

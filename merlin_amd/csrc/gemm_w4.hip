@@ -68,6 +68,10 @@ __device__ __forceinline__ void mfma_acc(f32x4_t& c, const u32x4& a, const u32x4
   else
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
+// The last K-loop iteration ends with this (hipcc moves it onto the loop's exit edge): 20 wait states between the last asm MFMA and the
+// register copies hipcc places at the loop exit to rearrange the accumulators for the epilogue.  Those copies come BEFORE any statement
+// after the loop (its s_nops have only a "memory" clobber), one MFMA behind the MFMA that writes them (tests/test_kernel_hazards_cpu.py).
+__device__ __forceinline__ void mfma_settle_exit() { asm volatile("s_nop 15\n\ts_nop 3" ::: "memory"); }
 
 constexpr int W4_PART = 256 * 128;     // 32 KiB: 256 rows x 64 k
 constexpr int W4_UNIT = 2 * W4_PART;   // A part + B part of one K-tile
@@ -795,6 +799,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, char* smem, int tm, i
       phase_o(S0{}, t);
       phase_e(S1{}, t + 1);
       phase_o(S1{}, t + 1);
+      if (t + 2 >= nk) mfma_settle_exit();
     }
   } else {
     using S2 = integral_constant<int, 2>;
@@ -807,6 +812,7 @@ __device__ __forceinline__ void w4_tile(const GemmArgs& g, char* smem, int tm, i
       phase_o(S1{}, t + 1);
       phase_e(S2{}, t + 2);
       phase_o(S2{}, t + 2);
+      if (t + 3 >= nk) mfma_settle_exit();
     }
   }
   // the s_nops cover the MFMA -> accumulator-read hazard that the compiler cannot see through the inline-asm MFMAs
@@ -1022,6 +1028,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_f8(GemmArgs g) {
   for (int t = 0; t < nk; t += 2) {  // nk is even (host)
     tile(I0{}, t);
     tile(I1{}, t + 1);
+    if (t + 2 >= nk) mfma_settle_exit();
   }
   asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 

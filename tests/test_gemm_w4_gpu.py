@@ -249,3 +249,124 @@ def test_w4_half_tiles_are_bit_identical_to_the_256_row_tiles(ops, dtype, M):
         assert torch.isfinite(h.float()).all(), nm
         assert torch.equal(f, h), (nm, float((f.float() - h.float()).abs().max()))
     assert relerr(half[0], a.float() @ w.float().t()) < 3 * EPS16[dtype]
+
+
+# ---- the 4-wave fp8 kernel element by element: every epilogue kind against the fp64 product of the dequantised operands --------------------------
+# Per element, |got - want| <= ulp(want) in the output type + C_ACC 2^-24 sum_k |a_k b_k|, carried through the element-wise op (its input
+# errors times the op's partial derivatives, + C_OP 2^-24 times the magnitude of the op's terms for its own fp32 arithmetic, + TINY_OP where
+# that arithmetic flushes a result below ~1e-35 to zero).  C_ACC is not the fp32 figure: the scaled fp8 MFMA sums a 128-k block's products
+# at less than fp32 precision.  On an MI355X the parent commit's kernel and this one gave identical values with errors up to ~140 2^-24
+# sum|ab| (K = 256, fp32 store; 16 failed there).  A bound relative to the tensor's max would hide an error confined to a few accumulator
+# registers of every tile (the loop-exit copies of tests/test_kernel_hazards_cpu.py); this one does not: one MFMA's 128-k contribution
+# missing from an element is typically ~sqrt(128) rms|ab|, above 2.5e4 2^-24 sum|ab| (50 x the bound) at every shape below.
+C_ACC = 512
+C_OP = 64
+TINY_OP = 2.0 ** -100
+U24 = 2.0 ** -24
+_MANT = {torch.bfloat16: 7, torch.float16: 10, torch.float32: 23}
+_TINY = {torch.bfloat16: 2.0 ** -133, torch.float16: 2.0 ** -24, torch.float32: 2.0 ** -149}
+
+# (M, N, K): the smallest admitted K (256: two 128-byte K-tiles, one loop iteration), K = 4096 and K = 11008, with M and N on and off the 256-row /
+# column tile edges; the last one is 16 x 16 = 256 tiles (fills the chip)
+F8_SHAPES = [(256, 512, 256), (300, 264, 256), (520, 776, 4096), (300, 520, 11008), (4096, 4096, 4096)]
+
+
+def _ulp(x, dtype):
+    _, e = torch.frexp(x.abs())
+    return torch.ldexp(torch.ones_like(x), (e - 1 - _MANT[dtype]).to(torch.int32)).clamp_min(_TINY[dtype])
+
+
+def _deq64(q8):
+    return q8[0].view(torch.float8_e4m3fn).double() * q8[1].double()[:, None]
+
+
+def _f8_three(ops, fn):
+    """fn() on the 4-wave fp8 kernel three times: the launches must be bit-identical."""
+    outs = [_with_kernel(ops, 4, fn) for _ in range(3)]
+    for o in outs[1:]:
+        for a, b in zip(outs[0] if isinstance(outs[0], tuple) else (outs[0],), o if isinstance(o, tuple) else (o,)):
+            assert torch.equal(a, b)
+    return outs[0]
+
+
+def _check(name, got, want, err, dtype):
+    """every element: |got - want| <= ulp_dtype(want) + err"""
+    d = (got.double() - want).abs()
+    tol = _ulp(want, dtype) + err
+    assert torch.isfinite(got.float()).all(), name
+    bad = d > tol
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        r, c = divmod(i, want.shape[1])
+        pytest.fail(f"{name}: {int(bad.sum())} of {bad.numel()} elements outside the bound, first [{r}, {c}]: got {float(got.flatten()[i])} "
+                    f"want {float(want.flatten()[i])} bound {float(tol.flatten()[i]):.3e}")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,N,K", F8_SHAPES)
+def test_w4_fp8_every_epilogue_kind_elementwise_vs_fp64(ops, dtype, M, N, K):
+    """gemm_w4_f8<DT, EK> forced: plain, residual, fp32 store, q|k|v + RoPE, gate|up + SwiGLU and the SwiGLU-backward dgrad, each element
+    against the float64 product of the dequantised e4m3 operands (per-row scales) followed by the float64 element-wise op."""
+    x = rnd(M, K, dtype=dtype)
+    a8 = ops.quant_fp8_rows(x)
+    xa = _deq64(a8)
+    xabs = xa.abs()
+
+    def prod(w):  # (fp64 product, the accumulation error bound C_ACC 2^-24 sum_k |a_k b_k|)
+        w8 = ops.quant_fp8_rows(w)
+        wd = _deq64(w8)
+        return w8, xa @ wd.t(), C_ACC * U24 * (xabs @ wd.abs().t())
+
+    # plain, residual, fp32 store
+    w8, ref, e = prod(rnd(N, K, dtype=dtype, seed=1, scale=0.3))
+    _check("plain", _f8_three(ops, lambda: ops.gemm_fp8(a8, w8, out_dtype=dtype)), ref, e, dtype)
+    resid = rnd(M, N, dtype=dtype, seed=2)
+    want = ref + resid.double()
+    _check("residual", _f8_three(ops, lambda: ops.gemm_fp8(a8, w8, out_dtype=dtype, resid=resid)), want, e + C_OP * U24 * (ref.abs() + resid.double().abs()), dtype)
+    got = _f8_three(ops, lambda: ops.gemm_fp8(a8, w8, out=torch.empty(M, N, dtype=torch.float32, device=dev()), dt16=dtype))
+    _check("fp32 store", got, ref, e, torch.float32)
+
+    # q|k|v + RoPE on the fp32 accumulators (D = 128, q and k heads rotated, v not)
+    D, H = 128, max(1, N // 384)
+    S = max(1, M // 2)
+    tab = ops.rope_table(S, D, 10000.0, dev())
+    w8, ref, e = prod(rnd(3 * H * D, K, dtype=dtype, seed=3, scale=0.3))
+    ref, e = ref.view(M, 3, H, D), e.view(M, 3, H, D)
+    pos = torch.arange(M, device=dev()) % S
+    cos, sin = tab[pos, :, 0].double()[:, None, :], tab[pos, :, 1].double()[:, None, :]
+    want, err = ref.clone(), e.clone()
+    for part in (0, 1):
+        lo, hi, elo, ehi = ref[:, part, :, :64], ref[:, part, :, 64:], e[:, part, :, :64], e[:, part, :, 64:]
+        mag = (lo * cos).abs() + (hi * sin).abs() + (hi * cos).abs() + (lo * sin).abs()
+        want[:, part] = torch.cat([lo * cos - hi * sin, hi * cos + lo * sin], -1)
+        err[:, part] = torch.cat([elo * cos.abs() + ehi * sin.abs(), ehi * cos.abs() + elo * sin.abs()], -1) + C_OP * U24 * torch.cat([mag, mag], -1) + TINY_OP
+    got = _f8_three(ops, lambda: ops.gemm_fp8_rope(a8, w8, tab, S, H, D, out_dtype=dtype))
+    _check("rope", got, want.view(M, -1), err.view(M, -1), dtype)
+
+    # gate|up + SwiGLU: gu rounded once from the accumulators, act = silu(gate) * up from the fp32 accumulators
+    ff = N
+    w8, gu, e = prod(rnd(2 * ff, K, dtype=dtype, seed=4, scale=0.3))
+    g, u, eg, eu = gu[:, :ff], gu[:, ff:], e[:, :ff], e[:, ff:]
+    s = torch.sigmoid(g)
+    act = g * s * u
+    dsilu = s * (1 + g * (1 - s))
+    err = (u * dsilu).abs() * eg + (g * s).abs() * eu + C_OP * U24 * act.abs() + TINY_OP
+    gu4, act4 = _f8_three(ops, lambda: ops.gemm_fp8_swiglu_fwd(a8, w8, out_dtype=dtype))
+    _check("swiglu gu", gu4, gu, e, dtype)
+    _check("swiglu act", act4, act, err, dtype)
+
+    # SwiGLU backward: dgu = swiglu_bwd(gu, dy Wd) with dact = dy Wd rounded once to the 16-bit stage
+    gu_in = rnd(M, 2 * ff, dtype=dtype, seed=5)
+    dy8 = ops.quant_fp8_rows(rnd(M, K, dtype=dtype, seed=6, scale=0.5))
+    wd8 = ops.quant_fp8_rows(rnd(ff, K, dtype=dtype, seed=7, scale=0.3))
+    dyd, wdd = _deq64(dy8), _deq64(wd8)
+    dact = dyd @ wdd.t()
+    ed = C_ACC * U24 * (dyd.abs() @ wdd.abs().t()) + _ulp(dact, dtype)
+    g, u = gu_in[:, :ff].double(), gu_in[:, ff:].double()
+    s = torch.sigmoid(g)
+    dsilu = s * (1 + g * (1 - s))
+    want = torch.cat([dact * u * dsilu, dact * g * s], 1)
+    err = torch.cat([(u * dsilu).abs() * ed + C_OP * U24 * (dact * u * s).abs() * (1 + (g * (1 - s)).abs()),
+                     (g * s).abs() * ed + C_OP * U24 * (dact * g * s).abs()], 1) + TINY_OP
+    got = _f8_three(ops, lambda: ops.gemm_fp8_swiglu_bwd(dy8, wd8, gu_in))
+    _check("swiglu backward", got, want, err, dtype)
