@@ -196,7 +196,8 @@ void mh_gemm_w4_half(int mode);
  * first K-tile fetched under the epilogue; 0 = one block per tile (A-B benchmarks). */
 void mh_gemm_persistent(int on);
 /* Tile raster of the 256x256 / 128x128 kernels: output tiles are visited in groups of `gm` tile-rows x all tile-columns, and each XCD
- * gets a contiguous run of the sequence (32 tiles per round = gm x 32/gm): default 4 (A-B benchmarks: 2..16). */
+ * gets a contiguous run of the sequence (32 tiles per round = gm x 32/gm).  gm in 1..64; default 0 = automatic (all tile rows when
+ * there are at most 8, otherwise 4), which any value out of range selects too (A-B benchmarks: 2..16). */
 void mh_gemm_raster_group(int gm);
 
 /* out[C, R_pad] = in[R, C]^T for 16-bit elements (operand re-layout for dgrad / wgrad GEMMs);

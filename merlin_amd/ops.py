@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib as L
-from ._lib import C, f32, i32, i64, p, u64
+from ._lib import C, f32, i32, i64, p, u64  # noqa: F401  (the wrappers: not used here any more, tools/ and tests/ reach them as ops.p, ops.i32, ...)
 
 EPI_BIAS, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_ACCUM, EPI_OUT_F32 = L.EPI_BIAS, L.EPI_QUICK_GELU, L.EPI_RESIDUAL, L.EPI_ACCUM, L.EPI_OUT_F32
 
@@ -85,13 +85,31 @@ def _rowmajor(t: torch.Tensor):
 
 
 def arch_ok(dev: int = 0) -> bool:
-    return bool(L.lib().mh_arch_ok(i32(dev)))
+    return bool(L.lib().mh_arch_ok(dev))
 
 
 # ---------------------------------------------------------------------------------------------
 SKINNY_SPLITK = os.environ.get("MH_SKINNY_SPLITK", "1") != "0"  # A/B switch
 SKINNY_SPLITK_ALL = os.environ.get("MH_SKINNY_SPLITK", "1") == "2"  # fp16 too (default: bf16 only, see _skinny_splitk_ok)
 SKINNY_MAX_ROWS = 4096
+
+
+def _epilogue(bias, act, resid, accum, out):
+    """-> (MH_EPI_* flag word of a GEMM launch, row stride of resid)."""
+    epi = 0
+    if bias is not None:
+        epi |= EPI_BIAS
+    if act == "quick_gelu":
+        epi |= EPI_QUICK_GELU
+    ldr = 0
+    if resid is not None:
+        epi |= EPI_RESIDUAL
+        ldr = _rowmajor(resid)
+    if accum:
+        epi |= EPI_ACCUM
+    if out.dtype == torch.float32:
+        epi |= EPI_OUT_F32
+    return epi, ldr
 
 
 def gemm_nt(a, b, *, out=None, bias=None, resid=None, act=None, accum=False, out_f32=False, n=None, a_t=False, b_t=False):
@@ -113,37 +131,21 @@ def gemm_nt(a, b, *, out=None, bias=None, resid=None, act=None, accum=False, out
         assert not accum
         out = torch.empty(M, N, dtype=torch.float32 if out_f32 else a.dtype, device=a.device)
     ldc = _rowmajor(out)
-    epi = 0
-    if bias is not None:
-        epi |= EPI_BIAS
-    if act == "quick_gelu":
-        epi |= EPI_QUICK_GELU
-    elif act is not None:
+    if act not in (None, "quick_gelu"):
         raise ValueError(act)
-    ldr = 0
-    if resid is not None:
-        epi |= EPI_RESIDUAL
-        ldr = _rowmajor(resid)
-    if accum:
-        epi |= EPI_ACCUM
-    if out.dtype == torch.float32:
-        epi |= EPI_OUT_F32
-    else:
-        assert out.dtype == a.dtype
+    epi, ldr = _epilogue(bias, act, resid, accum, out)
+    assert out.dtype in (torch.float32, a.dtype)
     # short sequences (a single 613-token example, a prompt's prefill): few output tiles and a long contraction -> split K over
     # several blocks per tile, the epilogue applied by the reduce pass (profiles/r03_skinny_gemm.txt)
     splits = 1
     if _skinny_splitk_ok(a.dtype) and M <= SKINNY_MAX_ROWS and N % 4 == 0 and ldc % 4 == 0:
-        splits = int(L.lib().mh_gemm_splitk_max(i32(M), i32(N), i32(K)))
+        splits = int(L.lib().mh_gemm_splitk_max(M, N, K))
     with _timed("gemm_nt", 2.0 * M * N * K, 2.0 * (M * K + N * K) + float(out.element_size()) * M * N):
         if splits > 1:
             ws = _splitk_workspace(a.device, splits * M * N)
-            L.check(L.lib().mh_gemm_splitk_epi(p(a), i64(lda), i32(int(a_t)), p(b), i64(ldb), i32(int(b_t)), p(out), i64(ldc), p(bias), p(resid),
-                                               i64(ldr), i32(M), i32(N), i32(K), i32(dt_of(a)), i32(epi), i32(splits), p(ws), _stream()),
-                    "mh_gemm_splitk_epi")
+            L.call("mh_gemm_splitk_epi", a, lda, int(a_t), b, ldb, int(b_t), out, ldc, bias, resid, ldr, M, N, K, dt_of(a), epi, splits, ws, _stream())
         else:
-            L.check(L.lib().mh_gemm(p(a), i64(lda), i32(int(a_t)), p(b), i64(ldb), i32(int(b_t)), p(out), i64(ldc), p(bias), p(resid),
-                                    i64(ldr), i32(M), i32(N), i32(K), i32(dt_of(a)), i32(epi), _stream()), "mh_gemm")
+            L.call("mh_gemm", a, lda, int(a_t), b, ldb, int(b_t), out, ldc, bias, resid, ldr, M, N, K, dt_of(a), epi, _stream())
     return out
 
 
@@ -159,9 +161,8 @@ def gemv(x, w, out=None, resid=None, out_f32=False, n=None):
         mm = min(step, M - m0)
         xs, os_ = x[m0:m0 + mm], out[m0:m0 + mm]
         rs = resid[m0:m0 + mm] if resid is not None else None
-        L.check(L.lib().mh_gemv(p(xs), i64(_rowmajor(xs)), p(w), i64(_rowmajor(w)), p(os_), i64(_rowmajor(os_)), p(rs),
-                                i64(_rowmajor(rs) if rs is not None else 0), i32(mm), i32(N), i32(K), i32(dt_of(x)),
-                                i32(int(out.dtype == torch.float32)), _stream()), "mh_gemv")
+        L.call("mh_gemv", xs, _rowmajor(xs), w, _rowmajor(w), os_, _rowmajor(os_), rs, _rowmajor(rs) if rs is not None else 0, mm, N, K, dt_of(x),
+               int(out.dtype == torch.float32), _stream())
     return out
 
 
@@ -174,8 +175,7 @@ def gemv_swiglu(x, wgu, out=None):
     if not _gemv_fused_rows_ok(M, K):
         return swiglu_fwd(gemv(x, wgu), out=out)
     out = torch.empty(M, ff, dtype=x.dtype, device=x.device) if out is None else out
-    L.check(L.lib().mh_gemv_swiglu(p(x), i64(_rowmajor(x)), p(wgu), i64(_rowmajor(wgu)), p(out), i64(_rowmajor(out)), i32(M), i32(ff), i32(K),
-                                   i32(dt_of(x)), _stream()), "mh_gemv_swiglu")
+    L.call("mh_gemv_swiglu", x, _rowmajor(x), wgu, _rowmajor(wgu), out, _rowmajor(out), M, ff, K, dt_of(x), _stream())
     return out
 
 
@@ -194,8 +194,7 @@ def gemv_norm(x, norm_w, eps, w, swiglu=False, out=None):
     ff = N // 2 if swiglu else 0
     assert w.shape[1] == K and x.dtype == w.dtype == norm_w.dtype and x.is_contiguous()
     out = torch.empty(M, ff if swiglu else N, dtype=x.dtype, device=x.device) if out is None else out
-    L.check(L.lib().mh_gemv_norm(p(x), i64(_rowmajor(x)), p(norm_w), f32(eps), p(w), i64(_rowmajor(w)), p(out), i64(_rowmajor(out)), i32(M), i32(N),
-                                 i32(K), i32(ff), i32(dt_of(x)), _stream()), "mh_gemv_norm")
+    L.call("mh_gemv_norm", x, _rowmajor(x), norm_w, eps, w, _rowmajor(w), out, _rowmajor(out), M, N, K, ff, dt_of(x), _stream())
     return out
 
 
@@ -204,7 +203,7 @@ def quant_fp8_b128(w):
     N, K = w.shape
     q = torch.empty(N, K, dtype=torch.uint8, device=w.device)
     sc = torch.empty(N, (K + 127) // 128, dtype=torch.float32, device=w.device)
-    L.check(L.lib().mh_quant_fp8_b128(p(w), i64(_rowmajor(w)), p(q), p(sc), i32(N), i32(K), i32(dt_of(w)), _stream()), "mh_quant_fp8_b128")
+    L.call("mh_quant_fp8_b128", w, _rowmajor(w), q, sc, N, K, dt_of(w), _stream())
     return q, sc
 
 
@@ -221,9 +220,8 @@ def gemv_fp8w(x, qw, out=None, resid=None, out_f32=False, n=None):
         mm = min(step, M - m0)
         xs, os_ = x[m0:m0 + mm], out[m0:m0 + mm]
         rs = resid[m0:m0 + mm] if resid is not None else None
-        L.check(L.lib().mh_gemv_fp8w(p(xs), i64(_rowmajor(xs)), p(q), p(sc), p(os_), i64(_rowmajor(os_)), p(rs),
-                                     i64(_rowmajor(rs) if rs is not None else 0), i32(mm), i32(N), i32(K), i32(dt_of(x)),
-                                     i32(int(out.dtype == torch.float32)), _stream()), "mh_gemv_fp8w")
+        L.call("mh_gemv_fp8w", xs, _rowmajor(xs), q, sc, os_, _rowmajor(os_), rs, _rowmajor(rs) if rs is not None else 0, mm, N, K, dt_of(x),
+               int(out.dtype == torch.float32), _stream())
     return out
 
 
@@ -244,8 +242,7 @@ def gemv_fp8w_norm(x, norm_w, eps, qw, swiglu=False, out=None):
             return gemv_fp8w(x, qw, out=out)
     assert q.shape[1] == K and x.is_contiguous()
     out = torch.empty(M, ff if swiglu else N, dtype=x.dtype, device=x.device) if out is None else out
-    L.check(L.lib().mh_gemv_fp8w_norm(p(x), i64(_rowmajor(x)), p(norm_w if fuse_norm else None), f32(eps), p(q), p(sc), p(out), i64(_rowmajor(out)),
-                                      i32(M), i32(N), i32(K), i32(ff), i32(dt_of(x)), _stream()), "mh_gemv_fp8w_norm")
+    L.call("mh_gemv_fp8w_norm", x, _rowmajor(x), norm_w if fuse_norm else None, eps, q, sc, out, _rowmajor(out), M, N, K, ff, dt_of(x), _stream())
     return out
 
 
@@ -264,9 +261,8 @@ def gemv_qkv_rope(x, norm_w, eps, w, table, pos, kcache, vcache, H, D, rope_pos=
     assert x.is_contiguous() and pos.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
     qkv = torch.empty(M, 3 * H * D, dtype=x.dtype, device=x.device)
     wq, sc = (w if fp8 else (None, None))
-    L.check(L.lib().mh_gemv_qkv_rope(p(x), i64(_rowmajor(x)), p(norm_w), f32(eps), p(None if fp8 else w), i64(0 if fp8 else _rowmajor(w)), p(wq), p(sc),
-                                     p(qkv), i64(_rowmajor(qkv)), i32(M), i32(K), i32(dt_of(x)), p(table), p(pos), p(rope_pos), p(kcache), p(vcache),
-                                     i32(H), i32(D), i32(kcache.shape[1]), _stream()), "mh_gemv_qkv_rope")
+    L.call("mh_gemv_qkv_rope", x, _rowmajor(x), norm_w, eps, None if fp8 else w, 0 if fp8 else _rowmajor(w), wq, sc, qkv, _rowmajor(qkv), M, K, dt_of(x), table,
+           pos, rope_pos, kcache, vcache, H, D, kcache.shape[1], _stream())
     return qkv
 
 
@@ -276,8 +272,7 @@ def decode_rope_append(qkv, table, pos, kcache, vcache, H, D, rope_pos=None):
     B = qkv.shape[0]
     assert qkv.is_contiguous() and pos.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
     assert rope_pos is None or rope_pos.dtype == torch.int32
-    L.check(L.lib().mh_decode_rope_append(p(qkv), p(table), p(pos), p(rope_pos), p(kcache), p(vcache), i32(B), i32(H), i32(D),
-                                          i32(kcache.shape[1]), i32(dt_of(qkv)), _stream()), "mh_decode_rope_append")
+    L.call("mh_decode_rope_append", qkv, table, pos, rope_pos, kcache, vcache, B, H, D, kcache.shape[1], dt_of(qkv), _stream())
 
 
 def attn_decode(q, kcache, vcache, lens, H, D, out=None, split_kv=True):
@@ -285,16 +280,15 @@ def attn_decode(q, kcache, vcache, lens, H, D, out=None, split_kv=True):
     B = q.shape[0]
     out = torch.empty(B, H * D, dtype=q.dtype, device=q.device) if out is None else out
     Smax = kcache.shape[1]
-    splits = int(L.lib().mh_attn_decode_splits(i32(B), i32(H), i32(Smax)))
+    splits = int(L.lib().mh_attn_decode_splits(B, H, Smax))
     ws = torch.empty(B * H * splits * (D + 2), dtype=torch.float32, device=q.device) if (splits > 1 and split_kv) else None
-    L.check(L.lib().mh_attn_decode(p(q), i64(q.stride(0)), p(kcache), p(vcache), p(out), p(lens), i32(B), i32(H), i32(D),
-                                   i32(Smax), p(ws), i32(dt_of(q)), _stream()), "mh_attn_decode")
+    L.call("mh_attn_decode", q, q.stride(0), kcache, vcache, out, lens, B, H, D, Smax, ws, dt_of(q), _stream())
     return out
 
 
 def attn_decode_fused_merge(on: bool):
     """A/B switch: split-KV partials merged by a second launch (default) or by the last block of a (b, h) to finish."""
-    L.lib().mh_attn_decode_fused_merge(i32(1 if on else 0))
+    L.lib().mh_attn_decode_fused_merge(1 if on else 0)
 
 
 _splitk_ws = {}
@@ -370,9 +364,8 @@ def _wgrad_call(dy, x, out, accum, splits):
     T, M = dy.shape
     N = x.shape[1]
     ws = _splitk_workspace(dy.device, splits * M * N) if splits > 1 else None
-    L.check(L.lib().mh_gemm_splitk(p(dy), i64(_rowmajor(dy)), i32(1), p(x), i64(_rowmajor(x)), i32(1), p(out), i64(_rowmajor(out)), i32(M), i32(N),
-                                   i32(T), i32(dt_of(dy)), i32(int(accum)), i32(int(out.dtype == torch.float32)), i32(splits), p(ws),
-                                   _stream()), "mh_gemm_splitk")
+    L.call("mh_gemm_splitk", dy, _rowmajor(dy), 1, x, _rowmajor(x), 1, out, _rowmajor(out), M, N, T, dt_of(dy), int(accum), int(out.dtype == torch.float32),
+           splits, ws, _stream())
 
 
 def wgrad_tn(dy, x, out, accum):
@@ -385,7 +378,7 @@ def wgrad_tn(dy, x, out, accum):
     with _timed("gemm_nt", 2.0 * M * N * T, 2.0 * (M * T + N * T + M * N)):
         plan = _tail_plan(M, N, T)
         if plan is None:
-            _wgrad_call(dy, x, out, accum, int(L.lib().mh_gemm_splitk_max(i32(M), i32(N), i32(T))))
+            _wgrad_call(dy, x, out, accum, int(L.lib().mh_gemm_splitk_max(M, N, T)))
         else:
             axis, cut, sp = plan
             if axis == "m":
@@ -428,7 +421,7 @@ def wgrad_tn_grouped(problems, accum, force=False):
             flops += 2.0 * dy.shape[1] * x.shape[1] * T
             nbytes += 2.0 * (dy.shape[1] * T + x.shape[1] * T + dy.shape[1] * x.shape[1])
         with _timed("gemm_nt", flops, nbytes):
-            rc = L.lib().mh_wgrad_grouped(arr, i32(len(problems)), i32(T), i32(dt_of(problems[0][0])), _stream())
+            rc = L.launch("mh_wgrad_grouped", arr, len(problems), T, dt_of(problems[0][0]), _stream())
         if rc == 0:
             return
         if rc != -4:  # MH_ERR_SHAPE = "not for this kernel": per-problem launches below; anything else is an error
@@ -444,8 +437,7 @@ def gemm_nt_rope(a, b, table, S, H, D, out=None):
     assert N == 3 * H * D and b.shape[1] == K and a.dtype == b.dtype
     out = torch.empty(M, N, dtype=a.dtype, device=a.device) if out is None else out
     with _timed("gemm_nt", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N)):
-        L.check(L.lib().mh_gemm_nt_rope(p(a), i64(_rowmajor(a)), p(b), i64(_rowmajor(b)), p(out), i64(_rowmajor(out)), i32(M), i32(N),
-                                        i32(K), i32(dt_of(a)), p(table), i32(S), i32(D), i32(2 * H * D), _stream()), "mh_gemm_nt_rope")
+        L.call("mh_gemm_nt_rope", a, _rowmajor(a), b, _rowmajor(b), out, _rowmajor(out), M, N, K, dt_of(a), table, S, D, 2 * H * D, _stream())
     return out
 
 
@@ -456,8 +448,7 @@ def gemm_swiglu_fwd(x, wgu):
     gu = torch.empty(M, 2 * ff, dtype=x.dtype, device=x.device)
     act = torch.empty(M, ff, dtype=x.dtype, device=x.device)
     with _timed("gemm_nt", 2.0 * M * 2 * ff * K, 2.0 * (M * K + 2 * ff * K + 3 * M * ff)):
-        L.check(L.lib().mh_gemm_swiglu_fwd(p(x), i64(_rowmajor(x)), p(wgu), i64(_rowmajor(wgu)), p(gu), i64(2 * ff), p(act), i64(ff),
-                                           i32(M), i32(ff), i32(K), i32(dt_of(x)), _stream()), "mh_gemm_swiglu_fwd")
+        L.call("mh_gemm_swiglu_fwd", x, _rowmajor(x), wgu, _rowmajor(wgu), gu, 2 * ff, act, ff, M, ff, K, dt_of(x), _stream())
     return gu, act
 
 
@@ -469,8 +460,7 @@ def gemm_swiglu_bwd(dy, wd, gu):
     assert wd.shape[0] == K and gu.shape == (M, 2 * ff)
     dgu = torch.empty_like(gu)
     with _timed("gemm_nt", 2.0 * M * ff * K, 2.0 * (M * K + ff * K + 4 * M * ff)):
-        L.check(L.lib().mh_gemm_swiglu_bwd(p(dy), i64(_rowmajor(dy)), p(wd), i64(_rowmajor(wd)), p(gu), i64(_rowmajor(gu)), p(dgu),
-                                           i64(_rowmajor(dgu)), i32(M), i32(ff), i32(K), i32(dt_of(dy)), _stream()), "mh_gemm_swiglu_bwd")
+        L.call("mh_gemm_swiglu_bwd", dy, _rowmajor(dy), wd, _rowmajor(wd), gu, _rowmajor(gu), dgu, _rowmajor(dgu), M, ff, K, dt_of(dy), _stream())
     return dgu
 
 
@@ -481,8 +471,7 @@ def gemm_gelu_fwd(x, w1, bias):
     f1 = torch.empty(M, N, dtype=x.dtype, device=x.device)
     a = torch.empty(M, N, dtype=x.dtype, device=x.device)
     with _timed("gemm_nt", 2.0 * M * N * K, 2.0 * (M * K + N * K + 2 * M * N)):
-        L.check(L.lib().mh_gemm_gelu_fwd(p(x), i64(_rowmajor(x)), p(w1), i64(_rowmajor(w1)), p(bias), p(f1), i64(N), p(a), i64(N), i32(M), i32(N), i32(K),
-                                         i32(dt_of(x)), _stream()), "mh_gemm_gelu_fwd")
+        L.call("mh_gemm_gelu_fwd", x, _rowmajor(x), w1, _rowmajor(w1), bias, f1, N, a, N, M, N, K, dt_of(x), _stream())
     return f1, a
 
 
@@ -493,8 +482,7 @@ def gemm_gelu_bwd(dy, w2, f1):
     assert w2.shape[0] == K and f1.shape == (M, N)
     df1 = torch.empty_like(f1)
     with _timed("gemm_nt", 2.0 * M * N * K, 2.0 * (M * K + N * K + 2 * M * N)):
-        L.check(L.lib().mh_gemm_gelu_bwd(p(dy), i64(_rowmajor(dy)), p(w2), i64(_rowmajor(w2)), p(f1), i64(_rowmajor(f1)), p(df1), i64(_rowmajor(df1)),
-                                         i32(M), i32(N), i32(K), i32(dt_of(dy)), _stream()), "mh_gemm_gelu_bwd")
+        L.call("mh_gemm_gelu_bwd", dy, _rowmajor(dy), w2, _rowmajor(w2), f1, _rowmajor(f1), df1, _rowmajor(df1), M, N, K, dt_of(dy), _stream())
     return df1
 
 
@@ -503,7 +491,7 @@ def quant_fp8_rows(x, k_pad=None):
     R, K = x.shape
     q = torch.zeros(R, k_pad, dtype=torch.uint8, device=x.device) if (k_pad is not None and k_pad > K) else torch.empty(R, K, dtype=torch.uint8, device=x.device)
     sc = torch.empty(R, dtype=torch.float32, device=x.device)
-    L.check(L.lib().mh_quant_fp8_rows(p(x), i64(_rowmajor(x)), p(q), i64(q.stride(0)), p(sc), i32(R), i32(K), i32(dt_of(x)), _stream()), "mh_quant_fp8_rows")
+    L.call("mh_quant_fp8_rows", x, _rowmajor(x), q, q.stride(0), sc, R, K, dt_of(x), _stream())
     return q, sc
 
 
@@ -528,7 +516,7 @@ def quant_fp8_rows_e4(w):
     q = torch.empty(N, K, dtype=torch.uint8, device=w.device)
     sc = torch.empty(N, dtype=torch.float32, device=w.device)
     ex = _exp_image(N, K, w.device)
-    L.check(L.lib().mh_quant_fp8_rows_e4(p(w), i64(_rowmajor(w)), p(q), p(sc), p(ex), i32(N), i32(K), i32(dt_of(w)), _stream()), "mh_quant_fp8_rows_e4")
+    L.call("mh_quant_fp8_rows_e4", w, _rowmajor(w), q, sc, ex, N, K, dt_of(w), _stream())
     return q, sc, ex
 
 
@@ -542,8 +530,7 @@ def quant_fp8_rows_t_e4(w):
     ws = _amax_ws.get((w.device, C_))
     if ws is None:
         ws = _amax_ws[(w.device, C_)] = torch.empty(C_, dtype=torch.int32, device=w.device)
-    L.check(L.lib().mh_quant_fp8_rows_t_e4(p(w), i64(_rowmajor(w)), p(qt), i64(Rp), p(sc), p(ex), p(ws), i32(R), i32(C_), i32(dt_of(w)), _stream()),
-            "mh_quant_fp8_rows_t_e4")
+    L.call("mh_quant_fp8_rows_t_e4", w, _rowmajor(w), qt, Rp, sc, ex, ws, R, C_, dt_of(w), _stream())
     return qt, sc, ex
 
 
@@ -557,8 +544,7 @@ def quant_fp8_rows_t(x):
     ws = _amax_ws.get((x.device, C_))
     if ws is None:
         ws = _amax_ws[(x.device, C_)] = torch.empty(C_, dtype=torch.int32, device=x.device)
-    L.check(L.lib().mh_quant_fp8_rows_t(p(x), i64(_rowmajor(x)), p(qt), i64(Rp), p(sc), p(ws), i32(R), i32(C_), i32(dt_of(x)), _stream()),
-            "mh_quant_fp8_rows_t")
+    L.call("mh_quant_fp8_rows_t", x, _rowmajor(x), qt, Rp, sc, ws, R, C_, dt_of(x), _stream())
     return qt, sc
 
 
@@ -582,16 +568,14 @@ def quant_fp8_both(x, c_pad=None, amax=None):
     sc = torch.empty(C_, dtype=torch.float32, device=x.device)
     if amax is not None:
         assert amax.dtype == torch.int32 and amax.numel() == R + C_ and amax.is_contiguous()
-        L.check(L.lib().mh_quant_fp8_rows_and_t_pre(p(x), i64(_rowmajor(x)), p(q), i64(q.stride(0)), p(sr), p(qt), i64(Rp), p(sc), p(amax), i32(R), i32(C_),
-                                                    i32(dt_of(x)), _stream()), "mh_quant_fp8_rows_and_t_pre")
+        L.call("mh_quant_fp8_rows_and_t_pre", x, _rowmajor(x), q, q.stride(0), sr, qt, Rp, sc, amax, R, C_, dt_of(x), _stream())
         return (q, sr), (qt, sc)
     ws = _both_ws.get((x.device, R + C_))
     if ws is None:
         if len(_both_ws) > 16:
             _both_ws.clear()
         ws = _both_ws[(x.device, R + C_)] = torch.empty(R + C_, dtype=torch.int32, device=x.device)
-    L.check(L.lib().mh_quant_fp8_rows_and_t(p(x), i64(_rowmajor(x)), p(q), i64(q.stride(0)), p(sr), p(qt), i64(Rp), p(sc), p(ws), i32(R), i32(C_),
-                                            i32(dt_of(x)), _stream()), "mh_quant_fp8_rows_and_t")
+    L.call("mh_quant_fp8_rows_and_t", x, _rowmajor(x), q, q.stride(0), sr, qt, Rp, sc, ws, R, C_, dt_of(x), _stream())
     return (q, sr), (qt, sc)
 
 
@@ -602,8 +586,8 @@ def quant_fp8_t_from_rows(x, row_scales):
     Rp = round_up(R, 128)
     qt = torch.empty(C_, Rp, dtype=torch.uint8, device=x.device)
     sc = torch.empty(C_, dtype=torch.float32, device=x.device)
-    L.check(L.lib().mh_max_to_vec(p(row_scales), i32(row_scales.numel()), p(sc), i32(C_), _stream()), "mh_max_to_vec")
-    L.check(L.lib().mh_quant_fp8_t_scaled(p(x), i64(_rowmajor(x)), p(qt), i64(Rp), p(sc), i32(R), i32(C_), i32(dt_of(x)), _stream()), "mh_quant_fp8_t_scaled")
+    L.call("mh_max_to_vec", row_scales, row_scales.numel(), sc, C_, _stream())
+    L.call("mh_quant_fp8_t_scaled", x, _rowmajor(x), qt, Rp, sc, R, C_, dt_of(x), _stream())
     return qt, sc
 
 
@@ -618,13 +602,11 @@ def gemm_fp8_swiglu_bwd(dy8, wdt8, gu, want_amax=False):
     if want_amax:
         amax = torch.empty(M + 2 * ff, dtype=torch.int32, device=gu.device)
         with _timed("gemm_fp8", 2.0 * M * ff * K):
-            L.check(L.lib().mh_gemm_fp8_swiglu_bwd_amax(p(qa), i64(qa.stride(0)), p(sa), p(qb), i64(qb.stride(0)), p(sb), p(eb), p(gu), i64(_rowmajor(gu)),
-                                                        p(dgu), i64(_rowmajor(dgu)), p(amax), i32(M), i32(ff), i32(K), i32(dt_of(gu)), _stream()),
-                    "mh_gemm_fp8_swiglu_bwd_amax")
+            L.call("mh_gemm_fp8_swiglu_bwd_amax", qa, qa.stride(0), sa, qb, qb.stride(0), sb, eb, gu, _rowmajor(gu), dgu, _rowmajor(dgu), amax, M, ff, K,
+                   dt_of(gu), _stream())
         return dgu, amax
     with _timed("gemm_fp8", 2.0 * M * ff * K):
-        L.check(L.lib().mh_gemm_fp8_swiglu_bwd(p(qa), i64(qa.stride(0)), p(sa), p(qb), i64(qb.stride(0)), p(sb), p(eb), p(gu), i64(_rowmajor(gu)),
-                                               p(dgu), i64(_rowmajor(dgu)), i32(M), i32(ff), i32(K), i32(dt_of(gu)), _stream()), "mh_gemm_fp8_swiglu_bwd")
+        L.call("mh_gemm_fp8_swiglu_bwd", qa, qa.stride(0), sa, qb, qb.stride(0), sb, eb, gu, _rowmajor(gu), dgu, _rowmajor(dgu), M, ff, K, dt_of(gu), _stream())
     return dgu
 
 
@@ -636,25 +618,10 @@ def gemm_fp8(a8, b8, out_dtype=torch.bfloat16, out=None, bias=None, resid=None, 
     N = qb.shape[0]
     assert qb.shape[1] == K
     out = torch.empty(M, N, dtype=out_dtype, device=qa.device) if out is None else out
-    epi = 0
-    if bias is not None:
-        epi |= EPI_BIAS
-    if act == "quick_gelu":
-        epi |= EPI_QUICK_GELU
-    ldr = 0
-    if resid is not None:
-        epi |= EPI_RESIDUAL
-        ldr = _rowmajor(resid)
-    if accum:
-        assert out is not None
-        epi |= EPI_ACCUM
-    dt = dt_of(out)
-    if out.dtype == torch.float32:
-        epi |= EPI_OUT_F32
-        dt = dt_of(dt16)
+    epi, ldr = _epilogue(bias, act, resid, accum, out)
+    dt = dt_of(dt16 if out.dtype == torch.float32 else out)
     with _timed("gemm_fp8", 2.0 * M * N * K):
-        L.check(L.lib().mh_gemm_fp8(p(qa), i64(qa.stride(0)), p(sa), p(qb), i64(qb.stride(0)), p(sb), p(eb), p(out), i64(_rowmajor(out)), p(bias),
-                                    p(resid), i64(ldr), i32(M), i32(N), i32(K), i32(dt), i32(epi), _stream()), "mh_gemm_fp8")
+        L.call("mh_gemm_fp8", qa, qa.stride(0), sa, qb, qb.stride(0), sb, eb, out, _rowmajor(out), bias, resid, ldr, M, N, K, dt, epi, _stream())
     return out
 
 
@@ -665,8 +632,7 @@ def gemm_fp8_rope(a8, b8, table, S, H, D, out_dtype=torch.bfloat16):
     N = qb.shape[0]
     out = torch.empty(M, N, dtype=out_dtype, device=qa.device)
     with _timed("gemm_fp8", 2.0 * M * N * K):
-        L.check(L.lib().mh_gemm_fp8_rope(p(qa), i64(qa.stride(0)), p(sa), p(qb), i64(qb.stride(0)), p(sb), p(eb), p(out), i64(N), i32(M), i32(N),
-                                         i32(K), i32(dt_of(out)), p(table), i32(S), i32(D), i32(2 * H * D), _stream()), "mh_gemm_fp8_rope")
+        L.call("mh_gemm_fp8_rope", qa, qa.stride(0), sa, qb, qb.stride(0), sb, eb, out, N, M, N, K, dt_of(out), table, S, D, 2 * H * D, _stream())
     return out
 
 
@@ -678,8 +644,7 @@ def gemm_fp8_swiglu_fwd(a8, b8, out_dtype=torch.bfloat16):
     gu = torch.empty(M, 2 * ff, dtype=out_dtype, device=qa.device)
     act = torch.empty(M, ff, dtype=out_dtype, device=qa.device)
     with _timed("gemm_fp8", 2.0 * M * 2 * ff * K):
-        L.check(L.lib().mh_gemm_fp8_swiglu_fwd(p(qa), i64(qa.stride(0)), p(sa), p(qb), i64(qb.stride(0)), p(sb), p(eb), p(gu), i64(2 * ff), p(act),
-                                               i64(ff), i32(M), i32(ff), i32(K), i32(dt_of(gu)), _stream()), "mh_gemm_fp8_swiglu_fwd")
+        L.call("mh_gemm_fp8_swiglu_fwd", qa, qa.stride(0), sa, qb, qb.stride(0), sb, eb, gu, 2 * ff, act, ff, M, ff, K, dt_of(gu), _stream())
     return gu, act
 
 
@@ -690,7 +655,7 @@ def transpose16(x, r_pad=None, out=None):
     r_pad = R if r_pad is None else r_pad
     if out is None:
         out = torch.empty(Cc, r_pad, dtype=x.dtype, device=x.device)
-    L.check(L.lib().mh_transpose16(p(x), i64(ldi), p(out), i64(_rowmajor(out)), i32(R), i32(Cc), i32(r_pad), _stream()), "mh_transpose16")
+    L.call("mh_transpose16", x, ldi, out, _rowmajor(out), R, Cc, r_pad, _stream())
     return out
 
 
@@ -698,7 +663,7 @@ def rmsnorm_fwd(x, w, eps, out=None):
     rows, d = x.shape
     assert x.is_contiguous() and w.is_contiguous()
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().mh_rmsnorm_fwd(p(x), p(w), p(out), p(None), i32(rows), i32(d), f32(eps), i32(dt_of(x)), _stream()), "mh_rmsnorm_fwd")
+    L.call("mh_rmsnorm_fwd", x, w, out, None, rows, d, eps, dt_of(x), _stream())
     return out
 
 
@@ -709,16 +674,16 @@ def rmsnorm_fwd_q8(x, w, eps):
     y = torch.empty_like(x)
     q = torch.empty(rows, d, dtype=torch.uint8, device=x.device)
     sc = torch.empty(rows, dtype=torch.float32, device=x.device)
-    L.check(L.lib().mh_rmsnorm_fwd_q8(p(x), p(w), p(y), p(q), p(sc), i32(rows), i32(d), f32(eps), i32(dt_of(x)), _stream()), "mh_rmsnorm_fwd_q8")
+    L.call("mh_rmsnorm_fwd_q8", x, w, y, q, sc, rows, d, eps, dt_of(x), _stream())
     return y, (q, sc)
 
 
 def norm_partials(rows: int) -> int:
-    return int(L.lib().mh_norm_bwd_partials(i32(rows)))
+    return int(L.lib().mh_norm_bwd_partials(rows))
 
 
 def reduce_partials(partial, nblk, d, out, accumulate):
-    L.check(L.lib().mh_reduce_partials(p(partial), i32(nblk), i32(d), p(out), i32(dt_of(out)), i32(int(accumulate)), _stream()), "mh_reduce_partials")
+    L.call("mh_reduce_partials", partial, nblk, d, out, dt_of(out), int(accumulate), _stream())
 
 
 def rmsnorm_bwd(x, w, dy, eps, dx=None, accumulate_dx=False, dw_out=None, dw_accumulate=False, ws=None):
@@ -727,8 +692,7 @@ def rmsnorm_bwd(x, w, dy, eps, dx=None, accumulate_dx=False, dw_out=None, dw_acc
     nblk = norm_partials(rows)
     part = torch.empty(nblk, d, dtype=torch.float32, device=x.device) if ws is None else ws
     dx = torch.empty_like(x) if dx is None else dx
-    L.check(L.lib().mh_rmsnorm_bwd(p(x), p(w), p(dy), p(dx), p(part), i32(rows), i32(d), f32(eps), i32(dt_of(x)),
-                                   i32(int(accumulate_dx)), _stream()), "mh_rmsnorm_bwd")
+    L.call("mh_rmsnorm_bwd", x, w, dy, dx, part, rows, d, eps, dt_of(x), int(accumulate_dx), _stream())
     if dw_out is not None:
         reduce_partials(part, nblk, d, dw_out, dw_accumulate)
     return dx
@@ -738,7 +702,7 @@ def layernorm_fwd(x, w, b, eps, out=None):
     rows, d = x.shape
     assert x.is_contiguous()
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().mh_layernorm_fwd(p(x), p(w), p(b), p(out), i32(rows), i32(d), f32(eps), i32(dt_of(x)), _stream()), "mh_layernorm_fwd")
+    L.call("mh_layernorm_fwd", x, w, b, out, rows, d, eps, dt_of(x), _stream())
     return out
 
 
@@ -748,8 +712,7 @@ def layernorm_bwd(x, w, dy, eps, dx=None, accumulate_dx=False, dw_out=None, db_o
     pw = torch.empty(nblk, d, dtype=torch.float32, device=x.device)
     pb = torch.empty(nblk, d, dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x) if dx is None else dx
-    L.check(L.lib().mh_layernorm_bwd(p(x), p(w), p(dy), p(dx), p(pw), p(pb), i32(rows), i32(d), f32(eps), i32(dt_of(x)),
-                                     i32(int(accumulate_dx)), _stream()), "mh_layernorm_bwd")
+    L.call("mh_layernorm_bwd", x, w, dy, dx, pw, pb, rows, d, eps, dt_of(x), int(accumulate_dx), _stream())
     if dw_out is not None:
         reduce_partials(pw, nblk, d, dw_out, accumulate)
     if db_out is not None:
@@ -762,7 +725,7 @@ def colsum(x, out, accumulate=False):
     rows, d = x.shape
     nblk = norm_partials(rows)
     part = torch.empty(nblk, d, dtype=torch.float32, device=x.device)
-    L.check(L.lib().mh_colsum_partial(p(x), i64(_rowmajor(x)), p(part), i32(rows), i32(d), i32(dt_of(x)), _stream()), "mh_colsum_partial")
+    L.call("mh_colsum_partial", x, _rowmajor(x), part, rows, d, dt_of(x), _stream())
     reduce_partials(part, nblk, d, out, accumulate)
     return out
 
@@ -772,50 +735,50 @@ def swiglu_fwd(gu, out=None):
     ff = ff2 // 2
     assert gu.is_contiguous()
     out = torch.empty(rows, ff, dtype=gu.dtype, device=gu.device) if out is None else out
-    L.check(L.lib().mh_swiglu_fwd(p(gu), p(out), i32(rows), i32(ff), i32(dt_of(gu)), _stream()), "mh_swiglu_fwd")
+    L.call("mh_swiglu_fwd", gu, out, rows, ff, dt_of(gu), _stream())
     return out
 
 
 def swiglu_bwd(gu, dout, dgu=None):
     rows, ff2 = gu.shape
     dgu = torch.empty_like(gu) if dgu is None else dgu
-    L.check(L.lib().mh_swiglu_bwd(p(gu), p(dout), p(dgu), i32(rows), i32(ff2 // 2), i32(dt_of(gu)), _stream()), "mh_swiglu_bwd")
+    L.call("mh_swiglu_bwd", gu, dout, dgu, rows, ff2 // 2, dt_of(gu), _stream())
     return dgu
 
 
 def quick_gelu_fwd(x, out=None):
     out = torch.empty_like(x) if out is None else out
-    L.check(L.lib().mh_quick_gelu_fwd(p(x), p(out), i64(x.numel()), i32(dt_of(x)), _stream()), "mh_quick_gelu_fwd")
+    L.call("mh_quick_gelu_fwd", x, out, x.numel(), dt_of(x), _stream())
     return out
 
 
 def quick_gelu_bwd(x, dy, dx=None):
     dx = torch.empty_like(x) if dx is None else dx
-    L.check(L.lib().mh_quick_gelu_bwd(p(x), p(dy), p(dx), i64(x.numel()), i32(dt_of(x)), _stream()), "mh_quick_gelu_bwd")
+    L.call("mh_quick_gelu_bwd", x, dy, dx, x.numel(), dt_of(x), _stream())
     return dx
 
 
 def add(a, b, out=None):
     out = torch.empty_like(a) if out is None else out
-    L.check(L.lib().mh_add(p(a), p(b), p(out), i64(a.numel()), i32(dt_of(a)), _stream()), "mh_add")
+    L.call("mh_add", a, b, out, a.numel(), dt_of(a), _stream())
     return out
 
 
 def convert(src, dst):
     assert src.numel() == dst.numel() and src.is_contiguous() and dst.is_contiguous()
-    L.check(L.lib().mh_convert(p(src), i32(dt_of(src)), p(dst), i32(dt_of(dst)), i64(src.numel()), _stream()), "mh_convert")
+    L.call("mh_convert", src, dt_of(src), dst, dt_of(dst), src.numel(), _stream())
     return dst
 
 
 def fill_normal_(t, key: int, start: int = 0, sigma: float = 0.02, offset: float = 0.0):
     assert t.is_contiguous()
-    L.check(L.lib().mh_fill_normal(p(t), i64(t.numel()), u64(key), i64(start), f32(sigma), f32(offset), i32(dt_of(t)), _stream()), "mh_fill_normal")
+    L.call("mh_fill_normal", t, t.numel(), key, start, sigma, offset, dt_of(t), _stream())
     return t
 
 
 def rope_table(S, D, theta, device):
     tab = torch.empty(S, D // 2, 2, dtype=torch.float32, device=device)
-    L.check(L.lib().mh_rope_table(p(tab), i32(S), i32(D), f32(theta), _stream()), "mh_rope_table")
+    L.call("mh_rope_table", tab, S, D, theta, _stream())
     return tab
 
 
@@ -823,7 +786,7 @@ def rope_qk_(qkv, table, S, H, D, inverse=False):
     """qkv [T, 3*H*D] (fused q|k|v rows) rotated in place on q and k."""
     T = qkv.shape[0]
     assert qkv.is_contiguous() and qkv.shape[1] == 3 * H * D
-    L.check(L.lib().mh_rope_qk(p(qkv), p(table), i32(T), i32(S), i32(H), i32(D), i32(int(inverse)), i32(dt_of(qkv)), _stream()), "mh_rope_qk")
+    L.call("mh_rope_qk", qkv, table, T, S, H, D, int(inverse), dt_of(qkv), _stream())
     return qkv
 
 
@@ -832,8 +795,7 @@ def attn_fwd2(q, k, v, B, S, H, D, causal, seqlens=None, out=None, lse=None):
     out = torch.empty(B * S, H * D, dtype=q.dtype, device=q.device) if out is None else out
     if lse is None:  # the kernel writes rows < S; the pad rows of a ragged S_pad must read as zeros in the backward
         lse = (torch.empty if S % 64 == 0 else torch.zeros)(B, H, round_up(S, 64), dtype=torch.float32, device=q.device)
-    L.check(L.lib().mh_attn_fwd2(p(q), i64(q.stride(0)), p(k), i64(k.stride(0)), p(v), i64(v.stride(0)), p(out), i64(out.stride(0)),
-                                 p(lse), p(seqlens), i32(B), i32(S), i32(H), i32(D), i32(int(causal)), i32(dt_of(q)), _stream()), "mh_attn_fwd2")
+    L.call("mh_attn_fwd2", q, q.stride(0), k, k.stride(0), v, v.stride(0), out, out.stride(0), lse, seqlens, B, S, H, D, int(causal), dt_of(q), _stream())
     return out, lse
 
 
@@ -878,9 +840,7 @@ def _spill_ws(B, S, H, device):
     (device, stream), shared by every layer (launches on one stream are ordered).  Returns None - the caller then runs the
     seven-product form, which needs no scratch - when the size exceeds ATTN_SPILL_MAX_BYTES (env MH_ATTN_SPILL_MAX_GB, default 12), exceeds a
     quarter of the HBM that is free right now, cannot be allocated (OOM), or a graph capture is in progress.  `release_attn_scratch()` frees it."""
-    lib = L.lib()
-    lib.mh_attn_bwd_spill_bytes.restype = C.c_int64
-    need = int(lib.mh_attn_bwd_spill_bytes(i32(B), i32(S), i32(H)))
+    need = int(L.lib().mh_attn_bwd_spill_bytes(B, S, H))
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     ws = _spill_cache.get(key)
     if ws is None or ws.numel() < need:
@@ -917,15 +877,11 @@ def attn_bwd2(q, k, v, o, do, lse, B, S, H, D, causal, seqlens=None, dq=None, dk
     if causal and D == 128:
         LAST_ATTN_BWD_FORM = "five-product" if ws is not None else "seven-product"  # (tests: which form the last causal D = 128 call took)
     if ws is not None:
-        L.check(L.lib().mh_attn_bwd2_spill(p(q), i64(q.stride(0)), p(k), i64(k.stride(0)), p(v), i64(v.stride(0)), p(o), i64(o.stride(0)),
-                                           p(do), i64(do.stride(0)), p(lse), p(delta), p(dq), i64(dq.stride(0)), p(dk), i64(dk.stride(0)),
-                                           p(dv), i64(dv.stride(0)), p(seqlens), i32(B), i32(S), i32(H), i32(D), i32(int(causal)), p(rope),
-                                           i32(dt_of(q)), p(ws), _stream()), "mh_attn_bwd2_spill")
+        L.call("mh_attn_bwd2_spill", q, q.stride(0), k, k.stride(0), v, v.stride(0), o, o.stride(0), do, do.stride(0), lse, delta, dq, dq.stride(0), dk,
+               dk.stride(0), dv, dv.stride(0), seqlens, B, S, H, D, int(causal), rope, dt_of(q), ws, _stream())
         return dq, dk, dv
-    L.check(L.lib().mh_attn_bwd2(p(q), i64(q.stride(0)), p(k), i64(k.stride(0)), p(v), i64(v.stride(0)), p(o), i64(o.stride(0)),
-                                 p(do), i64(do.stride(0)), p(lse), p(delta), p(dq), i64(dq.stride(0)), p(dk), i64(dk.stride(0)),
-                                 p(dv), i64(dv.stride(0)), p(seqlens), i32(B), i32(S), i32(H), i32(D), i32(int(causal)), p(rope),
-                                 i32(dt_of(q)), _stream()), "mh_attn_bwd2")
+    L.call("mh_attn_bwd2", q, q.stride(0), k, k.stride(0), v, v.stride(0), o, o.stride(0), do, do.stride(0), lse, delta, dq, dq.stride(0), dk, dk.stride(0), dv,
+           dv.stride(0), seqlens, B, S, H, D, int(causal), rope, dt_of(q), _stream())
     return dq, dk, dv
 
 
@@ -938,8 +894,7 @@ def im2col_patches(pixels, ps, kpad, dtype, rows_per_img=None, row0=0, out=None)
     rpi = G * G + row0 if rows_per_img is None else rows_per_img
     cols = torch.empty(N * rpi, kpad, dtype=dtype, device=pixels.device) if out is None else out
     assert cols.shape == (N * rpi, kpad) and cols.is_contiguous()
-    L.check(L.lib().mh_im2col_patches(p(pixels), i32(dt_of(pixels)), p(cols), i32(N), i32(Himg), i32(ps), i32(kpad), i32(rpi), i32(row0),
-                                      i32(dt_of(dtype)), _stream()), "mh_im2col_patches")
+    L.call("mh_im2col_patches", pixels, dt_of(pixels), cols, N, Himg, ps, kpad, rpi, row0, dt_of(dtype), _stream())
     return cols
 
 
@@ -947,8 +902,7 @@ def copy2d(src, dst, accumulate=False):
     """dst[r, c] (=|+=) src[r, c] over src's [rows, cols] block; both row-major 16-bit with their own row strides."""
     rows, cols = src.shape
     assert dst.shape[0] >= rows and dst.shape[1] >= cols and src.dtype == dst.dtype
-    L.check(L.lib().mh_copy2d(p(src), i64(_rowmajor(src)), p(dst), i64(_rowmajor(dst)), i32(rows), i32(cols), i32(int(accumulate)),
-                              i32(dt_of(src)), _stream()), "mh_copy2d")
+    L.call("mh_copy2d", src, _rowmajor(src), dst, _rowmajor(dst), rows, cols, int(accumulate), dt_of(src), _stream())
     return dst
 
 
@@ -960,8 +914,7 @@ def select_tokens(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
     out = torch.empty(R, dtype=torch.int64, device=logits.device)
     u = torch.empty(R, dtype=torch.float32, device=logits.device) if return_u else None
-    L.check(L.lib().mh_select_tokens(p(logits), i64(logits.stride(0)), i32(R), i32(V), i32(int(do_sample)), f32(temperature), i32(top_k),
-                                     f32(top_p), u64(seed & 0xFFFFFFFFFFFFFFFF), i64(step), p(out), p(u), _stream()), "mh_select_tokens")
+    L.call("mh_select_tokens", logits, logits.stride(0), R, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step, out, u, _stream())
     return (out, u) if return_u else out
 
 
@@ -971,7 +924,7 @@ def log_softmax_rows(logits, V=None, row_bias=None):
     V = logits.shape[1] if V is None else V
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
     out = torch.empty(R, V, dtype=torch.float32, device=logits.device)
-    L.check(L.lib().mh_log_softmax_rows(p(logits), i64(logits.stride(0)), i32(R), i32(V), p(out), i64(V), p(row_bias), _stream()), "mh_log_softmax_rows")
+    L.call("mh_log_softmax_rows", logits, logits.stride(0), R, V, out, V, row_bias, _stream())
     return out
 
 
@@ -980,8 +933,7 @@ def gather_rows2d(src, idx, dst, cols=None):
     assert src.dim() == 2 and dst.dim() == 2 and src.stride(1) == 1 and dst.stride(1) == 1 and idx.dtype == torch.int64
     cols = src.shape[1] if cols is None else cols
     es = src.element_size()
-    L.check(L.lib().mh_gather_rows2d(p(src), i64(src.stride(0) * es), p(idx), p(dst), i64(dst.stride(0) * es), i32(idx.numel()),
-                                     i64(cols * es), _stream()), "mh_gather_rows2d")
+    L.call("mh_gather_rows2d", src, src.stride(0) * es, idx, dst, dst.stride(0) * es, idx.numel(), cols * es, _stream())
     return dst
 
 
@@ -994,20 +946,20 @@ def gather_rows(table, idx, out=None):
 def vit_assemble(patch, cls, pos, N, G2):
     d = patch.shape[1]
     x = torch.empty(N * (G2 + 1), d, dtype=patch.dtype, device=patch.device)
-    L.check(L.lib().mh_vit_assemble(p(patch), p(cls), p(pos), p(x), i32(N), i32(G2), i32(d), i32(dt_of(patch)), _stream()), "mh_vit_assemble")
+    L.call("mh_vit_assemble", patch, cls, pos, x, N, G2, d, dt_of(patch), _stream())
     return x
 
 
 def conv3x3_cols(x, N, G, C, stride, rows_per_img, row0):
     Go = (G + 2 - 3) // stride + 1
     cols = torch.empty(N * Go * Go, C * 9, dtype=x.dtype, device=x.device)
-    L.check(L.lib().mh_conv3x3_cols(p(x), p(cols), i32(N), i32(G), i32(C), i32(stride), i32(rows_per_img), i32(row0), _stream()), "mh_conv3x3_cols")
+    L.call("mh_conv3x3_cols", x, cols, N, G, C, stride, rows_per_img, row0, _stream())
     return cols
 
 
 def conv3x3_col2im(dcols, N, G, C, stride, rows_per_img, row0):
     dx = torch.empty(N * rows_per_img, C, dtype=dcols.dtype, device=dcols.device)
-    L.check(L.lib().mh_conv3x3_col2im(p(dcols), p(dx), i32(N), i32(G), i32(C), i32(stride), i32(rows_per_img), i32(row0), i32(dt_of(dcols)), _stream()), "mh_conv3x3_col2im")
+    L.call("mh_conv3x3_col2im", dcols, dx, N, G, C, stride, rows_per_img, row0, dt_of(dcols), _stream())
     return dx
 
 
@@ -1015,7 +967,7 @@ def splice_index(ids, img_offset, P, im_patch, im_start, im_end, err, rows_per_i
     B, S = ids.shape
     assert ids.dtype == torch.int64 and ids.is_contiguous()
     src = torch.empty(B, S, dtype=torch.int32, device=ids.device)
-    L.check(L.lib().mh_splice_index(p(ids), p(img_offset), p(src), p(err), i32(B), i32(S), i32(P), i64(im_patch), i64(im_start), i64(im_end), i32(P if rows_per_img is None else rows_per_img), i32(row0), _stream()), "mh_splice_index")
+    L.call("mh_splice_index", ids, img_offset, src, err, B, S, P, im_patch, im_start, im_end, P if rows_per_img is None else rows_per_img, row0, _stream())
     return src
 
 
@@ -1023,7 +975,7 @@ def mask_lens(mask):
     B, S = mask.shape
     assert mask.is_contiguous() and mask.element_size() == 1
     lens = torch.empty(B, dtype=torch.int32, device=mask.device)
-    L.check(L.lib().mh_mask_lens(p(mask), p(lens), i32(B), i32(S), _stream()), "mh_mask_lens")
+    L.call("mh_mask_lens", mask, lens, B, S, _stream())
     return lens
 
 
@@ -1034,7 +986,7 @@ def norm_fwd_f32in(x32, w, eps, b=None, want_x16=False):
     assert x32.dtype == torch.float32 and x32.is_contiguous() and w.numel() == d
     y = torch.empty(rows, d, dtype=w.dtype, device=x32.device)
     x16 = torch.empty(rows, d, dtype=w.dtype, device=x32.device) if want_x16 else None
-    L.check(L.lib().mh_norm_fwd_f32in(p(x32), p(w), p(b), p(y), p(x16), i32(rows), i32(d), f32(eps), i32(dt_of(w)), _stream()), "mh_norm_fwd_f32in")
+    L.call("mh_norm_fwd_f32in", x32, w, b, y, x16, rows, d, eps, dt_of(w), _stream())
     return y, x16
 
 
@@ -1043,7 +995,7 @@ def vit_assemble_f32(patch32, cls, pos, N, G2):
     d = patch32.shape[1]
     assert patch32.dtype == torch.float32 and patch32.is_contiguous()
     x = torch.empty(N * (G2 + 1), d, dtype=torch.float32, device=patch32.device)
-    L.check(L.lib().mh_vit_assemble_f32(p(patch32), p(cls), p(pos), p(x), i32(N), i32(G2), i32(d), i32(dt_of(cls)), _stream()), "mh_vit_assemble_f32")
+    L.call("mh_vit_assemble_f32", patch32, cls, pos, x, N, G2, d, dt_of(cls), _stream())
     return x
 
 
@@ -1053,7 +1005,7 @@ def layernorm_f32_to_f32(x32, w, b, eps, want_x16=False):
     assert x32.dtype == torch.float32 and x32.is_contiguous()
     y = torch.empty(rows, d, dtype=torch.float32, device=x32.device)
     x16 = torch.empty(rows, d, dtype=w.dtype, device=x32.device) if want_x16 else None
-    L.check(L.lib().mh_layernorm_f32_to_f32(p(x32), p(w), p(b), p(y), p(x16), i32(rows), i32(d), f32(eps), i32(dt_of(w)), _stream()), "mh_layernorm_f32_to_f32")
+    L.call("mh_layernorm_f32_to_f32", x32, w, b, y, x16, rows, d, eps, dt_of(w), _stream())
     return y, x16
 
 
@@ -1063,7 +1015,7 @@ def embed_splice_fwd_f32(ids, src, embed, feats32):
     d = embed.shape[1]
     assert feats32 is None or (feats32.dtype == torch.float32 and feats32.is_contiguous())
     out = torch.empty(T, d, dtype=torch.float32, device=embed.device)
-    L.check(L.lib().mh_embed_splice_fwd_f32(p(ids), p(src), p(embed), p(feats32), p(out), i32(T), i32(d), i32(dt_of(embed)), _stream()), "mh_embed_splice_fwd_f32")
+    L.call("mh_embed_splice_fwd_f32", ids, src, embed, feats32, out, T, d, dt_of(embed), _stream())
     return out
 
 
@@ -1075,7 +1027,7 @@ def mask_unpad_index(mask):
     fwd = torch.empty(B * S, dtype=torch.int64, device=mask.device)
     inv = torch.empty(B * S, dtype=torch.int64, device=mask.device)
     cnt = torch.empty(B, dtype=torch.int32, device=mask.device)
-    L.check(L.lib().mh_mask_unpad_index(p(mask), p(fwd), p(inv), p(cnt), i32(B), i32(S), _stream()), "mh_mask_unpad_index")
+    L.call("mh_mask_unpad_index", mask, fwd, inv, cnt, B, S, _stream())
     return fwd, inv, cnt
 
 
@@ -1084,20 +1036,20 @@ def check_inputs(ids, labels, mask, lens, err, V):
     ref = ids if ids is not None else (labels if labels is not None else mask)
     B, S = ref.shape
     assert err.numel() >= 12 and err.dtype == torch.int32
-    L.check(L.lib().mh_check_inputs(p(ids), p(labels), p(mask), p(lens), p(err), i32(B), i32(S), i32(V), _stream()), "mh_check_inputs")
+    L.call("mh_check_inputs", ids, labels, mask, lens, err, B, S, V, _stream())
 
 
 def embed_splice_fwd(ids, src, embed, feats, out=None):
     T = ids.numel()
     d = embed.shape[1]
     out = torch.empty(T, d, dtype=embed.dtype, device=embed.device) if out is None else out
-    L.check(L.lib().mh_embed_splice_fwd(p(ids), p(src), p(embed), p(feats), p(out), i32(T), i32(d), i32(dt_of(embed)), _stream()), "mh_embed_splice_fwd")
+    L.call("mh_embed_splice_fwd", ids, src, embed, feats, out, T, d, dt_of(embed), _stream())
     return out
 
 
 def embed_splice_bwd(ids, src, dout, dfeats, dembed32):
     T, d = dout.shape
-    L.check(L.lib().mh_embed_splice_bwd(p(ids), p(src), p(dout), p(dfeats), p(dembed32), i32(T), i32(d), i32(dt_of(dout)), _stream()), "mh_embed_splice_bwd")
+    L.call("mh_embed_splice_bwd", ids, src, dout, dfeats, dembed32, T, d, dt_of(dout), _stream())
 
 
 def ce_fwd(logits, labels, V):
@@ -1107,7 +1059,7 @@ def ce_fwd(logits, labels, V):
     row_loss = torch.empty(T, dtype=torch.float32, device=logits.device)
     lse = torch.empty(T, dtype=torch.float32, device=logits.device)
     out2 = torch.empty(4, dtype=torch.float32, device=logits.device)
-    L.check(L.lib().mh_ce_fwd(p(logits), i64(logits.stride(0)), p(labels), p(row_loss), p(lse), p(out2), i32(B), i32(S), i32(V), _stream()), "mh_ce_fwd")
+    L.call("mh_ce_fwd", logits, logits.stride(0), labels, row_loss, lse, out2, B, S, V, _stream())
     return row_loss, lse, out2
 
 
@@ -1115,8 +1067,7 @@ def ce_bwd(logits, labels, lse, out2, V, Vpad, gscale, dtype, out=None):
     B, S = labels.shape
     T = B * S
     out = torch.empty(T, Vpad, dtype=dtype, device=logits.device) if out is None else out
-    L.check(L.lib().mh_ce_bwd(p(logits), i64(logits.stride(0)), p(labels), p(lse), p(out2), p(out), i64(out.stride(0)), i32(B), i32(S),
-                              i32(V), i32(Vpad), f32(gscale), i32(dt_of(dtype)), _stream()), "mh_ce_bwd")
+    L.call("mh_ce_bwd", logits, logits.stride(0), labels, lse, out2, out, out.stride(0), B, S, V, Vpad, gscale, dt_of(dtype), _stream())
     return out
 
 
@@ -1125,36 +1076,33 @@ def ce_bwd_rows(logits, labels, lse, out2, rows, V, Vpad, gscale, dtype):
     S = labels.shape[1]
     n = rows.numel()
     out = torch.empty(n, Vpad, dtype=dtype, device=logits.device)
-    L.check(L.lib().mh_ce_bwd_rows(p(logits), i64(logits.stride(0)), p(labels), p(lse), p(out2), p(out), i64(out.stride(0)), p(rows), i32(n), i32(S),
-                                   i32(V), i32(Vpad), f32(gscale), i32(dt_of(dtype)), _stream()), "mh_ce_bwd_rows")
+    L.call("mh_ce_bwd_rows", logits, logits.stride(0), labels, lse, out2, out, out.stride(0), rows, n, S, V, Vpad, gscale, dt_of(dtype), _stream())
     return out
 
 
 def adamw_(param, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0):
-    L.check(L.lib().mh_adamw(p(param), p(grad), p(m), p(v), i64(param.numel()), f32(lr), f32(beta1), f32(beta2), f32(eps), f32(wd),
-                             i32(step), f32(gscale), i32(dt_of(param)), _stream()), "mh_adamw")
+    L.call("mh_adamw", param, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, dt_of(param), _stream())
 
 
 def adamw_clip_(param, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev):
-    L.check(L.lib().mh_adamw_clip(p(param), p(grad), p(m), p(v), i64(param.numel()), f32(lr), f32(beta1), f32(beta2), f32(eps), f32(wd),
-                                  i32(step), f32(gscale), p(gscale_dev), i32(dt_of(param)), _stream()), "mh_adamw_clip")
+    L.call("mh_adamw_clip", param, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, dt_of(param), _stream())
 
 
 def clip_scale(sumsq_t, gscale, max_norm, out2):
-    L.check(L.lib().mh_clip_scale(p(sumsq_t), f32(gscale), f32(max_norm), p(out2), _stream()), "mh_clip_scale")
+    L.call("mh_clip_scale", sumsq_t, gscale, max_norm, out2, _stream())
 
 
 def sumsq_det(g, partial, out):
-    L.check(L.lib().mh_sumsq_det(p(g), i64(g.numel()), p(partial), p(out), i32(dt_of(g)), _stream()), "mh_sumsq_det")
+    L.call("mh_sumsq_det", g, g.numel(), partial, out, dt_of(g), _stream())
 
 
 def any_nonzero(g, flag):
     """flag (int32[1], zeroed by the caller) |= 1 when any 16-bit element of g is non-zero (exact, on the bit patterns)."""
-    L.check(L.lib().mh_any_nonzero(p(g), i64(g.numel()), p(flag), _stream()), "mh_any_nonzero")
+    L.call("mh_any_nonzero", g, g.numel(), flag, _stream())
 
 
 def sumsq(g, out):
-    L.check(L.lib().mh_sumsq(p(g), i64(g.numel()), p(out), i32(dt_of(g)), _stream()), "mh_sumsq")
+    L.call("mh_sumsq", g, g.numel(), out, dt_of(g), _stream())
 
 
 _gemv_mfma_min = 3
@@ -1164,12 +1112,12 @@ def gemv_mfma_min_rows(rows: int):
     """A/B switch: row count from which gemv / gemv_fp8w use the MFMA kernel (<= 0 restores the measured default, 3; 17 = never)."""
     global _gemv_mfma_min
     _gemv_mfma_min = rows if rows > 0 else 3
-    L.lib().mh_gemv_mfma_min_rows(i32(rows))
+    L.lib().mh_gemv_mfma_min_rows(rows)
 
 
 def gemv_mfma_pair_min_rows(rows16: int, rows_fp8: int):
     """A/B switch: row counts from which the SwiGLU / RoPE-append projections use the MFMA form (<= 0: defaults 6 / 4)."""
-    L.lib().mh_gemv_mfma_pair_min_rows(i32(rows16), i32(rows_fp8))
+    L.lib().mh_gemv_mfma_pair_min_rows(rows16, rows_fp8)
 
 
 def _gemv_rows_per_launch(K):
@@ -1186,47 +1134,47 @@ def _gemv_fused_rows_ok(M, K):
 
 def gemv_ksplit(on: bool):
     """A/B switch: K split over a block's waves in the 1-2 row GEMV at N <= 8192 (default on)."""
-    L.lib().mh_gemv_ksplit(i32(1 if on else 0))
+    L.lib().mh_gemv_ksplit(1 if on else 0)
 
 
 def gemv_mfma_wide(on: bool):
     """A/B switch: 16 instead of 8 waves per block in the MFMA GEMV at N <= 8192 (default on)."""
-    L.lib().mh_gemv_mfma_wide(i32(1 if on else 0))
+    L.lib().mh_gemv_mfma_wide(1 if on else 0)
 
 
 def attn_fwd_pingpong(on):
     """A/B switch of the D = 128 attention forward: 0 / False = attn_fwd2 (default), 1 / True = the ping-pong form (8-wave blocks, SIMD partners in
     opposite phases; csrc/attn_fwd3.hip), 2 = one wave per SIMD with 64 query rows per wave (csrc/attn_fwd4.hip)."""
-    L.lib().mh_attn_fwd_pingpong(i32(int(on)))
+    L.lib().mh_attn_fwd_pingpong(int(on))
 
 
 def attn_bwd_fused_kv(on):
     """A/B switch for dK and dV of the D = 128 attention backward: True / 2 = attn_bwd3_kv_k (default: one kernel, register-staged copies,
     continuous fragment stream), 1 = attn_bwd2_kv_k<MODE 3> (one kernel, LDS-DMA copies: rounds 2-4), False / 0 = two kernels."""
-    L.lib().mh_attn_bwd_fused_kv(i32(2 if on is True else int(on)))
+    L.lib().mh_attn_bwd_fused_kv(2 if on is True else int(on))
 
 
 def gemm_raster_group(gm: int):
-    """A/B switch: tile rows per raster group of the MFMA GEMM kernels (default 4)."""
-    L.lib().mh_gemm_raster_group(i32(gm))
+    """A/B switch: tile rows per raster group of the MFMA GEMM kernels (1..64; default 0 = automatic: every tile row when there are at most 8, else 4; out of range = automatic)."""
+    L.lib().mh_gemm_raster_group(gm)
 
 
 def gemm_persistent(on: bool):
     """A/B switch: persistent launch of the 256-tile GEMM kernels (default on; env MH_GEMM_PERSISTENT=0 turns it off at import)."""
-    L.lib().mh_gemm_persistent(i32(1 if on else 0))
+    L.lib().mh_gemm_persistent(1 if on else 0)
 
 
 def gemm_w4_policy(mask: int):
     """A/B switch: operand layouts the auto selection sends to the 4-wave 256x256 GEMM (bit 0 TN, bit 1 NN, bit 2 NT, bit 3 fp8 NT; default 11)."""
-    L.lib().mh_gemm_w4_policy(i32(mask))
+    L.lib().mh_gemm_w4_policy(mask)
 
 
 def gemm_w4_half(mode: int):
     """128-row block tiles of the 4-wave GEMM for NT products with few rows (short prefills): 0 = never, 1 = auto (default), 2 = wherever the form exists."""
-    L.lib().mh_gemm_w4_half(i32(mode))
+    L.lib().mh_gemm_w4_half(mode)
 
 
 def gemm_force_kernel(which: int):
     """0 = auto, 128 / 256 = force that tile size (tests, A/B benchmarks).  Other codes select the development arms and
     exist only in the dev library (tools/dev_arms/)."""
-    L.lib().mh_gemm_force_kernel(i32(which))
+    L.lib().mh_gemm_force_kernel(which)

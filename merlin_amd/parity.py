@@ -12,7 +12,6 @@ import torch
 
 from . import _lib as L
 from . import ops as O
-from ._lib import f32, i32, i64, p
 from .model.config import head_dim_of
 from .ops import _stream
 
@@ -26,7 +25,7 @@ def _ru(x, m):
 def _split3(x32):
     n = x32.numel()
     hml = torch.empty(3, *x32.shape, dtype=torch.bfloat16, device=x32.device)
-    L.check(L.lib().mh_p32_split3(p(x32), p(hml[0]), p(hml[1]), p(hml[2]), i64(n), _stream()), "mh_p32_split3")
+    L.call("mh_p32_split3", x32, hml[0], hml[1], hml[2], n, _stream())
     return hml[0], hml[1], hml[2]
 
 
@@ -42,19 +41,19 @@ def linear(x32, w, bias=None):
 
 def rmsnorm(x, w, eps):
     y = torch.empty_like(x)
-    L.check(L.lib().mh_p32_rmsnorm(p(x), p(w), p(y), i32(x.shape[0]), i32(x.shape[1]), f32(eps), _stream()), "mh_p32_rmsnorm")
+    L.call("mh_p32_rmsnorm", x, w, y, x.shape[0], x.shape[1], eps, _stream())
     return y
 
 
 def layernorm(x, w, b, eps):
     y = torch.empty_like(x)
-    L.check(L.lib().mh_p32_layernorm(p(x), p(w), p(b), p(y), i32(x.shape[0]), i32(x.shape[1]), f32(eps), _stream()), "mh_p32_layernorm")
+    L.call("mh_p32_layernorm", x, w, b, y, x.shape[0], x.shape[1], eps, _stream())
     return y
 
 
 def _ew(a, b, op, out_shape=None, ff=0):
     y = torch.empty(out_shape if out_shape is not None else a.shape, dtype=torch.float32, device=a.device)
-    L.check(L.lib().mh_p32_elementwise(p(a), p(b), p(y), i64(y.numel()), i32(op), i32(ff), _stream()), "mh_p32_elementwise")
+    L.call("mh_p32_elementwise", a, b, y, y.numel(), op, ff, _stream())
     return y
 
 
@@ -62,8 +61,7 @@ def attention(qkv, B, S, H, D, causal, lens):
     d = H * D
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     o = torch.empty(B * S, d, dtype=torch.float32, device=qkv.device)
-    L.check(L.lib().mh_p32_attention(p(q), i64(q.stride(0)), p(k), i64(k.stride(0)), p(v), i64(v.stride(0)), p(o), i64(d), p(lens), i32(B), i32(S),
-                                     i32(H), i32(D), i32(int(causal)), _stream()), "mh_p32_attention")
+    L.call("mh_p32_attention", q, q.stride(0), k, k.stride(0), v, v.stride(0), o, d, lens, B, S, H, D, int(causal), _stream())
     return o
 
 
@@ -124,13 +122,13 @@ def forward(engine, input_ids, attention_mask, labels, images):
         pix = torch.cat([im.to(dev).float() for im in images], dim=0).contiguous()
         N = pix.shape[0]
         cols = torch.empty(N * Sv, Kpad, dtype=torch.float32, device=dev)
-        L.check(L.lib().mh_p32_im2col(p(pix), p(cols), i32(N), i32(vc.image_size), i32(vc.patch_size), i32(Kpad), i32(Sv), i32(1), _stream()), "mh_p32_im2col")
+        L.call("mh_p32_im2col", pix, cols, N, vc.image_size, vc.patch_size, Kpad, Sv, 1, _stream())
         wpad = torch.zeros(vd, Kpad, dtype=torch.bfloat16, device=dev)
         O.copy2d(W.view(VT + "embeddings.patch_embedding.weight", shape=(vd, K)), wpad)
         patch = linear(cols, wpad)
         x = torch.empty(N * Sv, vd, dtype=torch.float32, device=dev)
-        L.check(L.lib().mh_p32_vit_assemble(p(patch), p(W.view(VT + "embeddings.class_embedding")), p(W.view(VT + "embeddings.position_embedding.weight")),
-                                            p(x), i32(N), i32(G2), i32(vd), _stream()), "mh_p32_vit_assemble")
+        L.call("mh_p32_vit_assemble", patch, W.view(VT + "embeddings.class_embedding"), W.view(VT + "embeddings.position_embedding.weight"), x, N, G2, vd,
+               _stream())
         eps = vc.layer_norm_eps
         x = layernorm(x, W.view(VT + "pre_layrnorm.weight"), W.view(VT + "pre_layrnorm.bias"), eps)
         Hv = vc.num_attention_heads
@@ -149,21 +147,20 @@ def forward(engine, input_ids, attention_mask, labels, images):
         if hasattr(proj, "conv_stride"):
             Go = (G + 2 - 3) // proj.conv_stride + 1
             c32 = torch.empty(N * Go * Go, vd * 9, dtype=torch.float32, device=dev)
-            L.check(L.lib().mh_p32_conv3x3_cols(p(x), p(c32), i32(N), i32(G), i32(vd), i32(proj.conv_stride), i32(Sv), i32(1), _stream()), "mh_p32_conv3x3_cols")
+            L.call("mh_p32_conv3x3_cols", x, c32, N, G, vd, proj.conv_stride, Sv, 1, _stream())
             feats = linear(c32, W.view(wn, shape=(A.params[wn].shape[0], vd * 9)), W.view(bn))
         else:
             feats = linear(x, W.view(wn), W.view(bn))
         assert engine._splice_geometry()[0] * N == feats.shape[0]
     engine._check_errors()
     x = torch.empty(T, d, dtype=torch.float32, device=dev)
-    L.check(L.lib().mh_p32_embed_splice(p(input_ids), p(src), p(W.view("model.embed_tokens.weight")), p(feats), p(x), i64(T), i32(d), _stream()),
-            "mh_p32_embed_splice")
+    L.call("mh_p32_embed_splice", input_ids, src, W.view("model.embed_tokens.weight"), feats, x, T, d, _stream())
     eps = cfg.rms_norm_eps
     for i in range(cfg.num_hidden_layers):
         q = f"model.layers.{i}."
         h1 = rmsnorm(x, W.view(q + "input_layernorm.weight"), eps)
         qkv = linear(h1, W.span(q + "self_attn.q_proj.weight", q + "self_attn.v_proj.weight", (3 * d, d)))
-        L.check(L.lib().mh_p32_rope(p(qkv), p(rope), i64(T), i32(S), i32(H), i32(D), _stream()), "mh_p32_rope")
+        L.call("mh_p32_rope", qkv, rope, T, S, H, D, _stream())
         o = attention(qkv, B, S, H, D, True, lens)
         x2 = _ew(linear(o, W.view(q + "self_attn.o_proj.weight")), x, 0)
         h2 = rmsnorm(x2, W.view(q + "post_attention_layernorm.weight"), eps)

@@ -79,3 +79,131 @@ def test_grouped_wgrad_host_plan_and_struct_layout():
     assert not O.wgrad_group_pays(48 * 577, [(vd, vff)] * 9)                                      # more problems than one launch holds
     assert C.sizeof(O._WgradProblem) == 64
     assert [f[0] for f in O._WgradProblem._fields_] == ["dy", "lddy", "x", "ldx", "out", "ldo", "M", "N", "accumulate", "reserved"]
+
+
+def test_every_declared_symbol_is_typed_from_the_header():
+    import ctypes as C
+
+    from merlin_amd import _lib as L
+
+    lib = L.lib()
+    assert sorted(L.PROTOTYPES) == L.declared_symbols() and len(L.PROTOTYPES) == len(L.declared_symbols())
+    for name, (restype, argtypes) in L.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    n_args = lambda name: len(getattr(lib, name).argtypes)  # noqa: E731
+    assert n_args("mh_version") == 0 and n_args("mh_attn_bwd2_spill") == 28 and n_args("mh_gemm") == 17
+    assert lib.mh_gemm.argtypes[1] is C.c_int64 and lib.mh_gemm.argtypes[2] is C.c_int and lib.mh_gemm.argtypes[-1] is L.DevPtr
+    assert lib.mh_fill_normal.argtypes[2] is C.c_uint64 and lib.mh_fill_normal.argtypes[4] is C.c_float
+    assert lib.mh_gemm.restype is C.c_int and lib.mh_strerror.restype is C.c_char_p and lib.mh_gemm_persistent.restype is None
+    assert lib.mh_attn_bwd_spill_bytes.restype is C.c_int64
+
+
+def test_64_bit_return_value_needs_no_patch():
+    """cfg 5 (B 4, S 8192, H 32): n = S / 128 = 64, n^2 + n units of 16 384 bytes per (batch, head) (csrc/attn_bwd2.hip ds_units_per_bh);
+    read as a C int the value would be 134 217 728."""
+    from merlin_amd import _lib as L
+
+    need = L.lib().mh_attn_bwd_spill_bytes(4, 8192, 32)
+    assert need == 4 * 32 * (64 * 64 + 64) * 16384 == 8724152320 and need > 2 ** 32
+
+
+def test_call_checks_count_and_types_before_the_library_is_entered():
+    """None of these may reach the kernel library: a launch with a wrong argument list would run with a garbage pointer or size."""
+    import ctypes as C
+
+    from merlin_amd import _lib as L
+
+    L.lib()
+    assert len(L.PROTOTYPES["mh_p32_rmsnorm"][1]) == 7  # (x, w, y, rows, d, eps, stream)
+    with pytest.raises(TypeError, match="takes 7 arguments, got 6"):
+        L.call("mh_p32_rmsnorm", None, None, None, 4, 16, 1e-5)
+    with pytest.raises(TypeError, match="takes 7 arguments, got 8"):
+        L.call("mh_p32_rmsnorm", None, None, None, 4, 16, 1e-5, None, None)
+    with pytest.raises(C.ArgumentError):
+        L.call("mh_p32_rmsnorm", None, None, None, 4.0, 16, 1e-5, None)   # a float where the prototype says int
+    with pytest.raises(C.ArgumentError):
+        L.call("mh_p32_rmsnorm", 1.5, None, None, 4, 16, 1e-5, None)      # neither a tensor, None, an address nor a ctypes pointer
+    with pytest.raises(KeyError):
+        L.call("mh_no_such_function")
+
+    class T:  # what the pointer type takes: tensors by data_ptr(), None, addresses, ctypes pointer values and arrays
+        def data_ptr(self):
+            return 0x7F0012345678
+
+    assert L.DevPtr.from_param(T()).value == 0x7F0012345678 and L.DevPtr.from_param(None) is None
+    assert L.DevPtr.from_param(1 << 40).value == 1 << 40
+    v, arr = C.c_void_p(5), (C.c_int64 * 2)()
+    assert L.DevPtr.from_param(v) is v and L.DevPtr.from_param(arr) is arr
+
+
+def test_missing_header_fails_loudly(tmp_path):
+    from merlin_amd import _lib as L
+
+    with pytest.raises(L.MerlinHipError):
+        L._parse_header(str(tmp_path / "nope.h"))
+    bad = tmp_path / "bad.h"
+    bad.write_text("int mh_ok(int a, void* stream);\nint mh_odd(size_t n, void* stream);\n")
+    with pytest.raises(L.MerlinHipError, match="size_t"):  # an unknown C type is an error, not a skipped entry
+        L._parse_header(str(bad))
+    bad.write_text("int mh_ok(int a, void* stream);\nunsigned mh_odd(int n);\n")
+    with pytest.raises(L.MerlinHipError, match="mh_odd"):  # so is a prototype the pattern cannot read
+        L._parse_header(str(bad))
+
+
+def test_constants_equal_the_headers_defines():
+    import re
+
+    from merlin_amd import _lib as L
+    from merlin_amd import ops as O
+
+    d = {k: int(v.strip("()")) for k, v in re.findall(r"#define\s+(MH_\w+)\s+(\(?-?\d+\)?)", open(L.HEADER).read())}
+    assert (L.MH_BF16, L.MH_F16, L.MH_F32) == (d["MH_BF16"], d["MH_F16"], d["MH_F32"]) == (0, 1, 2)
+    got = (O.EPI_BIAS, O.EPI_QUICK_GELU, O.EPI_RESIDUAL, O.EPI_ACCUM, O.EPI_OUT_F32)
+    assert got == (L.EPI_BIAS, L.EPI_QUICK_GELU, L.EPI_RESIDUAL, L.EPI_ACCUM, L.EPI_OUT_F32)
+    assert got == tuple(d["MH_EPI_" + k] for k in ("BIAS", "QUICK_GELU", "RESIDUAL", "ACCUM", "OUT_F32")) == (1, 2, 4, 8, 16)
+
+
+def test_every_call_site_in_the_package_matches_its_prototype():
+    """Static pass over merlin_amd/**/*.py: every L.call / L.launch names a declared symbol with the prototype's argument count, and no
+    launch function (last parameter `void* stream`) is called as an attribute of lib(), past the count check."""
+    import ast
+    import pathlib
+    import re
+
+    from merlin_amd import _lib as L
+
+    hdr = re.sub(r"/\*.*?\*/", "", open(L.HEADER).read(), flags=re.S)
+    launches = set(re.findall(r"\b(mh_\w+)\s*\([^()]*\bvoid\s*\*\s*stream\s*\)", hdr))
+    assert len(launches) > 80 and launches < set(L.PROTOTYPES) and all(L.PROTOTYPES[n][0] is L.C.c_int for n in launches)
+    sites, bad = 0, []
+    for f in (pathlib.Path(__file__).resolve().parents[1] / "merlin_amd").rglob("*.py"):
+        for node in ast.walk(ast.parse(f.read_text())):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)):
+                continue
+            where = f"{f.name}:{node.lineno}"
+            if node.func.attr in ("call", "launch") and isinstance(node.func.value, ast.Name) and node.func.value.id == "L":
+                name = node.args[0].value if node.args and isinstance(node.args[0], ast.Constant) else None
+                sites += 1
+                if name not in L.PROTOTYPES:
+                    bad.append(f"{where}: {name!r} is not declared (the name must be a literal)")
+                elif any(isinstance(a, ast.Starred) for a in node.args) or node.keywords:
+                    bad.append(f"{where}: {name}: starred / keyword arguments cannot be counted")
+                elif len(node.args) - 1 != len(L.PROTOTYPES[name][1]):
+                    bad.append(f"{where}: {name} takes {len(L.PROTOTYPES[name][1])} arguments, {len(node.args) - 1} passed")
+            elif node.func.attr in launches:
+                bad.append(f"{where}: {node.func.attr} launched without L.call")
+            elif node.func.attr.startswith("mh_") and len(node.args) != len(L.PROTOTYPES.get(node.func.attr, (None, node.args))[1]):
+                bad.append(f"{where}: {node.func.attr}: {len(node.args)} arguments passed")
+    assert not bad, "\n".join(bad)
+    assert sites >= 80, sites
+
+
+def test_setters_no_gpu_test_reaches_take_their_typed_arguments():
+    """The four A/B setters no other test calls (host-only: each stores one int), left at their defaults."""
+    from merlin_amd import ops as O
+
+    assert O.gemv_ksplit(True) is None and O.gemm_persistent(True) is None
+    assert O.gemm_w4_policy(11) is None and O.gemm_raster_group(0) is None
+    with pytest.raises(Exception, match="argument 1"):
+        O.gemm_raster_group(2.5)

@@ -42,7 +42,7 @@ for M in [int(a) for a in sys.argv[1:]] or [613, 101, 128, 256, 384, 1024, 2048]
     lg = torch.empty(M, V, dtype=torch.float32, device=dev)
     forms = [("q|k|v + RoPE  [M,12288,4096]", 2.0 * M * 3 * d * d, lambda: [O.gemm_nt_rope(x, w, rope, 4096, 32, 128) for w in wqkv]),
              ("gate|up + SwiGLU [M,22016,4096]", 2.0 * M * 2 * ff * d, lambda: [O.gemm_swiglu_fwd(x, w) for w in wgu]),
-             ("o -> fp32 stream += [M,4096,4096] (one pass)", 2.0 * M * d * d, lambda: [O.L.check(O.L.lib().mh_gemm(O.p(x), O.i64(d), O.i32(0), O.p(w), O.i64(d), O.i32(0), O.p(x32), O.i64(d), None, None, O.i64(0), O.i32(M), O.i32(d), O.i32(d), O.i32(O.dt_of(x)), O.i32(O.EPI_OUT_F32 | O.EPI_ACCUM), O._stream()), "mh_gemm") for w in wo]),
+             ("o -> fp32 stream += [M,4096,4096] (one pass)", 2.0 * M * d * d, lambda: [O.L.call("mh_gemm", x, d, 0, w, d, 0, x32, d, None, None, 0, M, d, d, O.dt_of(x), O.EPI_OUT_F32 | O.EPI_ACCUM, O._stream()) for w in wo]),
              ("lm_head fp32 logits [M,32064,4096]", 2.0 * M * V * d, lambda: [O.gemm_nt(x, wlm, out=lg) for _ in range(L)])]
     for name, fl, fn in forms:
         res = {}

@@ -14,7 +14,6 @@ for (No, Ki) in [(3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096), (4096, 
     for sp in (1, 2, 4, 8):
         ws = torch.empty(sp * No * Ki, device=dev)
         def f():
-            L.check(L.lib().mh_gemm_splitk(O.p(dy), O.i64(No), O.i32(1), O.p(x), O.i64(Ki), O.i32(1), O.p(out), O.i64(Ki), O.i32(No), O.i32(Ki), O.i32(T),
-                                           O.i32(O.dt_of(dy)), O.i32(0), O.i32(0), O.i32(sp), O.p(ws), O._stream()), "x")
+            L.call("mh_gemm_splitk", dy, No, 1, x, Ki, 1, out, Ki, No, Ki, T, O.dt_of(dy), 0, 0, sp, ws, O._stream())
         t = timeit(f)
         print(f"     splits={sp}: {t*1e3:.3f} ms {2.0*T*No*Ki/t/1e12:.0f} TF", flush=True)
