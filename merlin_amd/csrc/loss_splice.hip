@@ -31,12 +31,14 @@ __global__ __launch_bounds__(256) void ce_fwd_k(const float* __restrict__ logits
     const float4 x = ((const float4*)row)[i];
     const float mx = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
     const float mn = fmaxf(m, mx);
+    if (mn == -INFINITY) continue;  // nothing finite yet (masked-out logits): -inf - -inf is NaN, same guard as online_merge
     s = s * __expf(m - mn) + __expf(x.x - mn) + __expf(x.y - mn) + __expf(x.z - mn) + __expf(x.w - mn);
     m = mn;
   }
   for (int i = nv4 * 4 + threadIdx.x; i < V; i += 256) {
     const float x = row[i];
     const float mn = fmaxf(m, x);
+    if (mn == -INFINITY) continue;
     s = s * __expf(m - mn) + __expf(x - mn);
     m = mn;
   }

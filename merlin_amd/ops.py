@@ -1154,6 +1154,11 @@ def attn_bwd_fused_kv(on):
     L.lib().mh_attn_bwd_fused_kv(2 if on is True else int(on))
 
 
+def attn_wide_stores(on: bool):
+    """A/B switch: the row-per-lane epilogues of the attention kernels write 16 bytes per lane (default) or 8; bit-identical results."""
+    L.lib().mh_attn_wide_stores(1 if on else 0)
+
+
 def gemm_raster_group(gm: int):
     """A/B switch: tile rows per raster group of the MFMA GEMM kernels (1..64; default 0 = automatic: every tile row when there are at most 8, else 4; out of range = automatic)."""
     L.lib().mh_gemm_raster_group(gm)

@@ -1,0 +1,466 @@
+"""Per-element error bounds for the kernel tests: fp64 references with their condition magnitudes, rounding models, and the checker.
+
+A kernel output `got` is held to
+
+    |got - ref64| <= c * (eps16 * (|ref64| + B) + tiny)            for every element,
+
+where ref64 is the operation evaluated in float64 from the 16-bit inputs, B is its condition magnitude (the same sums with the terms in
+absolute value: what one rounding of an operand or of a partial sum can move the result by, in units of eps16), eps16 the unit roundoff of
+the output type (EPS16) and tiny the absolute rounding floor of that type (TINY: half the subnormal spacing; where the reference is exactly
+zero AND B is zero the output must be exactly zero, asserted separately).  One large element no longer sets the scale of a whole tensor.
+
+The LIMIT on c never comes from a kernel.  Every operation has a ROUNDING MODEL here (`model=dtype`): the same reference evaluated in fp32
+with the intermediates rounded to the 16-bit type where the kernels hold 16-bit MFMA operands (include/merlin_hip.h and the kernel
+comments: P before P V and P^T dO, dS before dS K and dS^T Q, o as stored before delta, and every stored output).  A test evaluates the
+model on ITS OWN inputs, measures the model's c (`c_model`) and allows `limit(c_model) = max(2, 2 * c_model)`: the factor 2 covers a
+different summation order (MFMA tiles, split-K, online softmax) and the exp2-based softmax of the kernels, both of which move a result by
+about as much again as the roundings the model performs; the floor of 2 is two roundings of the output type.
+
+Measured c, worst over the shapes of tests/test_componentwise_gpu.py and tests/test_entry_points_gpu.py on an MI355X (the model evaluated with torch on
+the same inputs in the same run; on the CPU shapes of tests/test_numerics_cpu.py the models score the same to two digits):
+
+    operation                         bf16 model  bf16 kernel   fp16 model  fp16 kernel
+    --------------------------------  ----------  -----------   ----------  -----------
+    accumulate, 4-wave staged              0.984        0.984        0.971        0.971
+    adamw m                                0.861        0.861        1.045        1.045
+    adamw p                                0.996        0.996        0.995        0.995
+    adamw v                                2.178        2.178        2.727        2.727
+    add                                    0.996        0.996        1.000        1.000
+    attention decode                       0.394        0.331        0.465        0.327
+    attention dk 5-product                 0.726        0.726        0.939        0.939
+    attention dk 7-product                 0.726        0.726        0.969        0.969
+    attention dq 5-product                 0.361        0.361        0.322        0.322
+    attention dq 7-product                 0.425        0.425        0.384        0.384
+    attention dv 5-product                 0.781        0.781        0.919        0.919
+    attention dv 7-product                 0.874        0.874        0.919        0.919
+    attention o (3 forward forms)          0.729        0.729        0.732        0.732
+    ce gradient                            0.996        0.996        1.000        1.000
+    conv3x3 col2im                         0.996        0.996        0.998        0.998
+    gemm 16-bit store, all epilogues       0.995        0.995        0.994        0.994
+    gemm fp32 store                        0.182        0.134        0.389        0.143
+    gemm split-K + epilogue                0.976        0.976        0.897        0.897
+    gemm+gelu act                          1.008        1.008        0.991        0.991
+    gemm+gelu bwd                          0.951        0.951        0.999        0.999
+    gemm+gelu f1                           0.993        0.993        0.992        0.992
+    gemm+rope                              0.990        0.990        0.980        0.980
+    gemm+swiglu act                        0.966        0.966        0.996        0.996
+    gemm+swiglu bwd                        0.977        0.977        0.999        0.999
+    gemm+swiglu gu                         0.995        0.995        0.988        0.988
+    gemv 16-bit                            0.992        0.992        0.981        0.981
+    gemv fp32                              0.112        0.044        0.192        0.043
+    layernorm db                           0.222        0.222        0.221        0.221
+    layernorm dw                           0.315        0.315        0.279        0.279
+    layernorm dx                           0.441        0.441        0.445        0.445
+    layernorm y                            0.498        0.498        0.500        0.500
+    quick-gelu bwd                         0.996        0.996        0.999        0.999
+    quick-gelu fwd                         0.996        0.996        0.997        0.997
+    reduce_partials                        0.980        0.980        0.980        0.980
+    reduce_partials (fp32 out)             0.252        0.252          nan          nan
+    rmsnorm dw                             0.453        0.453        0.422        0.422
+    rmsnorm dx                             0.496        0.496        0.497        0.497
+    rmsnorm y                              0.996        0.996        0.999        0.999
+    rope fwd / inverse                     1.274        1.274        1.479        1.471
+    swiglu bwd                             0.996        0.998        0.999        0.999
+    swiglu fwd                             0.996        0.996        0.999        0.999
+    wgrad split-K 16-bit                   0.995        0.995        0.992        0.992
+    wgrad split-K fp32                     0.131        0.109        0.336        0.131
+
+(Model and kernel mostly agree to three digits: the worst element is one whose error is the rounding of the output itself, and both round the
+same fp32 value.  Where the summation order matters - decode attention, fp32 stores - they differ.)
+
+The mutants of tests/test_numerics_cpu.py (a tile of keys dropped, a causal mask off by one, AdamW without bias correction, ...) score
+c between 5 and several thousand against limits of 2 to 4; the max-norm metric of tests/test_ops_gpu.py lets most of them pass in bf16.
+"""
+import math
+
+import torch
+
+EPS16 = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}
+# absolute rounding floor of a stored value: half the spacing of the subnormals (fp16: 2^-24 apart; bf16 and fp32 share an exponent range)
+TINY = {torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -150}
+F16_SUB = 2.0 ** -25  # half the spacing of fp16 subnormals: what rounding P (or dS) below 2^-14 to fp16 moves it by
+
+
+def limit(c_model):
+    """2 x the rounding model's own c: a different summation order and the exp2-based softmax move a result by about as much again as the
+    model's roundings do.  Floor 2 = two roundings of the output type.  Widening this factor is not an option (see the module docstring)."""
+    return max(2.0, 2.0 * float(c_model))
+
+
+def r16(x, dtype):
+    """x rounded to the 16-bit type, back in x's own type (dtype None / fp32 on an fp32 tensor: unchanged)."""
+    return x if dtype is None else x.to(dtype).to(x.dtype)
+
+
+def componentwise(got, ref64, B, eps16, tiny=0.0):
+    """-> (worst |got - ref64| / (eps16 * (|ref64| + B) + tiny'), index of that element).  Elements with ref64 == 0 and B == 0 (masked query
+    rows, zero padding, untouched cache rows) are not scored: they must be EXACTLY zero, which is asserted here."""
+    ref64 = ref64.double()
+    got = got.double().reshape(ref64.shape)
+    Bt = (B if isinstance(B, torch.Tensor) else torch.full_like(ref64, float(B))).double().expand_as(ref64)
+    exact = (ref64 == 0) & (Bt == 0)
+    bad = exact & (got != 0)
+    if bool(bad.any()):
+        i = int(bad.reshape(-1).nonzero()[0])
+        raise AssertionError(f"element {_unravel(i, ref64.shape)} must be exactly zero, got {float(got.reshape(-1)[i])!r} ({int(bad.sum())} such elements)")
+    assert bool(torch.isfinite(got).all()), f"{int((~torch.isfinite(got)).sum())} non-finite elements"
+    ratio = (got - ref64).abs() / (eps16 * (ref64.abs() + Bt) + max(tiny, 1e-300))
+    ratio = torch.where(exact, torch.zeros_like(ratio), ratio)
+    c, i = ratio.reshape(-1).max(0)
+    return float(c), _unravel(int(i), ref64.shape)
+
+
+def _unravel(i, shape):
+    idx = []
+    for n in reversed(shape):
+        idx.append(i % n)
+        i //= n
+    return tuple(reversed(idx))
+
+
+# ---- GEMM / GEMV ------------------------------------------------------------------------------------------------------------------------
+QUICK_GELU_SLOPE = 1.1  # max |d/dx x sigmoid(1.702 x)| = 1.0998: an error of the pre-activation is amplified by at most this
+
+
+def gemm(a, b, *, bias=None, resid=None, c_old=None, gelu=False, a_t=False, b_t=False, model=None, out_dtype=None, staged_accumulate=False):
+    """C = op(A) op(B)^T (+ bias) (quick-GELU) (+ resid) (+ C_old), the epilogue order of mh_gemm; out_dtype (default: a's) is the type C is
+    stored in.  -> (ref64, B) or, with model=dtype, the rounding model (fp32 product, ONE rounding to out_dtype at the store).
+    The condition magnitude is |A| |B|^T + |bias| (x 1.1 through quick-GELU) + |resid| + |C_old|, but NO term of it is rounded to 16 bits:
+    products of two 16-bit values are exact in fp32 and the sum is accumulated in fp32 (include/merlin_hip.h: "bf16/f16 MFMA, fp32
+    accumulate"), so a K-term sum moves only by the fp32 roundings of its partial sums.  Each is at most 2^-24 of that magnitude; they are
+    independent in sign, so K of them add up like sqrt(K), not K (the worst case K would let an fp32-stored result that was rounded to 16 bits on
+    the way pass in fp16: the mutant "fp32 store rounded to 16 bits first" of tests/test_numerics_cpu.py) - and the magnitude itself already
+    overstates every partial sum.  B is therefore that magnitude times (sqrt(K) + 4) * 2^-24 / eps(out_dtype), 4 for the epilogue's adds.
+    With the plain magnitude, eps16 * B exceeds a whole bias at K = 512 and the mutant "bias added twice" passes too.
+    staged_accumulate: the 4-wave kernel's 16-bit MH_EPI_ACCUM (csrc/gemm_w4.hip w4_store, "Staged epilogue": line 239 packs the quadrant to
+    16 bits into LDS - `pack2<DT>` in `stage8` - and line 463, `a[e] += o[e]`, adds C_old to those packed values on the way out) rounds the product BEFORE it adds C_old -
+    the arithmetic of torch's own `grad += new_grad` on 16-bit gradients.  The model then rounds there too and B gains the product's
+    magnitude once (one eps16 rounding of it).  The 8-wave and 128-tile kernels add in fp32 and are held to the form without it."""
+    wt = torch.float64 if model is None else torch.float32
+    od = a.dtype if out_dtype is None else out_dtype
+    A = (a.t() if a_t else a).to(wt)
+    Bm = (b if b_t else b.t()).to(wt)
+    K = A.shape[1]
+    acc = A @ Bm
+    cond = A.abs() @ Bm.abs() if model is None else None
+    if bias is not None:
+        acc = acc + bias.to(wt)
+        if model is None:
+            cond = cond + bias.to(wt).abs()
+    if gelu:
+        acc = acc * torch.sigmoid(1.702 * acc)
+        if model is None:
+            cond = cond * QUICK_GELU_SLOPE
+    staged = None
+    if staged_accumulate:
+        staged = acc.abs() if model is None else None
+        acc = r16(acc, None if model is None else od)
+    for extra in (resid, c_old):
+        if extra is not None:
+            acc = acc + extra.to(wt)
+            if model is None:
+                cond = cond + extra.to(wt).abs()
+    if model is None:
+        cond = cond * ((math.sqrt(K) + 4) * EPS16[torch.float32] / EPS16[od])
+        return acc, (cond if staged is None else cond + staged)
+    return r16(acc, None if od == torch.float32 else od)
+
+
+# ---- attention (one head) -----------------------------------------------------------------------------------------------------------------
+def attention(q, k, v, do=None, *, causal, n_valid=None, model=None, allowed=None, chunk=2048, keep=False):
+    """One (batch, head): q, k, v, do [S, D] in the 16-bit type.  Semantics of mh_attn_fwd2 / mh_attn_bwd2: keys >= n_valid excluded, query
+    rows >= n_valid zero.  Chunked over queries (the fp64 score matrix of S = 8192 is never held whole).
+    model=None: fp64 reference -> dict o, lse, B_o and, with do: dq, dk, dv, B_dq, B_dk, B_dv, abs_dv, abs_dk, abs_dq.
+        B_o = P |V|;  B_dv = P^T |dO|;  |dS|_bound = P o (|dP| + sum_d |o||dO|),  B_dq = |dS|_bound |K| scale,  B_dk = |dS|_bound^T |Q| scale.
+        abs_* = sum_i |dO_i| (resp. scale sum_i |Q_i|, scale sum_j |K_j|) over the ATTENDED pairs: multiplied by F16_SUB it is what rounding P / dS
+        to fp16 subnormals can move dV / dK / dQ by (see `f16_subnormal_B`).
+    model=dtype: the rounding model in fp32 - P rounded before P V (csrc/attn_fwd2.hip packs exp2 of the scores into the MFMA A operand) and
+        before P^T dO, dS rounded before dS K and dS^T Q (csrc/attn_bwd2.hip; the five-product form stores that 16-bit dS), delta taken from
+        the o that was stored, every output rounded.
+    allowed(q0, q1) -> bool [q1 - q0, S] replaces the mask (the mutants of tests/test_numerics_cpu.py)."""
+    wt = torch.float64 if model is None else torch.float32
+    rd = (lambda x: x) if model is None else (lambda x: r16(x, model))
+    S, D = q.shape
+    scale = 1.0 / math.sqrt(D)
+    n = S if n_valid is None else int(n_valid)
+    Q, K, V = q.to(wt), k.to(wt), v.to(wt)
+    dO = None if do is None else do.to(wt)
+    ar = torch.arange(S, device=q.device)
+    out = {"o": torch.zeros(S, D, dtype=wt, device=q.device), "lse": torch.zeros(S, dtype=wt, device=q.device)}
+    names = ["B_o"] if do is None else ["B_o", "dq", "dk", "dv", "B_dq", "B_dk", "B_dv", "abs_dv", "abs_dk", "abs_dq"]
+    for nm in names:
+        if model is None or nm in ("dq", "dk", "dv"):
+            out[nm] = torch.zeros(S, D, dtype=wt, device=q.device)
+    for q0 in range(0, S, chunk):
+        q1 = min(S, q0 + chunk)
+        if allowed is not None:
+            ok = allowed(q0, q1)
+        else:
+            ok = (ar[None, :] < n) & (ar[q0:q1, None] < n)
+            if causal:
+                ok = ok & (ar[None, :] <= ar[q0:q1, None])
+        s = ((Q[q0:q1] @ K.t()) * scale).masked_fill(~ok, float("-inf"))
+        m = s.amax(1, keepdim=True)
+        m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+        e = torch.exp(s - m)
+        l = e.sum(1, keepdim=True)
+        linv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
+        o = rd((rd(e) @ V) * linv)
+        P = e * linv
+        out["o"][q0:q1] = o
+        out["lse"][q0:q1] = torch.where(l > 0, m + torch.log(l.clamp_min(1e-300)), torch.zeros_like(l))[:, 0]
+        if model is None:
+            out["B_o"][q0:q1] = P @ V.abs()
+        if dO is None:
+            continue
+        g = dO[q0:q1]
+        delta = (o * g).sum(1, keepdim=True)
+        dP = g @ V.t()
+        out["dv"] += rd(P).t() @ g
+        dS = P * (dP - delta)
+        dS16 = rd(dS)
+        out["dq"][q0:q1] = (dS16 @ K) * scale
+        out["dk"] += (dS16.t() @ Q[q0:q1]) * scale
+        if model is None:
+            out["B_dv"] += P.t() @ g.abs()
+            dSb = P * (dP.abs() + (o.abs() * g.abs()).sum(1, keepdim=True))
+            out["B_dq"][q0:q1] = (dSb @ K.abs()) * scale
+            out["B_dk"] += (dSb.t() @ Q[q0:q1].abs()) * scale
+            okf = ok.to(wt)
+            out["abs_dv"] += okf.t() @ g.abs()
+            out["abs_dk"] += (okf.t() @ Q[q0:q1].abs()) * scale
+            out["abs_dq"][q0:q1] = (okf @ K.abs()) * scale
+        if keep:
+            out["P"], out["dS"], out["ok"] = P, dS, ok
+    if dO is not None:
+        for nm in ("dq", "dk", "dv"):
+            out[nm] = rd(out[nm])
+    return out
+
+
+def f16_subnormal_B(ref, name, dtype):
+    """B of dq / dk / dv with the fp16 subnormal term folded in.  P (and with it dS) below 2^-14 is subnormal in fp16: rounding it moves it by
+    up to F16_SUB ABSOLUTELY, not by eps16 relatively, and at S = 4096 most of a softmax row is that small.  The 16-bit MFMA operand P of
+    P^T dO therefore moves dV[j] by up to F16_SUB * sum_i |dO_i| over the queries i that attend key j; dS in dS^T Q moves dK likewise with the
+    Q sum.  dQ = dS K has the same operand, so it gets the K sum.  In units of eps16 that is abs_* * F16_SUB / eps16.  bf16 has fp32's exponent range: no term."""
+    B = ref["B_" + name]
+    if dtype == torch.float16:
+        B = B + ref["abs_" + name] * (F16_SUB / EPS16[dtype])
+    return B
+
+
+# ---- norms ---------------------------------------------------------------------------------------------------------------------------------
+def rmsnorm(x, w, eps, dy=None, *, dx_old=None, model=None):
+    """LlamaRMSNorm y = w x rstd, rstd = rsqrt(mean x^2 + eps).  -> dict y, B_y (0: the sum of squares has no cancellation, one rounding at the
+    store) and, with dy: dx = rstd (w dy - xh mean(xh w dy)) (+ dx_old), dw = sum_rows dy xh, with B_dx, B_dw = the same sums of absolute values."""
+    wt = torch.float64 if model is None else torch.float32
+    X, W = x.to(wt), w.to(wt)
+    rstd = torch.rsqrt((X * X).mean(1, keepdim=True) + eps)
+    xh = X * rstd
+    out = {"y": r16(xh * W, model), "B_y": 0.0}
+    if dy is not None:
+        G = dy.to(wt) * W
+        proj = (xh * G).mean(1, keepdim=True)
+        dx = rstd * (G - xh * proj)
+        Bdx = rstd * (G.abs() + xh.abs() * (xh * G).abs().mean(1, keepdim=True))
+        if dx_old is not None:
+            dx, Bdx = dx + dx_old.to(wt), Bdx + dx_old.to(wt).abs()
+        out.update(dx=r16(dx, model), B_dx=Bdx, dw=(dy.to(wt) * xh).sum(0), B_dw=(dy.to(wt) * xh).abs().sum(0))
+    return out
+
+
+def layernorm(x, w, b, eps, dy=None, *, dx_old=None, model=None):
+    """nn.LayerNorm.  y = xh w + b, B_y = |xh w| + |b|; dx = rstd (g - mean g - xh mean(g xh)), g = w dy; dw = sum dy xh, db = sum dy."""
+    wt = torch.float64 if model is None else torch.float32
+    X, W, Bb = x.to(wt), w.to(wt), b.to(wt)
+    mu = X.mean(1, keepdim=True)
+    rstd = torch.rsqrt(((X - mu) ** 2).mean(1, keepdim=True) + eps)
+    xh = (X - mu) * rstd
+    out = {"y": r16(xh * W + Bb, model), "B_y": (xh * W).abs() + Bb.abs()}
+    if dy is not None:
+        DY = dy.to(wt)
+        G = DY * W
+        dx = rstd * (G - G.mean(1, keepdim=True) - xh * (G * xh).mean(1, keepdim=True))
+        Bdx = rstd * (G.abs() + G.abs().mean(1, keepdim=True) + xh.abs() * (G * xh).abs().mean(1, keepdim=True))
+        if dx_old is not None:
+            dx, Bdx = dx + dx_old.to(wt), Bdx + dx_old.to(wt).abs()
+        out.update(dx=r16(dx, model), B_dx=Bdx, dw=(DY * xh).sum(0), B_dw=(DY * xh).abs().sum(0), db=DY.sum(0), B_db=DY.abs().sum(0))
+    return out
+
+
+def reduce_rows(partial, old=None, *, model=None):
+    """mh_reduce_partials: out[d] = sum_r partial[r, d] (+ old).  -> (ref64, B = sum |partial| + |old|) or the model (fp32 sum, one rounding)."""
+    wt = torch.float64 if model is None else torch.float32
+    s = partial.to(wt).sum(0)
+    Bc = partial.to(wt).abs().sum(0)
+    if old is not None:
+        s, Bc = s + old.to(wt), Bc + old.to(wt).abs()
+    return (s, Bc) if model is None else r16(s, None if model == torch.float32 else model)
+
+
+# ---- elementwise: single roundings of a short expression, B = 0 ----------------------------------------------------------------------------
+def _wt(model):
+    return torch.float64 if model is None else torch.float32
+
+
+def swiglu_fwd(gu, *, model=None):
+    ff = gu.shape[1] // 2
+    g, u = gu[:, :ff].to(_wt(model)), gu[:, ff:].to(_wt(model))
+    return r16(g * torch.sigmoid(g) * u, model)
+
+
+def swiglu_bwd(gu, dout, *, model=None):
+    ff = gu.shape[1] // 2
+    g, u, d = gu[:, :ff].to(_wt(model)), gu[:, ff:].to(_wt(model)), dout.to(_wt(model))
+    sg = torch.sigmoid(g)
+    return r16(torch.cat([d * u * sg * (1 + g * (1 - sg)), d * g * sg], 1), model)
+
+
+def quick_gelu_fwd(x, *, model=None):
+    X = x.to(_wt(model))
+    return r16(X * torch.sigmoid(1.702 * X), model)
+
+
+def quick_gelu_bwd(x, dy, *, model=None):
+    X, d = x.to(_wt(model)), dy.to(_wt(model))
+    sg = torch.sigmoid(1.702 * X)
+    return r16(d * sg * (1 + 1.702 * X * (1 - sg)), model)
+
+
+def add(a, b, *, model=None):
+    return r16(a.to(_wt(model)) + b.to(_wt(model)), model)
+
+
+def rope_table(S, D, theta, device="cpu"):
+    """[S, D/2, 2] (cos, sin) in fp32 from fp64 angles (layout of mh_rope_table)."""
+    inv = theta ** (-torch.arange(0, D, 2, dtype=torch.float64, device=device) / D)
+    ang = torch.arange(S, dtype=torch.float64, device=device)[:, None] * inv[None, :]
+    return torch.stack([ang.cos(), ang.sin()], -1).float()
+
+
+def rope(x, table, S, *, inverse=False, model=None):
+    """Rotate-half RoPE of x [T, nheads, D] at position t % S with the fp32 table the kernel itself reads: out1 = x1 c - x2 s, out2 = x2 c + x1 s
+    (inverse: s -> -s)."""
+    wt = _wt(model)
+    T, _, D = x.shape
+    X = x.to(wt)
+    pos = torch.arange(T, device=x.device) % S
+    c, s = table[pos, :, 0].to(wt)[:, None, :], table[pos, :, 1].to(wt)[:, None, :]
+    if inverse:
+        s = -s
+    x1, x2 = X[..., :D // 2], X[..., D // 2:]
+    return r16(torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], -1), model)
+
+
+# ---- the same element maths behind a GEMM (fused epilogues): the argument itself carries one 16-bit rounding ---------------------------------
+# mh_gemm_swiglu_fwd / mh_gemm_gelu_fwd / mh_gemm_nt_rope store the projection AND a function of it; the 8-wave kernel applies the function
+# to the ROUNDED 16-bit tile (include/merlin_hip.h: "bit-identical to the unfused sequence"), the 4-wave kernel to the fp32 accumulators.
+# Against the fp64 function of the fp64 projection, the result may therefore move by eps16 |x f'(x)| per argument x on top of its own store.
+def swiglu_fwd_cond(gu64, B_gu=None):
+    """B of act = silu(gate) * up when gate | up come out of a GEMM: |d act / d gate| (|gate| + B_gate) + |d act / d up| (|up| + B_up), B_gu the
+    GEMM's own B (a gate that cancels to ~ 0 in the product is uncertain by B_gate, not by eps16 |gate|)."""
+    ff = gu64.shape[1] // 2
+    g, u = gu64[:, :ff], gu64[:, ff:]
+    Bg, Bu = (0.0, 0.0) if B_gu is None else (B_gu[:, :ff], B_gu[:, ff:])
+    sg = torch.sigmoid(g)
+    return (u * sg * (1 + g * (1 - sg))).abs() * (g.abs() + Bg) + (g * sg).abs() * (u.abs() + Bu)
+
+
+def quick_gelu_fwd_cond(x64, B_x=0.0):
+    sg = torch.sigmoid(1.702 * x64)
+    return (sg * (1 + 1.702 * x64 * (1 - sg))).abs() * (x64.abs() + B_x)
+
+
+def rope_cond(x64, table, S):
+    """|x1 c| + |x2 s| per output: what a rounding of x1 and of x2 moves the rotated pair by."""
+    T, _, D = x64.shape
+    pos = torch.arange(T, device=x64.device) % S
+    c, s = table[pos, :, 0].double()[:, None, :].abs(), table[pos, :, 1].double()[:, None, :].abs()
+    x1, x2 = x64[..., :D // 2].abs(), x64[..., D // 2:].abs()
+    return torch.cat([x1 * c + x2 * s, x2 * c + x1 * s], -1)
+
+
+def attention_decode(q, kc, vc, n, *, model=None):
+    """One sequence of mh_attn_decode: q [H, D], caches [Smax, H, D], keys [0, n).  -> (o [H, D], B = P |V|); the model rounds P like the
+    prefill kernels do (the decode kernels keep P in fp32: one rounding fewer than the model allows)."""
+    wt = _wt(model)
+    H, D = q.shape
+    Q, K, V = q.to(wt)[:, None, :], kc[:n].to(wt).permute(1, 0, 2), vc[:n].to(wt).permute(1, 0, 2)
+    P = torch.softmax((Q @ K.transpose(1, 2)) / math.sqrt(D), -1)
+    o = (r16(P, model) @ V)[:, 0]
+    return r16(o, model) if model is not None else (o, (P @ V.abs())[:, 0])
+
+
+# ---- shifted cross-entropy -----------------------------------------------------------------------------------------------------------------
+def shifted_labels(labels):
+    """Row (b, s) is scored against labels[b, s + 1]; the last position of a sample and -100 are ignored (-100 here)."""
+    sh = torch.full_like(labels, -100)
+    sh[:, :-1] = labels[:, 1:]
+    return sh.reshape(-1)
+
+
+def cross_entropy(logits, labels, V, gscale=1.0, *, model=None):
+    """logits fp32 [T, >= V], labels int64 [B, S].  -> dict lse [T], row_loss [T], count, mean (NaN when count == 0, like torch), dlogits [T, V] =
+    gscale / count (softmax - onehot) on scored rows, 0 elsewhere.  B = 0 per element: softmax entries of 1e-6 are held to their own size."""
+    wt = _wt(model)
+    x = logits[:, :V].to(wt)
+    lab = shifted_labels(labels)
+    scored = (lab >= 0) & (lab < V)
+    lse = torch.logsumexp(x, 1)
+    safe = lab.clamp(0, V - 1)
+    row_loss = torch.where(scored, lse - x.gather(1, safe[:, None])[:, 0], torch.zeros_like(lse))
+    count = int(scored.sum())
+    sm = torch.exp(x - lse[:, None])
+    sm.scatter_add_(1, safe[:, None], -scored.to(wt)[:, None])
+    d = sm * scored.to(wt)[:, None] * ((gscale / count) if count else 0.0)
+    return {"lse": lse, "row_loss": row_loss, "count": count, "mean": (row_loss.sum() / count) if count else torch.tensor(float("nan")),
+            "dlogits": r16(d, model)}
+
+
+# ---- AdamW: ONE step from the kernel's own previous state -----------------------------------------------------------------------------------
+def _f32(x):
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def adamw_step(p, g, m, v, *, lr, beta1, beta2, eps, wd, step, gscale=1.0, gscale_dev=None, model=None):
+    """torch.optim.AdamW (decoupled decay, bias-corrected) with g scaled by gscale (* gscale_dev).  p, g 16-bit, m, v fp32: the state BEFORE the
+    step, as the kernel left it, so the only accumulated error of p is its single 16-bit store (B_p: fp32 effects only).  The hyper-parameters are the C ABI's
+    `float` arguments: their fp32 values are the inputs of the reference too (1 - beta is then exact in fp32 as well).
+    -> dict p, m, v, B_p, B_m (= |beta1 m| + |(1 - beta1) g|).  The model multiplies gscale by the device-side factor in fp32 first, as
+    csrc/elementwise.hip adamw_k does (`gscale *= *gscale_dev`), and takes the bias corrections as fp32 values (mh_adamw: 1.0f - powf(beta, step))."""
+    wt = _wt(model)
+    lr, beta1, beta2, eps, wd, gscale = (_f32(x) for x in (lr, beta1, beta2, eps, wd, gscale))
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    if gscale_dev is not None:
+        gscale = gscale * _f32(gscale_dev)
+    if model is not None:
+        gscale, bc1, bc2 = _f32(gscale), _f32(bc1), _f32(bc2)
+    P, G, M, Vv = p.to(wt), g.to(wt) * gscale, m.to(wt), v.to(wt)
+    mn = beta1 * M + (1 - beta1) * G
+    vn = beta2 * Vv + (1 - beta2) * G * G
+    decayed, upd = P * (1 - lr * wd), lr * (mn / bc1) / (torch.sqrt(vn / bc2) + eps)
+    # B_p: nothing in the update is rounded to 16 bits, but its two terms can cancel (a weight crossing zero): each carries a few fp32
+    # roundings (products, quotient, square root: 8 in all), which count against a result far smaller than either term
+    Bp = (decayed.abs() + upd.abs()) * (8 * EPS16[torch.float32] / EPS16.get(p.dtype, EPS16[torch.float32]))
+    return {"p": r16(decayed - upd, model), "m": mn, "v": vn, "B_p": Bp, "B_m": (beta1 * M).abs() + ((1 - beta1) * G).abs()}
+
+
+def resolvable(p_new64, p_old, tol):
+    """Fraction of elements whose reference step |p_new - p_old| exceeds 8 x the tolerance they are checked with: below that a kernel that does
+    nothing at all passes.  tol: tensor, the absolute tolerance per element."""
+    return float(((p_new64 - p_old.double()).abs() > 8 * tol).double().mean())
+
+
+# Hyper-parameters chosen so that ONE step is resolvable in bf16 (a step must exceed 8 x 2 x 2^-8 = 6 % of |p|) and so that the decay alone
+# (lr * wd = 5 % of |p| per step) is: the model's real weights (sigma 0.02) and a tensor of ones standing for norm weights.
+ADAMW_CASES = {"weights": dict(sigma=0.02, offset=0.0, lr=4e-3, wd=12.5), "norm weights (ones)": dict(sigma=0.0, offset=1.0, lr=0.1, wd=0.5)}
+
+
+def adamw_inputs(case, n, dtype, step):
+    c = ADAMW_CASES[case]
+    gen = torch.Generator().manual_seed(n)
+    p0 = (c["offset"] + c["sigma"] * torch.randn(n, generator=gen)).to(dtype)
+    base = torch.randn(n, generator=gen).abs() * 1e-2 * torch.where(p0.float() < 0, -1.0, 1.0)
+    # a consistent direction, towards zero: |m^| / sqrt(v^) stays near 1, every step is a full lr, and |p| (the scale of the tolerance) never grows
+    g = (base * (1 + 0.1 * math.sin(step))).to(dtype)
+    return p0, g

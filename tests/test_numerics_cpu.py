@@ -1,0 +1,254 @@
+"""The per-element checker of tests/numerics.py against itself, without a GPU: for every operation it must ACCEPT the rounding model (the fp32
+evaluation with the kernels' 16-bit roundings) and REJECT every mutant - a plain fp64 reference with one deliberate defect, stored in the 16-bit
+type like a kernel's output - at c >= 2 x the limit the kernels are held to.  Every line printed is `mutant dtype: c vs limit`."""
+import math
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import numerics as N  # noqa: E402
+
+DTYPES = [torch.bfloat16, torch.float16]
+
+
+def rnd(*shape, dtype, scale=1.0, seed=0):
+    g = torch.Generator(device="cpu").manual_seed(seed + sum(shape))
+    return (torch.randn(*shape, generator=g) * scale).to(dtype)
+
+
+def score(got, ref, B, dtype):
+    """c of `got`; inf when an element that must be exactly zero is not (the checker raises there)."""
+    try:
+        return N.componentwise(got, ref, B, N.EPS16[dtype], N.TINY[dtype])[0]
+    except AssertionError:
+        return float("inf")
+
+
+def accept(name, dtype, model, ref, B, cap):
+    """The checker accepts the model: its c is finite and small (cap: what the rounding analysis of the operation allows), so the limit
+    derived from it is tight enough to mean something."""
+    c = score(model, ref, B, dtype)
+    print(f"model  {name:34s} {str(dtype)[6:]:9s} c = {c:8.3f}  limit = {N.limit(c):.3f}")
+    assert c <= cap, (name, dtype, c)
+    return N.limit(c)
+
+
+def reject(name, dtype, got, ref, B, lim):
+    c = score(got.to(dtype) if got.dtype == torch.float64 else got, ref, B, dtype)
+    print(f"mutant {name:34s} {str(dtype)[6:]:9s} c = {c:8.1f}  limit = {lim:.3f}")
+    assert c >= 2 * lim, (name, dtype, c, lim)
+
+
+# ---- attention ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("S", [1024, 2048])
+def test_attention_model_accepted_and_tile_mutants_rejected(dtype, S):
+    D = 128
+    qkv = rnd(S, 3 * D, dtype=dtype)  # one head of the suite's fused q|k|v rows
+    q, k, v = (qkv[:, i * D:(i + 1) * D] for i in range(3))
+    do = rnd(S, D, dtype=dtype, seed=9)
+    ref = N.attention(q, k, v, do, causal=True, keep=True)
+    mod = N.attention(q, k, v, do, causal=True, model=dtype)
+    lim = {}
+    for nm in ("o", "dv", "dq", "dk"):
+        B = ref["B_o"] if nm == "o" else N.f16_subnormal_B(ref, nm, dtype)
+        # one rounding of the 16-bit operand and one of the output, each at most eps16 * (|ref| + B): c <= 2 before fp32 effects
+        lim[nm] = accept(f"attention {nm} S={S}", dtype, mod[nm], ref[nm], B, cap=2.0)
+    Bs = {nm: N.f16_subnormal_B(ref, nm, dtype) for nm in ("dq", "dk", "dv")}
+    scale = 1.0 / math.sqrt(D)
+    ar = torch.arange(S)
+
+    dv = ref["dv"].clone(); dv[-64:] = 0
+    reject(f"dV last 64-key tile zero S={S}", dtype, dv, ref["dv"], Bs["dv"], lim["dv"])
+    dk = ref["dk"].clone(); dk[-64:] = 0
+    reject(f"dK last 64-key tile zero S={S}", dtype, dk, ref["dk"], Bs["dk"], lim["dk"])
+    dq = ref["dq"].clone(); dq[-64:] -= (ref["dS"][-64:, -64:] @ k[-64:].double()) * scale
+    reject(f"dQ loses the diagonal tile S={S}", dtype, dq, ref["dq"], Bs["dq"], lim["dq"])
+
+    def skip_tile(q0, q1):
+        ok = ar[None, :] <= ar[q0:q1, None]
+        hole = (ar[q0:q1, None] >= S - 64) & (ar[None, :] >= S // 2) & (ar[None, :] < S // 2 + 64)
+        return ok & ~hole
+    o = N.attention(q, k, v, causal=True, allowed=skip_tile)["o"]
+    reject(f"fwd skips a 64-key tile S={S}", dtype, o, ref["o"], ref["B_o"], lim["o"])
+
+    def off_by_one(q0, q1):
+        i = ar[q0:q1, None]
+        return ar[None, :] <= torch.where(i >= S // 2, i + 1, i)
+    o = N.attention(q, k, v, causal=True, allowed=off_by_one)["o"]
+    reject(f"causal mask off by one S={S}", dtype, o, ref["o"], ref["B_o"], lim["o"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_key_padding_off_by_one_rejected(dtype):
+    S, D, n = 300, 128, 177  # the ragged shape of test_attention_fwd_bwd
+    qkv = rnd(S, 3 * D, dtype=dtype)
+    q, k, v = (qkv[:, i * D:(i + 1) * D] for i in range(3))
+    ref = N.attention(q, k, v, causal=True, n_valid=n)
+    lim = accept("attention o ragged", dtype, N.attention(q, k, v, causal=True, n_valid=n, model=dtype)["o"], ref["o"], ref["B_o"], cap=2.0)
+    assert float(ref["o"][n:].abs().max()) == 0.0 and float(ref["B_o"][n:].abs().max()) == 0.0
+    ar = torch.arange(S)
+    # (a) one key too many, the padded query rows still zero: non-causal, so every valid row sees the extra key
+    refn = N.attention(q, k, v, causal=False, n_valid=n)
+    limn = accept("attention o ragged non-causal", dtype, N.attention(q, k, v, causal=False, n_valid=n, model=dtype)["o"], refn["o"], refn["B_o"], cap=2.0)
+    o = N.attention(q, k, v, causal=False, allowed=lambda q0, q1: (ar[None, :] < n + 1) & (ar[q0:q1, None] < n))["o"]
+    reject("key padding: one key too many", dtype, o, refn["o"], refn["B_o"], limn)
+    # (b) the whole length off by one, causal: the only difference is query row n, which must be exactly zero
+    o = N.attention(q, k, v, causal=True, n_valid=n + 1)["o"]
+    reject("key padding: row n not zero", dtype, o, ref["o"], ref["B_o"], lim)
+
+
+# ---- GEMM --------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gemm_model_accepted_and_tile_mutants_rejected(dtype):
+    M, Nn, K = 200, 328, 512  # edge tiles in both dimensions of a 128- or 256-wide tiling
+    a, b, bias, resid = rnd(M, K, dtype=dtype), rnd(Nn, K, dtype=dtype, seed=1), rnd(Nn, dtype=dtype, seed=2), rnd(M, Nn, dtype=dtype, seed=3)
+    for kw in ({}, {"bias": bias}, {"bias": bias, "gelu": True}, {"bias": bias, "resid": resid}, {"c_old": resid}):
+        ref, B = N.gemm(a, b, **kw)
+        # fp32 accumulation: the one rounding at the store dominates
+        accept(f"gemm {'+'.join(kw) or 'plain'}", dtype, N.gemm(a, b, model=dtype, **kw), ref, B, cap=1.5)
+    ref32, B32 = N.gemm(a, b, out_dtype=torch.float32)
+    c = N.componentwise(N.gemm(a, b, model=dtype, out_dtype=torch.float32), ref32, B32, N.EPS16[torch.float32])[0]
+    print(f"model  gemm fp32 store {dtype}: c = {c:.3f}")
+    assert c <= 1.0  # B is the worst-case bound of a K-term fp32 sum there
+    rounded_first = N.gemm(a, b, model=dtype).float()  # the product stored in 16 bits, then widened: one rounding the fp32 store must not have
+    c16 = N.componentwise(rounded_first, ref32, B32, N.EPS16[torch.float32])[0]
+    print(f"mutant {'fp32 store rounded to 16 bits first':34s} {str(dtype)[6:]:9s} c = {c16:8.1f}  limit = {N.limit(c):.3f}")
+    assert c16 >= 2 * N.limit(c)
+    ref, B = N.gemm(a, b, bias=bias)
+    lim = N.limit(score(N.gemm(a, b, bias=bias, model=dtype), ref, B, dtype))
+    short = ref.clone()
+    short[192:200, 256:] -= a[192:200, -32:].double() @ b[256:, -32:].double().t()
+    reject("gemm omits the last 32 of K", dtype, short, ref, B, lim)
+    twice = ref.clone()
+    twice[:, 256:] += bias[256:].double()
+    reject("gemm adds the bias twice", dtype, twice, ref, B, lim)
+
+
+# ---- norms, elementwise, RoPE -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_models_accepted_and_mutants_rejected(dtype):
+    rows, d, eps = 37, 256, 1e-5
+    x, w, dy = rnd(rows, d, dtype=dtype), (1 + 0.1 * torch.randn(d, generator=torch.Generator().manual_seed(5))).to(dtype), rnd(rows, d, dtype=dtype, seed=2)
+    x[3] = (x[3].float() * 1e-3).to(dtype)  # a near-zero row: eps decides its scale
+    old = rnd(rows, d, dtype=dtype, seed=4)
+    ref, mod = N.rmsnorm(x, w, eps, dy, dx_old=old), N.rmsnorm(x, w, eps, dy, dx_old=old, model=dtype)
+    ly = accept("rmsnorm y", dtype, mod["y"], ref["y"], ref["B_y"], cap=1.01)
+    lx = accept("rmsnorm dx (accumulate)", dtype, mod["dx"], ref["dx"], ref["B_dx"], cap=1.01)
+    accept("rmsnorm dw", dtype, N.r16(mod["dw"], dtype), ref["dw"], ref["B_dw"], cap=1.01)
+    X, W, G = x.double(), w.double(), dy.double() * w.double()
+    rstd = torch.rsqrt((X * X).mean(1, keepdim=True) + eps)
+    reject("rmsnorm dx without the projection", dtype, rstd * G + old.double(), ref["dx"], ref["B_dx"], lx)
+    y_noeps = ref["y"].clone()
+    y_noeps[3] = X[3] * torch.rsqrt((X[3] * X[3]).mean()) * W
+    reject("rmsnorm drops eps on a tiny row", dtype, y_noeps, ref["y"], ref["B_y"], ly)
+    b = rnd(d, dtype=dtype, seed=6, scale=0.1)
+    ref, mod = N.layernorm(x, w, b, eps, dy), N.layernorm(x, w, b, eps, dy, model=dtype)
+    for nm in ("y", "dx", "dw", "db"):
+        accept(f"layernorm {nm}", dtype, N.r16(mod[nm], dtype), ref[nm], ref["B_" + nm], cap=1.01)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_elementwise_and_rope_models_accepted_and_mutants_rejected(dtype):
+    gu, dout = rnd(64, 512, dtype=dtype), rnd(64, 256, dtype=dtype, seed=1)
+    # ONE rounding of an fp32 value: c <= 1 (+ fp32 effects)
+    for name, ref, mod in (("swiglu fwd", N.swiglu_fwd(gu), N.swiglu_fwd(gu, model=dtype)),
+                           ("swiglu bwd", N.swiglu_bwd(gu, dout), N.swiglu_bwd(gu, dout, model=dtype)),
+                           ("quick-gelu fwd", N.quick_gelu_fwd(gu), N.quick_gelu_fwd(gu, model=dtype)),
+                           ("quick-gelu bwd", N.quick_gelu_bwd(gu, gu.flip(0)), N.quick_gelu_bwd(gu, gu.flip(0), model=dtype)),
+                           ("add", N.add(gu, gu.flip(0)), N.add(gu, gu.flip(0), model=dtype))):
+        accept(name, dtype, mod, ref, 0.0, cap=1.0 + 1e-3)
+    g, u, d = gu[:, :256].double(), gu[:, 256:].double(), dout.double()
+    reject("swiglu bwd with plain sigmoid", dtype, torch.cat([d * u * torch.sigmoid(g), d * g * torch.sigmoid(g)], 1), N.swiglu_bwd(gu, dout), 0.0, 2.0)
+    S, H, D = 50, 2, 128
+    x = rnd(2 * S, H, D, dtype=dtype, seed=3)
+    tab = N.rope_table(S, D, 10000.0)
+    ref = N.rope(x, tab, S)
+    lim = accept("rope", dtype, N.rope(x, tab, S, model=dtype), ref, 0.0, cap=1.0 + 1e-3)
+    accept("rope inverse", dtype, N.rope(x, tab, S, inverse=True, model=dtype), N.rope(x, tab, S, inverse=True), 0.0, cap=1.0 + 1e-3)
+    bad = ref.clone()
+    bad[-1] = N.rope(x, tab, S, inverse=True)[-1]
+    reject("rope inverse on the last row", dtype, bad, ref, 0.0, lim)
+
+
+# ---- loss ----------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("V", [103, 32003])
+def test_cross_entropy_model_accepted_and_count_mutant_rejected(dtype, V):
+    Bn, S = 2, 17
+    g = torch.Generator().manual_seed(V)
+    logits = torch.randn(Bn * S, V, generator=g) * 3
+    labels = torch.randint(0, V, (Bn, S), generator=g)
+    labels[0, :5] = -100
+    ref = N.cross_entropy(logits, labels, V, gscale=0.5)
+    tref = torch.nn.functional.cross_entropy(logits.double().view(Bn, S, V)[:, :-1].reshape(-1, V), labels[:, 1:].reshape(-1), ignore_index=-100)
+    assert abs(float(ref["mean"]) - float(tref)) < 1e-12 * float(tref)  # the reference itself against torch in fp64
+    mod = N.cross_entropy(logits, labels, V, gscale=0.5, model=dtype)
+    lim = accept(f"ce gradient V={V}", dtype, mod["dlogits"], ref["dlogits"], 0.0, cap=1.05)
+    cnt = ref["count"]
+    lab = N.shifted_labels(labels)
+    onehot = torch.zeros_like(ref["dlogits"])
+    sc = lab >= 0
+    onehot[sc.nonzero()[:, 0], lab[sc]] = -0.5 / cnt
+    soft = ref["dlogits"] - onehot
+    reject(f"ce softmax part x count/(count+1) V={V}", dtype, soft * (cnt / (cnt + 1)) + onehot, ref["dlogits"], 0.0, lim)
+
+
+# ---- AdamW ----------------------------------------------------------------------------------------------------------------------------------
+ADAMW_CASES, adamw_inputs = N.ADAMW_CASES, N.adamw_inputs
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", list(ADAMW_CASES))
+def test_adamw_model_accepted_steps_resolvable_and_mutants_rejected(dtype, case):
+    n, hp = 4096 + 5, dict(beta1=0.9, beta2=0.95, eps=1e-8)
+    lr, wd, gscale = ADAMW_CASES[case]["lr"], ADAMW_CASES[case]["wd"], 0.5
+    p, _ = adamw_inputs(case, n, dtype, 1)
+    m, v = torch.zeros(n), torch.zeros(n)
+    worst = {}
+    for step in range(1, 11):
+        _, g = adamw_inputs(case, n, dtype, step)
+        kw = dict(lr=lr, wd=wd, step=step, gscale=gscale, **hp)
+        ref, mod = N.adamw_step(p, g, m, v, **kw), N.adamw_step(p, g, m, v, model=dtype, **kw)
+        cp = score(mod["p"], ref["p"], ref["B_p"], dtype)
+        cm = N.componentwise(mod["m"], ref["m"], ref["B_m"], N.EPS16[torch.float32])[0]
+        cv = N.componentwise(mod["v"], ref["v"], 0.0, N.EPS16[torch.float32], 1e-37)[0]
+        assert cp <= 1.0 + 1e-3 and cm <= 2.0 and cv <= 4.0, (step, cp, cm, cv)  # one 16-bit store; two / four fp32 roundings
+        lp, lm = N.limit(cp), N.limit(cm)
+        tol = lp * N.EPS16[dtype] * ref["p"].abs()
+        frac = N.resolvable(ref["p"], p, tol)
+        assert frac >= 0.9, (case, dtype, step, frac)
+        muts = {"does nothing": (p.double(), None),
+                "no bias correction": (N.adamw_step(p, g, m, v, **{**kw, "step": 10 ** 6})["p"], None),
+                "no weight decay": (N.adamw_step(p, g, m, v, **{**kw, "wd": 0.0})["p"], None),
+                "ignores gscale": (None, N.adamw_step(p, g, m, v, **{**kw, "gscale": 1.0})["m"])}
+        for name, (pm, mm) in muts.items():
+            c = score(pm.to(dtype), ref["p"], ref["B_p"], dtype) if pm is not None else N.componentwise(mm.float(), ref["m"], ref["B_m"], N.EPS16[torch.float32])[0]
+            worst[name] = max(worst.get(name, 0.0), c / (lp if pm is not None else lm))
+        p, m, v = mod["p"].to(dtype), mod["m"], mod["v"]
+    # every step is checked on its own, from the state the kernel itself left: a defect fails the test when ANY of the ten steps rejects it
+    for name, ratio in worst.items():
+        print(f"mutant adamw {name:22s} {case:20s} {str(dtype)[6:]:9s} largest c / limit over 10 steps = {ratio:10.1f}")
+        assert ratio >= 2.0, (name, case, dtype, ratio)
+
+
+def test_adamw_reference_is_torch_adamw_in_fp64():
+    """numerics.adamw_step against torch.optim.AdamW itself, both in float64 and fed their own state over five steps: the reference the kernels
+    are held to is not a formula of this suite's own.  (torch is given the fp32 values of the hyper-parameters, as adamw_step takes them.)"""
+    n, hp = 513, dict(lr=4e-3, beta1=0.9, beta2=0.95, eps=1e-8, wd=12.5)
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+    gen = torch.Generator().manual_seed(11)
+    p = (0.02 * torch.randn(n, generator=gen)).to(torch.bfloat16).double()
+    tp = p.clone().requires_grad_()
+    opt = torch.optim.AdamW([tp], lr=f32(hp["lr"]), betas=(f32(hp["beta1"]), f32(hp["beta2"])), eps=f32(hp["eps"]), weight_decay=f32(hp["wd"]))
+    m, v = torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+    for step in range(1, 6):
+        g = (1e-2 * torch.randn(n, generator=gen)).to(torch.bfloat16)
+        tp.grad = g.double() * 0.5
+        opt.step()
+        out = N.adamw_step(p, g, m, v, step=step, gscale=0.5, **hp)
+        p, m, v = out["p"], out["m"], out["v"]
+        assert p.dtype == torch.float64 and float((p - tp.detach()).abs().max()) <= 1e-13 * float(tp.detach().abs().max()), step

@@ -2,10 +2,14 @@
 same op, on inputs rounded to the 16-bit storage type (so the comparison measures the kernel, not
 the input quantisation).  Tolerances are relative to the reference's max magnitude."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
 
 pytestmark = pytest.mark.gpu
 
@@ -465,6 +469,25 @@ def test_adamw(ops, dtype):
         opt.step()
         ops.adamw_(p, g, m, v, 1e-2, 0.9, 0.95, 1e-8, 0.1, step)
     assert relerr(p, ref.detach()) < 6 * EPS16[dtype]
+    # The bound above is relative to max |p| (~ 3.5): a kernel that does nothing scores 0.0098 against 0.0234 in bf16.  So, per element and one step at
+    # a time from the kernel's own state (tests/numerics.py), with steps the 16-bit type resolves: lr 0.25 moves every element by ~ 0.25 per step where
+    # the tolerance 2 x 2^-8 |p| is below 0.03 for |p| < 4, and lr * wd = 5 % of |p| makes the decay itself visible.
+    import numerics as N
+
+    lr, wd, hp = 0.25, 0.2, dict(beta1=0.9, beta2=0.95, eps=1e-8)
+    p, m, v = p0.clone(), torch.zeros(n, device=dev()), torch.zeros(n, device=dev())
+    for step in range(1, 4):
+        p_old, m_old, v_old, kw = p.clone(), m.clone(), v.clone(), dict(lr=lr, wd=wd, step=step, **hp)
+        want, model = N.adamw_step(p_old, g, m_old, v_old, **kw), N.adamw_step(p_old, g, m_old, v_old, model=dtype, **kw)
+        score = lambda t: N.componentwise(t, want["p"], want["B_p"], N.EPS16[dtype], N.TINY[dtype])  # noqa: E731
+        lim = N.limit(score(model["p"])[0])
+        assert N.resolvable(want["p"], p_old, lim * N.EPS16[dtype] * want["p"].abs()) >= 0.9  # without this guard a no-op kernel passes
+        ops.adamw_(p, g, m, v, lr, hp["beta1"], hp["beta2"], hp["eps"], wd, step)
+        c, at = score(p)
+        assert c <= lim, (step, c, at)
+        # the same bound rejects, on this very step, an update that does nothing and one without bias correction (step -> infinity)
+        assert score(p_old)[0] >= 2 * lim
+        assert score(N.adamw_step(p_old, g, m_old, v_old, **{**kw, "step": 10 ** 6})["p"].to(dtype))[0] >= 2 * lim
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
