@@ -7,9 +7,12 @@ Forward (reference call chain -> here):
   clip_encoder.py:74-82 / HF CLIPVisionModel            -> tower()   (im2col+GEMM, LN, 23 layers)
   mlp_projector.py:19-23 / conv_projector.py:23-39      -> projector()
   base_mmgpt.py:99-160                                  -> splice()  (index kernel + one gather)
-  llama_mmgpt.py:75   LlamaModel (32 x decoder layer)   -> llama_layer_fwd()
-  llama_flash_attn_monkey_patch.py:20-103               -> fused QKV GEMM + RoPE + flash attention
-  llama_mmgpt.py:87-100 lm_head + shifted CE            -> head_loss()
+  llama_mmgpt.py:75   LlamaModel (32 x decoder layer)   -> _llama_layer_fwd() | _llama_layer_fwd_fp8()
+  llama_flash_attn_monkey_patch.py:20-103               -> fused QKV GEMM + RoPE + flash attention (_attn_fwd)
+  llama_mmgpt.py:87-100 lm_head + shifted CE            -> the tail of forward(); _head_bwd_rows / _fp8 / _dense
+There is ONE layer schedule per tower and operand precision: _llama_layer_fwd / _vit_layer_fwd (16-bit operands, on a 16-bit or an
+fp32 residual stream: _stream_norm / _stream_add pick by the stream's dtype) and _llama_layer_fwd_fp8 / _vit_layer_fwd_fp8 (inference
+and training), each with its _bwd.  All of them return (16-bit layer input, stream after the layer, saved activations | None).
 Backward mirrors it layer by layer.  Each decoder / encoder layer keeps only its input; the layer
 forward is recomputed inside the backward (the reference trains with --gradient_checkpointing True,
 pretrain.sh:31), or, with `save_activations=True`, kept resident (288 GB HBM makes that affordable).
@@ -234,6 +237,45 @@ class HipEngine:
         xT = O.transpose16(x, r_pad=Tpad)
         O.gemm_nt(dyT, xT, out=gout, accum=not fresh)
 
+    @staticmethod
+    def _qkv(t):
+        """The q | k | v thirds of a fused [T, 3 d] buffer (or of its gradient) as column views."""
+        d = t.shape[1] // 3
+        return t[:, :d], t[:, d:2 * d], t[:, 2 * d:]
+
+    @staticmethod
+    def _stream_norm(x, w, eps, b=None, want_x16=True):
+        """The norm that reads the residual stream x (b = None: RMSNorm, else LayerNorm) -> (h, x16): x16 = the 16-bit copy of x that
+        the backward keeps.  An fp32 stream's reader writes it next to h (only when wanted); a 16-bit stream is its own copy."""
+        if x.dtype == torch.float32:
+            return O.norm_fwd_f32in(x, w, eps, b=b, want_x16=want_x16)
+        return (O.rmsnorm_fwd(x, w, eps) if b is None else O.layernorm_fwd(x, w, b, eps)), x
+
+    @staticmethod
+    def _stream_add(x, a, w, bias=None):
+        """x + a w^T (+ bias) -> the residual stream after the projection: an fp32 stream is updated IN PLACE (fp32 read-modify-write
+        in the GEMM epilogue), a 16-bit one is a new tensor."""
+        if x.dtype == torch.float32:
+            return O.gemm_nt(a, w, bias=bias, out=x, accum=True)
+        return O.gemm_nt(a, w, bias=bias, resid=x)
+
+    def _lm_head_w(self):
+        """lm_head.weight with its zero pad rows: [Vpad, d], the vocabulary rounded up to whole 64-row tiles."""
+        cfg = self.model.config
+        Vpad, d = _ru(cfg.vocab_size, 64), cfg.hidden_size
+        return self.arena.view("lm_head.weight", numel=Vpad * d, shape=(Vpad, d))
+
+    def _lm_head_g(self):
+        """The gradient block of _lm_head_w(): rows [V, Vpad) receive exact zeros (dlogits' pad columns are zero)."""
+        cfg = self.model.config
+        Vpad, d = _ru(cfg.vocab_size, 64), cfg.hidden_size
+        off = self.arena.offset["lm_head.weight"]
+        return self.arena.gflat[off: off + Vpad * d].view(Vpad, d)
+
+    def _tower_embed_names(self):
+        """The bucket behind the tower's first layer: patch / class / position embeddings + pre_layrnorm."""
+        return [n for n in self.arena.names if n.startswith(VT + "embeddings.") or n.startswith(VT + "pre_layrnorm")]
+
     def _ready(self, names):
         if self.on_grads_ready is not None:
             self.on_grads_ready(names)
@@ -250,24 +292,24 @@ class HipEngine:
     # ------------------------------------------------------------------------------------------
     # vision tower
     # ------------------------------------------------------------------------------------------
-    def _vit_layer_fwd(self, W, x, N, S, vc, keep):
+    def _vit_layer_fwd(self, W, x, N, S, vc, keep, need_x16=True):
+        """One CLIP encoder layer on the residual stream x [T, vd] (16-bit: a new tensor per projection; fp32: updated IN PLACE) ->
+        (x16 = the 16-bit copy of the layer input for the backward, the stream after the layer, saved activations | None)."""
         H = vc.num_attention_heads
-        vd = vc.hidden_size
-        D = vd // H
+        D = vc.hidden_size // H
         eps = vc.layer_norm_eps
-        h1 = O.layernorm_fwd(x, W.ln1w, W.ln1b, eps)
+        h1, x16 = self._stream_norm(x, W.ln1w, eps, b=W.ln1b, want_x16=need_x16)  # (the 16-bit copy is the BACKWARD's: not written without one)
         qkv = O.gemm_nt(h1, W.wqkv, bias=W.bqkv)
-        q, k, v = qkv[:, :vd], qkv[:, vd:2 * vd], qkv[:, 2 * vd:]
-        o, lse = O.attn_fwd2(q, k, v, N, S, H, D, causal=False)
-        x2 = O.gemm_nt(o, W.wo, bias=W.bo, resid=x)
-        h2 = O.layernorm_fwd(x2, W.ln2w, W.ln2b, eps)
+        o, lse = O.attn_fwd2(*self._qkv(qkv), N, S, H, D, causal=False)
+        x = self._stream_add(x, o, W.wo, bias=W.bo)
+        h2, x2 = self._stream_norm(x, W.ln2w, eps, b=W.ln2b, want_x16=keep)
         if keep:
             f1, a = self._fc1_gelu(h2, W)  # f1 (kept for the backward) and quick_gelu(f1) from one launch
         else:
             f1 = None
             a = O.gemm_nt(h2, W.w1, bias=W.b1, act="quick_gelu")
-        y = O.gemm_nt(a, W.w2, bias=W.b2, resid=x2)
-        return y, (((None if self.mem_level else h1), qkv, o, lse, x2, (None if self.mem_level else h2), f1, a) if keep else None)
+        x = self._stream_add(x, a, W.w2, bias=W.b2)
+        return x16, x, (((None if self.mem_level else h1), qkv, o, lse, x2, (None if self.mem_level else h2), f1, a) if keep else None)
 
     @staticmethod
     def _fc1_gelu(h2, W):
@@ -283,7 +325,7 @@ class HipEngine:
         D = vd // H
         eps = vc.layer_norm_eps
         if saved is None:
-            _, saved = self._vit_layer_fwd(W, x, N, S, vc, keep=True)
+            _, _, saved = self._vit_layer_fwd(W, x, N, S, vc, keep=True)
         h1, qkv, o, lse, x2, h2, f1, a = saved
         if h1 is None:  # mem_level >= 1: re-derived from the saved 16-bit layer inputs
             h1 = O.layernorm_fwd(x, W.ln1w, W.ln1b, eps)
@@ -315,8 +357,8 @@ class HipEngine:
             self._wgrad(dx2, o, A.gview(p + "self_attn.out_proj.weight"), fresh, Tpad)
         O.colsum(dx2, A.gview(p + "self_attn.out_proj.bias"), accumulate=acc)
         dqkv = torch.empty_like(qkv)
-        q, k, v = qkv[:, :vd], qkv[:, vd:2 * vd], qkv[:, 2 * vd:]
-        O.attn_bwd2(q, k, v, o, do, lse, N, S, H, D, False, dq=dqkv[:, :vd], dk=dqkv[:, vd:2 * vd], dv=dqkv[:, 2 * vd:])
+        dq, dk, dv = self._qkv(dqkv)
+        O.attn_bwd2(*self._qkv(qkv), o, do, lse, N, S, H, D, False, dq=dq, dk=dk, dv=dv)
         dh1 = O.gemm_nt(dqkv, W.wqkv, b_t=True)
         gqkv = A.gspan(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (3 * vd, vd))
         if grouped:
@@ -346,16 +388,14 @@ class HipEngine:
 
     def _vit_layer_fwd_fp8(self, W, li, x, N, S, vc, keep):
         H = vc.num_attention_heads
-        vd = vc.hidden_size
-        D = vd // H
+        D = vc.hidden_size // H
         eps = vc.layer_norm_eps
         Q = self.fp8_tower_weights(li)
         dt = x.dtype
         h1 = O.layernorm_fwd(x, W.ln1w, W.ln1b, eps)
         a1 = O.quant_fp8_rows(h1)
         qkv = O.gemm_fp8(a1, Q["wqkv"], out_dtype=dt, bias=W.bqkv)
-        q, k, v = qkv[:, :vd], qkv[:, vd:2 * vd], qkv[:, 2 * vd:]
-        o, lse = O.attn_fwd2(q, k, v, N, S, H, D, causal=False)
+        o, lse = O.attn_fwd2(*self._qkv(qkv), N, S, H, D, causal=False)
         a2 = O.quant_fp8_rows(o)
         x2 = O.gemm_fp8(a2, Q["wo"], out_dtype=dt, bias=W.bo, resid=x)
         h2 = O.layernorm_fwd(x2, W.ln2w, W.ln2b, eps)
@@ -368,7 +408,7 @@ class HipEngine:
             a = O.gemm_fp8(a3, Q["w1"], out_dtype=dt, bias=W.b1, act="quick_gelu")
         a4 = O.quant_fp8_rows(a)
         y = O.gemm_fp8(a4, Q["w2"], out_dtype=dt, bias=W.b2, resid=x2)
-        return y, ((h1, qkv, o, lse, x2, h2, f1, a, (a1[1], a2[1], a3[1], a4[1])) if keep else None)
+        return x, y, ((h1, qkv, o, lse, x2, h2, f1, a, (a1[1], a2[1], a3[1], a4[1])) if keep else None)
 
     def _vit_layer_bwd_fp8(self, W, li, x, dy, N, S, vc, saved, fresh):
         A = self.arena
@@ -377,7 +417,7 @@ class HipEngine:
         D = vd // H
         eps = vc.layer_norm_eps
         if saved is None:
-            _, saved = self._vit_layer_fwd_fp8(W, li, x, N, S, vc, keep=True)
+            _, _, saved = self._vit_layer_fwd_fp8(W, li, x, N, S, vc, keep=True)
         h1, qkv, o, lse, x2, h2, f1, a, (s_h1, s_o, s_h2, s_a) = saved
         Q = self.fp8_tower_weights(li)
         dt = x.dtype
@@ -403,8 +443,8 @@ class HipEngine:
         O.colsum(dx2, A.gview(p + "self_attn.out_proj.bias"), accumulate=acc)
         del dx28, dx2T8
         dqkv = torch.empty_like(qkv)
-        q, k, v = qkv[:, :vd], qkv[:, vd:2 * vd], qkv[:, 2 * vd:]
-        O.attn_bwd2(q, k, v, o, do, lse, N, S, H, D, False, dq=dqkv[:, :vd], dk=dqkv[:, vd:2 * vd], dv=dqkv[:, 2 * vd:])
+        dq, dk, dv = self._qkv(dqkv)
+        O.attn_bwd2(*self._qkv(qkv), o, do, lse, N, S, H, D, False, dq=dq, dk=dk, dv=dv)
         dqkv8, dqkvT8 = O.quant_fp8_both(dqkv)
         dh1 = O.gemm_fp8(dqkv8, Q["wqkvT"], out_dtype=dt)
         self._wgrad_fp8(dqkvT8, h1, s_h1, A.gspan(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (3 * vd, vd)), fresh)
@@ -456,35 +496,29 @@ class HipEngine:
             # pre_layrnorm fp32 -> fp32; x0 = the 16-bit copy of its input the backward keeps.  (16-bit tensors at the start of the
             # stream were a sixth of the full-depth logits error: profiles/r04_parity_floor.txt)
             x0_32 = O.vit_assemble_f32(O.gemm_nt(cols, wpad, out_f32=True), cls_w, pos_w, N, G2)
-            x32, x0 = O.layernorm_f32_to_f32(x0_32, A.view(VT + "pre_layrnorm.weight"), A.view(VT + "pre_layrnorm.bias"), vc.layer_norm_eps,
-                                             want_x16=train_tower)
+            x, x0 = O.layernorm_f32_to_f32(x0_32, A.view(VT + "pre_layrnorm.weight"), A.view(VT + "pre_layrnorm.bias"), vc.layer_norm_eps,
+                                           want_x16=train_tower)
             del x0_32
-            for i in range(L):
-                x16, sv = self._vit_layer_fwd_r32(self.vit[i], x32, N, S, vc, keep=train_tower and self.save_activations, need_x16=train_tower)
-                if train_tower:
-                    xs.append(x16)
-                saves.append(sv)
-            x = O.convert(x32, torch.empty(x32.shape, dtype=dt, device=dev))  # hidden_states[select_layer] as the projector's 16-bit GEMM operand
-            del x32
-            L = 0
         else:
             x0 = O.vit_assemble(O.gemm_nt(cols, wpad), cls_w, pos_w, N, G2)
             x = O.layernorm_fwd(x0, A.view(VT + "pre_layrnorm.weight"), A.view(VT + "pre_layrnorm.bias"), vc.layer_norm_eps)
         fp8_tower = bool(ctx is not None and ctx.get("fp8_train") and self.fp8_tower and not r32 and vd % 128 == 0 and
                          vc.intermediate_size % 128 == 0)
+        keep = train_tower and self.save_activations
         for i in range(L):
-            if train_tower:
-                xs.append(x)
             if fp8_tower:
-                x, sv = self._vit_layer_fwd_fp8(self.vit[i], i, x, N, S, vc, keep=train_tower and self.save_activations)
+                x16, x, sv = self._vit_layer_fwd_fp8(self.vit[i], i, x, N, S, vc, keep)
             else:
-                x, sv = self._vit_layer_fwd(self.vit[i], x, N, S, vc, keep=train_tower and self.save_activations)
+                x16, x, sv = self._vit_layer_fwd(self.vit[i], x, N, S, vc, keep, need_x16=train_tower)
+            if train_tower:
+                xs.append(x16)
             saves.append(sv)
-        if ctx is not None:
-            ctx["fp8_tower"] = fp8_tower
+            x16 = None  # (a 16-bit stream's x16 IS the layer input: without a backward it is not held past its layer)
+        if r32:
+            x = O.convert(x, torch.empty(x.shape, dtype=dt, device=dev))  # hidden_states[select_layer] as the projector's 16-bit GEMM operand
         if ctx is not None:
             ctx.update(vit_cols=cols if train_tower else None, vit_x0=x0 if train_tower else None, vit_xs=xs, vit_saves=saves,
-                       vit_N=N, vit_S=S, vit_Kpad=Kpad)
+                       vit_N=N, vit_S=S, vit_Kpad=Kpad, fp8_tower=fp8_tower)
         return x, N, S
 
     def tower_bwd(self, ctx, dx, fresh):
@@ -517,7 +551,7 @@ class HipEngine:
         gw = torch.empty(vd, Kpad, dtype=dx0.dtype, device=dx0.device)
         O.wgrad_tn(dx0, ctx["vit_cols"], gw, accum=False)
         O.copy2d(gw[:, :K], A.gview(VT + "embeddings.patch_embedding.weight").view(vd, K), accumulate=acc)
-        self._ready([n for n in A.names if n.startswith(VT + "embeddings.") or n.startswith(VT + "pre_layrnorm")])
+        self._ready(self._tower_embed_names())
 
     # ------------------------------------------------------------------------------------------
     # projector
@@ -556,23 +590,15 @@ class HipEngine:
         A = self.arena
         x = ctx["proj_in"]
         wname, bname = "model.projector.projector.weight", "model.projector.projector.bias"
+        conv = ctx.get("proj_conv")  # (N, G, vd, stride, S): the weight is the implicit GEMM's [d, vd*9], x its gathered columns
+        wshape = (A.params[wname].shape[0], conv[2] * 9) if conv is not None else None
         dx = None
-        if "proj_conv" in ctx:
-            N, G, vd, stride, S = ctx["proj_conv"]
-            w = A.view(wname, shape=(A.params[wname].shape[0], vd * 9))
-            if ctx["train_tower"]:
-                dcols = O.gemm_nt(dfeats, w, b_t=True)  # [rows, vd*9]
-                dx = O.conv3x3_col2im(dcols, N, G, vd, stride, S, 1)
-            if self._trainable(wname):
-                self._wgrad(dfeats, x, A.gview(wname).view(w.shape), fresh, _ru(x.shape[0], 64))
-                O.colsum(dfeats, A.gview(bname), accumulate=not fresh)
-                self._ready([wname, bname])
-            return dx
         if ctx["train_tower"]:
-            dx = O.gemm_nt(dfeats, A.view(wname), b_t=True)
+            dx = O.gemm_nt(dfeats, A.view(wname, shape=wshape), b_t=True)
+            if conv is not None:  # dx was d(columns) [rows, vd*9]
+                dx = O.conv3x3_col2im(dx, *conv, 1)
         if self._trainable(wname):
-            T = x.shape[0]
-            self._wgrad(dfeats, x, A.gview(wname), fresh, _ru(T, 64))
+            self._wgrad(dfeats, x, A.gview(wname, shape=wshape), fresh, _ru(x.shape[0], 64))
             O.colsum(dfeats, A.gview(bname), accumulate=not fresh)
             self._ready([wname, bname])
         return dx
@@ -580,18 +606,20 @@ class HipEngine:
     # ------------------------------------------------------------------------------------------
     # Llama
     # ------------------------------------------------------------------------------------------
-    def _llama_layer_fwd(self, W, x, B, S, lens, keep, kv_out=None, unpad=None):
+    def _llama_layer_fwd(self, W, x, B, S, lens, keep, kv_out=None, unpad=None, need_x16=True):
+        """One decoder layer on the residual stream x [T, d] (16-bit: a new tensor per projection; fp32: updated IN PLACE) ->
+        (x16 = the 16-bit copy of the layer input for the backward, the stream after the layer, saved activations | None)."""
         cfg = self.model.config
-        d, H, D = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg)
+        H, D = cfg.num_attention_heads, head_dim_of(cfg)
         eps = cfg.rms_norm_eps
-        h1 = O.rmsnorm_fwd(x, W.ln1, eps)
+        h1, x16 = self._stream_norm(x, W.ln1, eps, want_x16=need_x16)  # (the 16-bit copy is the BACKWARD's: not written without one)
         qkv = O.gemm_nt_rope(h1, W.wqkv, self.rope, S, H, D)  # q|k|v projection with RoPE in the GEMM epilogue
         o, lse, packed = self._attn_fwd(qkv, B, S, H, D, lens, unpad, kv_out)
-        x2 = O.gemm_nt(o, W.wo, resid=x)
-        h2 = O.rmsnorm_fwd(x2, W.ln2, eps)
+        x = self._stream_add(x, o, W.wo)                      # x += o Wo^T
+        h2, x2 = self._stream_norm(x, W.ln2, eps, want_x16=keep)
         gu, act = O.gemm_swiglu_fwd(h2, W.wgu)  # gate|up projection; SwiGLU in the same launch's epilogue
-        y = O.gemm_nt(act, W.wd, resid=x2)
-        return y, (self._slim(W, (h1, qkv, o, lse, x2, h2, gu, act, packed)) if keep else None)
+        x = self._stream_add(x, act, W.wd)                    # x += act Wd^T
+        return x16, x, (self._slim(W, (h1, qkv, o, lse, x2, h2, gu, act, packed)) if keep else None)
 
     def _slim(self, W, saved):
         """mem_level: drop what the backward can re-derive (see __init__)."""
@@ -601,40 +629,6 @@ class HipEngine:
         drop_act = self.mem_level >= 2 and int(W.p.split(".")[2]) < self.mem_act_layers
         return (None, qkv, o, lse, x2, None, gu, None if drop_act else act, packed)
 
-    def _llama_layer_fwd_r32(self, W, x32, B, S, lens, keep, kv_out=None, unpad=None, need_x16=True):
-        """_llama_layer_fwd on the fp32 residual stream: x32 [T, d] is updated IN PLACE; returns (x16 = the 16-bit copy of the layer
-        input for the backward, saved activations | None)."""
-        cfg = self.model.config
-        H, D = cfg.num_attention_heads, head_dim_of(cfg)
-        eps = cfg.rms_norm_eps
-        h1, x16 = O.norm_fwd_f32in(x32, W.ln1, eps, want_x16=need_x16)  # (the 16-bit copy of the layer input is the BACKWARD's: not written without one)
-        qkv = O.gemm_nt_rope(h1, W.wqkv, self.rope, S, H, D)
-        o, lse, packed = self._attn_fwd(qkv, B, S, H, D, lens, unpad, kv_out)
-        O.gemm_nt(o, W.wo, out=x32, accum=True)           # x += o Wo^T, fp32 read-modify-write in the GEMM epilogue
-        h2, x2_16 = O.norm_fwd_f32in(x32, W.ln2, eps, want_x16=keep)
-        gu, act = O.gemm_swiglu_fwd(h2, W.wgu)
-        O.gemm_nt(act, W.wd, out=x32, accum=True)         # x += act Wd^T
-        return x16, (self._slim(W, (h1, qkv, o, lse, x2_16, h2, gu, act, packed)) if keep else None)
-
-    def _vit_layer_fwd_r32(self, W, x32, N, S, vc, keep, need_x16=True):
-        H = vc.num_attention_heads
-        vd = vc.hidden_size
-        D = vd // H
-        eps = vc.layer_norm_eps
-        h1, x16 = O.norm_fwd_f32in(x32, W.ln1w, eps, b=W.ln1b, want_x16=need_x16)
-        qkv = O.gemm_nt(h1, W.wqkv, bias=W.bqkv)
-        q, k, v = qkv[:, :vd], qkv[:, vd:2 * vd], qkv[:, 2 * vd:]
-        o, lse = O.attn_fwd2(q, k, v, N, S, H, D, causal=False)
-        O.gemm_nt(o, W.wo, bias=W.bo, out=x32, accum=True)
-        h2, x2_16 = O.norm_fwd_f32in(x32, W.ln2w, eps, b=W.ln2b, want_x16=keep)
-        if keep:
-            f1, a = self._fc1_gelu(h2, W)
-        else:
-            f1 = None
-            a = O.gemm_nt(h2, W.w1, bias=W.b1, act="quick_gelu")
-        O.gemm_nt(a, W.w2, bias=W.b2, out=x32, accum=True)
-        return x16, (((None if self.mem_level else h1), qkv, o, lse, x2_16, (None if self.mem_level else h2), f1, a) if keep else None)
-
     # ---- attention under a key-padding mask (llama_flash_attn_monkey_patch.py:87-102) ---------------------------------------------
     # Right-padded batches (the collator's, collator.py:29-34) only need per-sample lengths: the kernels skip keys >= lens[b] and
     # zero the padded query rows.  Any other mask takes the reference's own route: unpad_input (gather the valid rows of the ROTATED
@@ -643,7 +637,7 @@ class HipEngine:
     def _attn_fwd(self, qkv, B, S, H, D, lens, unpad, kv_out=None):
         d = H * D
         if unpad is None:
-            q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
+            q, k, v = self._qkv(qkv)
             if kv_out is not None:  # prefill: rotated keys and values go to the decode cache [B, Smax, d]
                 kv_out[0][:, :S].copy_(k.view(B, S, d))
                 kv_out[1][:, :S].copy_(v.view(B, S, d))
@@ -651,7 +645,7 @@ class HipEngine:
             return o, lse, None
         fwd, inv, cnt = unpad
         qkv_c = O.gather_rows2d(qkv, fwd, torch.empty_like(qkv))
-        q, k, v = qkv_c[:, :d], qkv_c[:, d:2 * d], qkv_c[:, 2 * d:]
+        q, k, v = self._qkv(qkv_c)
         if kv_out is not None:  # the cache keeps only the VALID keys (rows 0..count-1); their rotation already carries the position
             kv_out[0][:, :S].copy_(k.view(B, S, d))
             kv_out[1][:, :S].copy_(v.view(B, S, d))
@@ -661,11 +655,10 @@ class HipEngine:
 
     def _attn_bwd(self, qkv, o, do, lse, B, S, H, D, lens, unpad, packed):
         """-> dqkv [T, 3 H D] w.r.t. the UN-rotated q, k (inverse RoPE applied)."""
-        d = H * D
         dqkv = torch.empty_like(qkv)
         if unpad is None:
-            q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-            O.attn_bwd2(q, k, v, o, do, lse, B, S, H, D, True, seqlens=lens, dq=dqkv[:, :d], dk=dqkv[:, d:2 * d], dv=dqkv[:, 2 * d:],
+            dq, dk, dv = self._qkv(dqkv)
+            O.attn_bwd2(*self._qkv(qkv), o, do, lse, B, S, H, D, True, seqlens=lens, dq=dq, dk=dk, dv=dv,
                         rope=self.rope)  # inverse RoPE of dq, dk fused into the kernels' epilogues
             return dqkv
         fwd, inv, cnt = unpad
@@ -675,9 +668,9 @@ class HipEngine:
         else:
             qkv_c, o_c = packed
         do_c = O.gather_rows2d(do, fwd, torch.empty_like(do))
-        q, k, v = qkv_c[:, :d], qkv_c[:, d:2 * d], qkv_c[:, 2 * d:]
         dqkv_c = torch.empty_like(qkv)
-        O.attn_bwd2(q, k, v, o_c, do_c, lse, B, S, H, D, True, seqlens=cnt, dq=dqkv_c[:, :d], dk=dqkv_c[:, d:2 * d], dv=dqkv_c[:, 2 * d:])
+        dq, dk, dv = self._qkv(dqkv_c)
+        O.attn_bwd2(*self._qkv(qkv_c), o_c, do_c, lse, B, S, H, D, True, seqlens=cnt, dq=dq, dk=dk, dv=dv)
         O.gather_rows2d(dqkv_c, inv, dqkv)
         return O.rope_qk_(dqkv, self.rope, S, H, D, inverse=True)  # positions are those of the UNPACKED rows
 
@@ -688,21 +681,6 @@ class HipEngine:
         self._fp8_fwd = self._drop_zero_exponents([dict(wqkv=O.quant_fp8_rows_e4(W.wqkv), wo=O.quant_fp8_rows_e4(W.wo), wgu=O.quant_fp8_rows_e4(W.wgu),
                                                         wd=O.quant_fp8_rows_e4(W.wd)) for W in self.llama])
         return self._fp8_fwd
-
-    def _llama_layer_fwd_fp8(self, W, Q, x, B, S, lens, kv_out=None, unpad=None):
-        """Decoder layer with every Linear on the scaled-fp8 MFMA: activations are quantised per token row right before
-        each GEMM (dynamic scaling), weights per output channel (once); residual stream, norms, RoPE, attention and
-        SwiGLU stay 16-bit.  Forward only."""
-        cfg = self.model.config
-        d, H, D = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg)
-        eps = cfg.rms_norm_eps
-        _, a1 = O.rmsnorm_fwd_q8(x, W.ln1, eps)
-        qkv = O.gemm_fp8_rope(a1, Q["wqkv"], self.rope, S, H, D, out_dtype=x.dtype)
-        o, _, _ = self._attn_fwd(qkv, B, S, H, D, lens, unpad, kv_out)
-        x2 = O.gemm_fp8(O.quant_fp8_rows(o), Q["wo"], out_dtype=x.dtype, resid=x)
-        _, a3 = O.rmsnorm_fwd_q8(x2, W.ln2, eps)
-        _, act = O.gemm_fp8_swiglu_fwd(a3, Q["wgu"], out_dtype=x.dtype)
-        return O.gemm_fp8(O.quant_fp8_rows(act), Q["wd"], out_dtype=x.dtype, resid=x2)
 
     # ---- fp8 TRAINING step (BASELINE cfg 5: "fp8 MFMA weight path"; no reference counterpart, SURVEY §2b K12) -------------
     # Every decoder Linear - forward, dgrad and wgrad - runs on the scaled-fp8 MFMA as an NT product of two ROW-quantised
@@ -725,9 +703,7 @@ class HipEngine:
     def fp8_head_weights(self):
         """lm_head.weight [V, d] for the fp8 training step: per-output-channel copy (logits) and the copy of its transpose (dgrad)."""
         def make():
-            cfg = self.model.config
-            V, d = cfg.vocab_size, cfg.hidden_size
-            wlm = self.arena.view("lm_head.weight", numel=_ru(V, 64) * d, shape=(_ru(V, 64), d))  # incl. the zero pad rows
+            wlm = self._lm_head_w()  # incl. the zero pad rows
             # (the transposed copy is quantised per input channel only: its rows are the whole vocabulary long, beyond what the
             #  block-exponent image of the 8-wave kernel holds)
             return self._drop_zero_exponents([dict(w=O.quant_fp8_rows_e4(wlm), wT=O.quant_fp8_rows_t(wlm))])[0]
@@ -748,14 +724,17 @@ class HipEngine:
                 d[k] = d[k][:2]
         return layers
 
-    def _llama_layer_fwd_fp8_train(self, W, li, x, B, S, lens, keep, unpad=None):
+    def _llama_layer_fwd_fp8(self, W, Q, x, B, S, lens, keep, kv_out=None, unpad=None):
+        """Decoder layer with every Linear on the scaled-fp8 MFMA: activations are quantised per token row right before each GEMM
+        (dynamic scaling), weights per output channel (Q: this layer's dict from quantize_forward_weights() - inference - or
+        fp8_train_weights(li) - training); residual stream, norms, RoPE, attention and SwiGLU stay 16-bit.  Returns like
+        _llama_layer_fwd: (the layer input, the layer output, saved activations | None)."""
         cfg = self.model.config
-        d, H, D = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg)
+        H, D = cfg.num_attention_heads, head_dim_of(cfg)
         eps = cfg.rms_norm_eps
-        Q = self.fp8_train_weights(li)
         h1, a1 = O.rmsnorm_fwd_q8(x, W.ln1, eps)  # norm + row quantisation of its output in one launch
         qkv = O.gemm_fp8_rope(a1, Q["wqkv"], self.rope, S, H, D, out_dtype=x.dtype)
-        o, lse, packed = self._attn_fwd(qkv, B, S, H, D, lens, unpad)
+        o, lse, packed = self._attn_fwd(qkv, B, S, H, D, lens, unpad, kv_out)
         a2 = O.quant_fp8_rows(o)
         x2 = O.gemm_fp8(a2, Q["wo"], out_dtype=x.dtype, resid=x)
         h2, a3 = O.rmsnorm_fwd_q8(x2, W.ln2, eps)
@@ -763,7 +742,7 @@ class HipEngine:
         a4 = O.quant_fp8_rows(act)
         y = O.gemm_fp8(a4, Q["wd"], out_dtype=x.dtype, resid=x2)
         # the row scales (one float per token) are kept: their maximum is the tensor-wide scale of the transposed wgrad operand
-        return y, ((h1, qkv, o, lse, x2, h2, gu, act, (a1[1], a2[1], a3[1], a4[1]), packed) if keep else None)
+        return x, y, ((h1, qkv, o, lse, x2, h2, gu, act, (a1[1], a2[1], a3[1], a4[1]), packed) if keep else None)
 
     def _wgrad_fp8(self, dyT8, x, sx, gout, fresh):
         """gout[N_out, K_in] (+)= dy^T x on the scaled-fp8 MFMA: both operands as transposed e4m3 copies (contraction over the
@@ -779,10 +758,10 @@ class HipEngine:
         A = self.arena
         d, ff, H, D = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, head_dim_of(cfg)
         eps = cfg.rms_norm_eps
-        if saved is None:
-            _, saved = self._llama_layer_fwd_fp8_train(W, li, x, B, S, lens, keep=True, unpad=unpad)
-        h1, qkv, o, lse, x2, h2, gu, act, (s_h1, s_o, s_h2, s_act), packed = saved
         Q = self.fp8_train_weights(li)
+        if saved is None:
+            _, _, saved = self._llama_layer_fwd_fp8(W, Q, x, B, S, lens, keep=True, unpad=unpad)
+        h1, qkv, o, lse, x2, h2, gu, act, (s_h1, s_o, s_h2, s_act), packed = saved
         p = W.p
         acc = not fresh
         train = self._trainable(p + "mlp.down_proj.weight")
@@ -822,68 +801,55 @@ class HipEngine:
         d, ff, H, D = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, head_dim_of(cfg)
         eps = cfg.rms_norm_eps
         if saved is None:
-            _, saved = self._llama_layer_fwd(W, x, B, S, lens, keep=True, unpad=unpad)
+            _, _, saved = self._llama_layer_fwd(W, x, B, S, lens, keep=True, unpad=unpad)
         h1, qkv, o, lse, x2, h2, gu, act, packed = saved
         T = x.shape[0]
         Tpad = _ru(T, 64)
         p = W.p
         acc = not fresh
         train = self._trainable(p + "mlp.down_proj.weight")
-        if rows is not None:
-            # LAST decoder layer under a sparse loss (engine.sparse_head): dy - the gradient of this layer's output - is exactly zero on every
-            # row the loss does not score (the head's dgrad gathered zero rows there and RMSNorm backward is row-wise), so the MLP half, the
-            # post-attention norm and the o projection of this layer contract / map over the scored rows alone: the rows are gathered into
-            # compact [npad, .] operands (rows_f: flat positions, -1 = zero pad row), run through the same kernels, and the two results the
-            # rest of the backward needs dense - d(attention output) and the residual gradient - are gathered back (rows_i; zero rows elsewhere).
-            rows_f, rows_i = rows
-            npad = rows_f.numel()
-            g2 = lambda t: O.gather_rows2d(t, rows_f, torch.empty(npad, t.shape[1], dtype=t.dtype, device=t.device))  # noqa: E731
-            dy_c, gu_c, x2_c = g2(dy), g2(gu), g2(x2)
-            dgu_c = O.gemm_swiglu_bwd(dy_c, W.wd, gu_c)
-            if train:
-                act_c = g2(act) if act is not None else O.swiglu_fwd(gu_c)
-                self._wgrad(dy_c, act_c, A.gview(p + "mlp.down_proj.weight"), fresh, npad)
-                del act_c
-            del act, gu, gu_c
-            dh2_c = O.gemm_nt(dgu_c, W.wgu, b_t=True)
-            if train:
-                h2_c = g2(h2) if h2 is not None else O.rmsnorm_fwd(x2_c, W.ln2, eps)
-                self._wgrad(dgu_c, h2_c, A.gspan(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", (2 * ff, d)), fresh, npad)
-                del h2_c
-            del dgu_c, h2
-            dx2_c = O.rmsnorm_bwd(x2_c, W.ln2, dh2_c, eps, dx=dy_c, accumulate_dx=True,
-                                  dw_out=A.gview(p + "post_attention_layernorm.weight") if train else None, dw_accumulate=acc)
-            do_c = O.gemm_nt(dx2_c, W.wo, b_t=True)
-            if train:
-                self._wgrad(dx2_c, g2(o), A.gview(p + "self_attn.o_proj.weight"), fresh, npad)
-            do = O.gather_rows2d(do_c, rows_i, torch.empty(T, d, dtype=do_c.dtype, device=do_c.device))
-            dx2 = O.gather_rows2d(dx2_c, rows_i, dy)  # (dy's storage: its values live on in dx2_c)
-            del dy_c, x2_c, dh2_c, dx2_c, do_c
+        # ---- MLP half, post-attention norm and o projection: ONE schedule, over all T rows (g = identity) or, with `rows`, over the scored ones.
+        # LAST decoder layer under a sparse loss (engine.sparse_head): dy - the gradient of this layer's output - is exactly zero on every
+        # row the loss does not score (the head's dgrad gathered zero rows there and RMSNorm backward is row-wise), so the MLP half, the
+        # post-attention norm and the o projection of this layer contract / map over the scored rows alone: the rows are gathered into
+        # compact [npad, .] operands (rows_f: flat positions, -1 = zero pad row), run through the same kernels, and the two results the
+        # rest of the backward needs dense - d(attention output) and the residual gradient - are gathered back (rows_i; zero rows elsewhere).
+        # Each operand of a weight gradient is gathered right before the launch that reads it.
+        if rows is None:
+            g, Rpad = (lambda t: t), Tpad
         else:
-            dgu = O.gemm_swiglu_bwd(dy, W.wd, gu)  # dact = dy Wd never leaves the kernel: SwiGLU backward in the epilogue
-            if train:
-                if act is None:  # mem_level 2: not kept
-                    act = O.swiglu_fwd(gu)
-                self._wgrad(dy, act, A.gview(p + "mlp.down_proj.weight"), fresh, Tpad)
-            del act
-            dh2 = O.gemm_nt(dgu, W.wgu, b_t=True)
-            if train:
-                if h2 is None:  # mem_level >= 1: the normed operand is re-derived from the saved 16-bit layer-half input
-                    h2 = O.rmsnorm_fwd(x2, W.ln2, eps)
-                self._wgrad(dgu, h2, A.gspan(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", (2 * ff, d)), fresh, Tpad)
-            del dgu, gu, h2
-            dx2 = O.rmsnorm_bwd(x2, W.ln2, dh2, eps, dx=dy, accumulate_dx=True,
-                                dw_out=A.gview(p + "post_attention_layernorm.weight") if train else None, dw_accumulate=acc)
-            do = O.gemm_nt(dx2, W.wo, b_t=True)
-            if train:
-                self._wgrad(dx2, o, A.gview(p + "self_attn.o_proj.weight"), fresh, Tpad)
+            rows_f, rows_i = rows
+            Rpad = rows_f.numel()
+            g = lambda t: O.gather_rows2d(t, rows_f, torch.empty(Rpad, t.shape[1], dtype=t.dtype, device=t.device))  # noqa: E731
+        dy_c, gu_c, x2_c = g(dy), g(gu), g(x2)
+        dgu = O.gemm_swiglu_bwd(dy_c, W.wd, gu_c)  # dact = dy Wd never leaves the kernel: SwiGLU backward in the epilogue
+        if train:
+            act_c = g(act) if act is not None else O.swiglu_fwd(gu_c)  # (mem_level 2: not kept)
+            self._wgrad(dy_c, act_c, A.gview(p + "mlp.down_proj.weight"), fresh, Rpad)
+            del act_c
+        del gu_c
+        dh2 = O.gemm_nt(dgu, W.wgu, b_t=True)
+        if train:
+            # mem_level >= 1: the normed operand is re-derived from the saved 16-bit layer-half input
+            h2_c = g(h2) if h2 is not None else O.rmsnorm_fwd(x2_c, W.ln2, eps)
+            self._wgrad(dgu, h2_c, A.gspan(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", (2 * ff, d)), fresh, Rpad)
+            del h2_c
+        del dgu
+        dx2 = O.rmsnorm_bwd(x2_c, W.ln2, dh2, eps, dx=dy_c, accumulate_dx=True,
+                            dw_out=A.gview(p + "post_attention_layernorm.weight") if train else None, dw_accumulate=acc)
+        do = O.gemm_nt(dx2, W.wo, b_t=True)
+        if train:
+            self._wgrad(dx2, g(o), A.gview(p + "self_attn.o_proj.weight"), fresh, Rpad)
+        if rows is not None:  # back to all T rows
+            do = O.gather_rows2d(do, rows_i, torch.empty(T, d, dtype=do.dtype, device=do.device))
+            dx2 = O.gather_rows2d(dx2, rows_i, dy)  # (dy's storage: its values live on in the compact dx2 = dy_c)
+            del dy_c, x2_c, dh2
+        # ---- attention and the q|k|v projection: always dense
         dqkv = self._attn_bwd(qkv, o, do, lse, B, S, H, D, lens, unpad, packed)
         dh1 = O.gemm_nt(dqkv, W.wqkv, b_t=True)
         if train:
-            if h1 is None:
-                h1 = O.rmsnorm_fwd(x, W.ln1, eps)
-            self._wgrad(dqkv, h1, A.gspan(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (3 * d, d)), fresh, Tpad)
-        del h1
+            self._wgrad(dqkv, h1 if h1 is not None else O.rmsnorm_fwd(x, W.ln1, eps),  # (mem_level >= 1: re-derived, gone after the launch)
+                        A.gspan(p + "self_attn.q_proj.weight", p + "self_attn.v_proj.weight", (3 * d, d)), fresh, Tpad)
         dx = O.rmsnorm_bwd(x, W.ln1, dh1, eps, dx=dx2, accumulate_dx=True,
                            dw_out=A.gview(p + "input_layernorm.weight") if train else None, dw_accumulate=acc)
         if train:
@@ -1013,13 +979,13 @@ class HipEngine:
             lens = None
             ctx["lens"] = None
         ctx["unpad"] = unpad
-        x32 = None
         if inputs_embeds is not None:
             x = inputs_embeds.to(device=dev, dtype=dt).reshape(T, d).contiguous()
+            if r32:
+                x = O.convert(x, torch.empty(x.shape, dtype=torch.float32, device=dev))
         elif r32:  # the decoder's fp32 stream starts from the projector's fp32 output and the widened embedding rows
-            x = None
-            x32 = O.embed_splice_fwd_f32(input_ids.view(-1), src.view(-1) if src is not None else None,
-                                         A.view("model.embed_tokens.weight", shape=(cfg.vocab_size, d)), feats)
+            x = O.embed_splice_fwd_f32(input_ids.view(-1), src.view(-1) if src is not None else None,
+                                       A.view("model.embed_tokens.weight", shape=(cfg.vocab_size, d)), feats)
         else:
             x = O.embed_splice_fwd(input_ids.view(-1), src.view(-1) if src is not None else None,
                                    A.view("model.embed_tokens.weight", shape=(cfg.vocab_size, d)), feats)
@@ -1028,51 +994,33 @@ class HipEngine:
         # ---- decoder ----
         xs, saves = [], []
         fp8_train = fp8 == "train"
+        keep = want_grad and self.save_activations
         if fp8 and (d % 128 or cfg.intermediate_size % 128):
             raise RuntimeError("the fp8 GEMM path needs hidden and intermediate sizes that are multiples of 128")
-        if fp8 and not fp8_train:
-            if want_grad:
-                raise RuntimeError("model.fp8_forward is the inference form (forward only); set model.fp8_training = True for the fp8 training step")
-            F8 = getattr(self, "_fp8_fwd", None) or self.quantize_forward_weights()
-        if r32:
-            if x32 is None:
-                x32 = O.convert(x, torch.empty(x.shape, dtype=torch.float32, device=dev))
-            for li, W in enumerate(self.llama):
-                x16, sv = self._llama_layer_fwd_r32(W, x32, B, S, lens, keep=want_grad and self.save_activations,
-                                                    kv_out=(kv_cache.k[li], kv_cache.v[li]) if kv_cache is not None else None, unpad=unpad,
-                                                    need_x16=want_grad)
-                if want_grad:
-                    xs.append(x16)
-                saves.append(sv)
-        for li, W in enumerate(self.llama if not r32 else ()):
+        if fp8_train and kv_cache is not None:
+            raise RuntimeError("prefill runs the 16-bit or fp8-forward path")
+        if fp8 and not fp8_train and want_grad:
+            raise RuntimeError("model.fp8_forward is the inference form (forward only); set model.fp8_training = True for the fp8 training step")
+        if fp8:
             if fp8_train:
-                if kv_cache is not None:
-                    raise RuntimeError("prefill runs the 16-bit or fp8-forward path")
-                if want_grad:
-                    xs.append(x)
-                x, sv = self._llama_layer_fwd_fp8_train(W, li, x, B, S, lens, keep=want_grad and self.save_activations, unpad=unpad)
-                saves.append(sv)
-                continue
-            if fp8:
-                x = self._llama_layer_fwd_fp8(W, F8[li], x, B, S, lens,
-                                              kv_out=(kv_cache.k[li], kv_cache.v[li]) if kv_cache is not None else None, unpad=unpad)
-                saves.append(None)
-                continue
-            if want_grad:
-                xs.append(x)
-            x, sv = self._llama_layer_fwd(W, x, B, S, lens, keep=want_grad and self.save_activations,
-                                          kv_out=(kv_cache.k[li], kv_cache.v[li]) if kv_cache is not None else None, unpad=unpad)
-            saves.append(sv)
-        if r32:
-            hn, x = O.norm_fwd_f32in(x32, A.view("model.norm.weight"), cfg.rms_norm_eps, want_x16=want_grad)
-            del x32
+                Q8 = [self.fp8_train_weights(li) for li in range(len(self.llama))]
+            else:
+                Q8 = getattr(self, "_fp8_fwd", None) or self.quantize_forward_weights()
+            layer = lambda li, x, kv: self._llama_layer_fwd_fp8(self.llama[li], Q8[li], x, B, S, lens, keep, kv_out=kv, unpad=unpad)  # noqa: E731
         else:
-            hn = O.rmsnorm_fwd(x, A.view("model.norm.weight"), cfg.rms_norm_eps)
+            layer = lambda li, x, kv: self._llama_layer_fwd(self.llama[li], x, B, S, lens, keep, kv_out=kv, unpad=unpad, need_x16=want_grad)  # noqa: E731
+        for li in range(len(self.llama)):
+            x16, x, sv = layer(li, x, (kv_cache.k[li], kv_cache.v[li]) if kv_cache is not None else None)
+            if want_grad:
+                xs.append(x16)
+            saves.append(sv)
+            x16 = None  # (a 16-bit stream's x16 IS the layer input: without a backward it is not held past its layer)
+        hn, x = self._stream_norm(x, A.view("model.norm.weight"), cfg.rms_norm_eps, want_x16=want_grad)
         ctx.update(xs=xs, saves=saves, x_last=x if want_grad else None)
         # ---- lm_head + shifted CE (llama_mmgpt.py:87-100) ----
         V = cfg.vocab_size
         Vpad = _ru(V, 64)
-        wlm = A.view("lm_head.weight", numel=Vpad * d, shape=(Vpad, d))
+        wlm = self._lm_head_w()
         if last_only:  # prefill of generate(): only each sequence's last valid position feeds the sampler
             last = (lens.to(torch.int64) - 1) if lens is not None else torch.full((B,), S - 1, dtype=torch.int64, device=dev)
             rows = O.gather_rows(hn, torch.arange(B, device=dev) * S + last.clamp_min(0))
@@ -1110,15 +1058,72 @@ class HipEngine:
         lg = logits.view(B, S, Vpad)[:, :, :V]
         return loss, lg, ctx
 
+    def _scored_rows(self, ctx):
+        """(rows_f [npad], rows_i [T]) when the forward tabled the scored rows and they are at most half of the batch, else None."""
+        if ctx.get("scored_rows") is None or ctx.get("fp8_head"):
+            return None
+        rows_f, rows_i, host, ev = ctx["scored_rows"]
+        ev.synchronize()  # (recorded in the forward: long done)
+        npad = _ru(max(int(host[0]), 1), 256)
+        return (rows_f[:npad], rows_i) if 2 * npad <= ctx["B"] * ctx["S"] else None
+
+    def _head_bwd_rows(self, ctx, rows, gscale, acc):
+        """lm_head backward over the scored rows alone (engine.sparse_head) -> dhn [T, d], exact zeros on the un-scored rows."""
+        cfg = self.model.config
+        T, d, V = ctx["B"] * ctx["S"], cfg.hidden_size, cfg.vocab_size
+        dt = self.arena.flat.dtype
+        rows_f, rows_i = rows
+        npad = rows_f.numel()
+        dl_c = O.ce_bwd_rows(ctx["logits"], ctx["labels"], ctx["ce_lse"], ctx["ce_out"], rows_f, V, _ru(V, 64), float(gscale), dt)  # [npad, Vpad], zero rows behind the count
+        ctx["logits"] = None
+        hn_c = O.gather_rows2d(ctx["hn"], rows_f, torch.empty(npad, d, dtype=dt, device=dl_c.device))
+        dhn_c = O.gemm_nt(dl_c, self._lm_head_w(), b_t=True)  # [npad, d]
+        if self._trainable("lm_head.weight"):
+            O.gemm_nt(dl_c, hn_c, a_t=True, b_t=True, out=self._lm_head_g(), accum=acc)
+        return O.gather_rows2d(dhn_c, rows_i, torch.empty(T, d, dtype=dt, device=dl_c.device))
+
+    def _head_bwd_fp8(self, ctx, gscale, fresh):
+        """lm_head backward on the scaled-fp8 MFMA (fp8 training step, engine.fp8_head) -> dhn [T, d]."""
+        V = self.model.config.vocab_size
+        Vpad = _ru(V, 64)
+        dt = self.arena.flat.dtype
+        dlogits = O.ce_bwd(ctx["logits"], ctx["labels"], ctx["ce_lse"], ctx["ce_out"], V, Vpad, float(gscale), dt)
+        ctx["logits"] = None
+        train_head = self._trainable("lm_head.weight")
+        V128 = _ru(Vpad, 128)  # the dgrad contracts over the (padded) vocabulary in whole 128-blocks: zero columns behind Vpad
+        dl8, dlT8 = O.quant_fp8_both(dlogits, c_pad=V128) if train_head else (O.quant_fp8_rows(dlogits, k_pad=V128), None)
+        dhn = O.gemm_fp8(dl8, self.fp8_head_weights()["wT"], out_dtype=dt)  # [T, d]
+        if train_head:
+            self._wgrad_fp8(dlT8, ctx["hn"], ctx["hn_scales"], self._lm_head_g(), fresh)
+        return dhn
+
+    def _head_bwd_dense(self, ctx, gscale, acc):
+        """lm_head backward over every row: dhn [T, d] = dlogits W, dW (+)= dlogits^T hn."""
+        V = self.model.config.vocab_size
+        Vpad = _ru(V, 64)
+        T = ctx["B"] * ctx["S"]
+        dt = self.arena.flat.dtype
+        dlogits = O.ce_bwd(ctx["logits"], ctx["labels"], ctx["ce_lse"], ctx["ce_out"], V, Vpad, float(gscale), dt)
+        ctx["logits"] = None
+        dhn = O.gemm_nt(dlogits, self._lm_head_w(), b_t=True)  # [T, d]; B = W^T [d, Vpad]
+        if not self._trainable("lm_head.weight"):
+            return dhn
+        if T % 64 == 0:
+            O.gemm_nt(dlogits, ctx["hn"], a_t=True, b_t=True, out=self._lm_head_g(), accum=acc)
+        else:  # T is no whole number of 64-token tiles: zero-padded transposed copies
+            Tpad = _ru(T, 64)
+            dlT = O.transpose16(dlogits, r_pad=Tpad)  # [Vpad, Tpad]
+            hnT = O.transpose16(ctx["hn"], r_pad=Tpad)
+            O.gemm_nt(dlT[:V], hnT, out=self.arena.gview("lm_head.weight"), accum=acc)
+        return dhn
+
     def backward(self, ctx, gscale=1.0):
         """d(loss)/d(params) * gscale into the gradient arena (param.grad views)."""
         m = self.model
         cfg = m.config
         A = self.arena
         B, S = ctx["B"], ctx["S"]
-        T, d, V = B * S, cfg.hidden_size, cfg.vocab_size
-        Vpad = _ru(V, 64)
-        Tpad = _ru(T, 64)
+        d, V = cfg.hidden_size, cfg.vocab_size
         dt = A.flat.dtype
         fresh = A.ensure_grads()
         if self.on_backward_begin is not None:
@@ -1128,56 +1133,14 @@ class HipEngine:
         # Every trainable bucket is reported through _ready() on EVERY backward, in one fixed order (head, decoder layers
         # L-1..0, embedding, projector, tower layers, tower embeddings), whatever this rank's batch contained: the
         # data-parallel all-reduce sequence is then identical on all ranks (merlin_amd/dp.py).
-        # ---- head ----
-        wlm = A.view("lm_head.weight", numel=Vpad * d, shape=(Vpad, d))
-        sparse = None
-        if ctx.get("scored_rows") is not None and not ctx.get("fp8_head"):
-            rows_f, rows_i, host, ev = ctx["scored_rows"]
-            ev.synchronize()  # (recorded in the forward: long done)
-            n = int(host[0])
-            npad = _ru(max(n, 1), 256)
-            if 2 * npad <= T:
-                sparse = (rows_f[:npad], rows_i)
+        # ---- head: d(loss)/d(normed hidden state) [T, d]; each path writes lm_head's gradient itself ----
+        sparse = self._scored_rows(ctx)
         if sparse is not None:
-            rows_f, rows_i = sparse
-            npad = rows_f.numel()
-            dl_c = O.ce_bwd_rows(ctx["logits"], ctx["labels"], ctx["ce_lse"], ctx["ce_out"], rows_f, V, Vpad, float(gscale), dt)  # [npad, Vpad], zero rows behind the count
-            ctx["logits"] = None
-            hn_c = O.gather_rows2d(ctx["hn"], rows_f, torch.empty(npad, d, dtype=dt, device=dl_c.device))
-            dhn_c = O.gemm_nt(dl_c, wlm, b_t=True)  # [npad, d]
-            if self._trainable("lm_head.weight"):
-                off = A.offset["lm_head.weight"]
-                O.gemm_nt(dl_c, hn_c, a_t=True, b_t=True, out=A.gflat[off: off + Vpad * d].view(Vpad, d), accum=acc)
-            dhn = O.gather_rows2d(dhn_c, rows_i, torch.empty(T, d, dtype=dt, device=dl_c.device))  # un-scored rows: exact zeros
-            del dl_c, hn_c, dhn_c
-            dlogits = None
-        else:
-            dlogits = O.ce_bwd(ctx["logits"], ctx["labels"], ctx["ce_lse"], ctx["ce_out"], V, Vpad, float(gscale), dt)
-            ctx["logits"] = None
-        if sparse is not None:
-            pass
+            dhn = self._head_bwd_rows(ctx, sparse, gscale, acc)
         elif ctx.get("fp8_head"):
-            train_head = self._trainable("lm_head.weight")
-            V128 = _ru(Vpad, 128)  # the dgrad contracts over the (padded) vocabulary in whole 128-blocks: zero columns behind Vpad
-            dl8, dlT8 = O.quant_fp8_both(dlogits, c_pad=V128) if train_head else (O.quant_fp8_rows(dlogits, k_pad=V128), None)
-            dhn = O.gemm_fp8(dl8, self.fp8_head_weights()["wT"], out_dtype=dt)  # [T, d]
-            if train_head:  # rows [V, Vpad) of the padded gradient block receive exact zeros (dlogits' pad columns are zero)
-                off = A.offset["lm_head.weight"]
-                self._wgrad_fp8(dlT8, ctx["hn"], ctx["hn_scales"], A.gflat[off: off + Vpad * d].view(Vpad, d), fresh)
-            del dl8, dlT8
+            dhn = self._head_bwd_fp8(ctx, gscale, fresh)
         else:
-            dhn = O.gemm_nt(dlogits, wlm, b_t=True)  # [T, d]; B = W^T [d, Vpad]
-        if sparse is None and self._trainable("lm_head.weight") and not ctx.get("fp8_head"):
-            if T % 64 == 0:
-                # rows [V, Vpad) of the padded gradient block receive exact zeros (dlogits' pad columns are zero)
-                off = A.offset["lm_head.weight"]
-                O.gemm_nt(dlogits, ctx["hn"], a_t=True, b_t=True, out=A.gflat[off: off + Vpad * d].view(Vpad, d), accum=acc)
-            else:
-                dlT = O.transpose16(dlogits, r_pad=Tpad)  # [Vpad, Tpad]
-                hnT = O.transpose16(ctx["hn"], r_pad=Tpad)
-                O.gemm_nt(dlT[:V], hnT, out=A.gview("lm_head.weight"), accum=acc)
-                del dlT, hnT
-        del dlogits
+            dhn = self._head_bwd_dense(ctx, gscale, acc)
         dx = O.rmsnorm_bwd(ctx["x_last"], A.view("model.norm.weight"), dhn, cfg.rms_norm_eps,
                            dw_out=A.gview("model.norm.weight") if self._trainable("model.norm.weight") else None, dw_accumulate=acc)
         self._ready(["lm_head.weight", "model.norm.weight"])
@@ -1232,7 +1195,7 @@ class HipEngine:
             if tower_train:
                 for i in reversed(range(tower.layers_used)):
                     self._untouched(self.vit[i].names, fresh)
-                self._untouched([n for n in A.names if n.startswith(VT + "embeddings.") or n.startswith(VT + "pre_layrnorm")], fresh)
+                self._untouched(self._tower_embed_names(), fresh)
         # trainable parameters no backward ever reaches (CLIP layers past select_layer, post_layernorm; a tower whose
         # freeze flag is set while its tensors still require grad): zero, never reported (identically on every rank)
         if fresh and tower is not None:
@@ -1316,67 +1279,42 @@ class HipEngine:
         """fp8 (OCP e4m3, one scale per 128 k) copies of the decoder's Linear weights for the decode step (BASELINE cfg 5's
         weight format; activations stay 16-bit).  ~half the bytes per token.  Re-run after the weights change."""
         self.ensure_arena()
-        A = self.arena
-        cfg = self.model.config
-        V, d = cfg.vocab_size, cfg.hidden_size
         q = []
         for W in self.llama:
             q.append(dict(wqkv=O.quant_fp8_b128(W.wqkv), wo=O.quant_fp8_b128(W.wo), wgu=O.quant_fp8_b128(W.wgu), wd=O.quant_fp8_b128(W.wd)))
-        Vpad = _ru(V, 64)
-        wlm = A.view("lm_head.weight", numel=Vpad * d, shape=(Vpad, d))
-        self._fp8 = dict(layers=q, lm_head=O.quant_fp8_b128(wlm[:V]))
+        self._fp8 = dict(layers=q, lm_head=O.quant_fp8_b128(self._lm_head_w()[:self.model.config.vocab_size]))
         return self._fp8
 
     def decode_step(self, tokens, cache, fp8=False):
         """One new token per sequence (tokens int64 [B]) at position cache.lens[b]; returns logits fp32 [B, V] and
         advances the cache.  Every op is an HBM-bound kernel: weights and cache are streamed exactly once.
         fp8=True uses the fp8 weight copies of quantize_decode_weights()."""
+        cfg = self.model.config
+        A = self.arena
+        d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
+        eps = cfg.rms_norm_eps
         if fp8:
-            return self._decode_step_fp8(tokens, cache)
-        cfg = self.model.config
-        A = self.arena
-        d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
-        eps = cfg.rms_norm_eps
+            F8 = getattr(self, "_fp8", None) or self.quantize_decode_weights()
+            gemv, gemv_norm, head = O.gemv_fp8w, O.gemv_fp8w_norm, F8["lm_head"]
+            layers = [(Q["wqkv"], Q["wo"], Q["wgu"], Q["wd"]) for Q in F8["layers"]]
+        else:
+            gemv, gemv_norm, head = O.gemv, O.gemv_norm, self._lm_head_w()
+            layers = [(W.wqkv, W.wo, W.wgu, W.wd) for W in self.llama]
         emb = A.view("model.embed_tokens.weight", shape=(V, d))
         x = O.gather_rows(emb, tokens.to(A.flat.device).view(-1))
         pos = cache.lens
         lens1 = pos + 1
-        for li, W in enumerate(self.llama):
+        for li, (wqkv, wo, wgu, wd) in enumerate(layers):
+            W = self.llama[li]
             # input_layernorm + q|k|v projection + RoPE + K/V append: one launch
-            qkv = O.gemv_qkv_rope(x, W.ln1, eps, W.wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
+            qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
             o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
-            x2 = O.gemv(o, W.wo, resid=x)
-            act = O.gemv_norm(x2, W.ln2, eps, W.wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
-            x = O.gemv(act, W.wd, resid=x2)
+            x2 = gemv(o, wo, resid=x)
+            act = gemv_norm(x2, W.ln2, eps, wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
+            x = gemv(act, wd, resid=x2)
         hn = O.rmsnorm_fwd(x, A.view("model.norm.weight"), eps)
-        Vpad = _ru(V, 64)
-        wlm = A.view("lm_head.weight", numel=Vpad * d, shape=(Vpad, d))
-        logits = O.gemv(hn, wlm, out_f32=True, n=V)
+        logits = gemv(hn, head, out_f32=True, n=V)  # (the 16-bit weight view carries its zero pad rows; the fp8 copy has V rows)
         cache.lens.add_(1)  # in place (after every kernel that read it as `pos`): the captured graph sees the same buffer
-        if cache.rpos is not None:
-            cache.rpos.add_(1)
-        return logits
-
-    def _decode_step_fp8(self, tokens, cache):
-        cfg = self.model.config
-        A = self.arena
-        F8 = getattr(self, "_fp8", None) or self.quantize_decode_weights()
-        d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
-        eps = cfg.rms_norm_eps
-        emb = A.view("model.embed_tokens.weight", shape=(V, d))
-        x = O.gather_rows(emb, tokens.to(A.flat.device).view(-1))
-        pos = cache.lens
-        lens1 = pos + 1
-        for li, W in enumerate(self.llama):
-            Q = F8["layers"][li]
-            qkv = O.gemv_qkv_rope(x, W.ln1, eps, Q["wqkv"], self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
-            o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
-            x2 = O.gemv_fp8w(o, Q["wo"], resid=x)
-            act = O.gemv_fp8w_norm(x2, W.ln2, eps, Q["wgu"], swiglu=True)
-            x = O.gemv_fp8w(act, Q["wd"], resid=x2)
-        hn = O.rmsnorm_fwd(x, A.view("model.norm.weight"), eps)
-        logits = O.gemv_fp8w(hn, F8["lm_head"], out_f32=True)
-        cache.lens.add_(1)
         if cache.rpos is not None:
             cache.rpos.add_(1)
         return logits
