@@ -353,6 +353,24 @@ int mh_attn_decode_splits(int B, int H, int Smax);
 void mh_attn_decode_fused_merge(int on);
 int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens,
                    int B, int H, int D, int Smax, float* ws, int dt, void* stream);
+/* fp8 KV cache of the decode step (half the cache bytes per token): K and V rows as OCP e4m3 bytes k8 / v8 [B, Smax, H*D] with one fp32
+ * scale per (sequence, head, token), kscale / vscale [B, H, Smax] (head-major: a (b, h) block of the attention kernel reads its scales
+ * contiguously).  The scale is an exact power of two: over the D channels of the group, scale = 2^e with e the smallest integer such that
+ * max|x| * 2^-e <= 448 (max|x| = m * 2^ex, m in [0.5, 1): e = ex - 9 if m <= 0.875, else ex - 8), e >= -126, and e = 0 for an all-zero
+ * group; byte = e4m3_rne(x * 2^-e), which never saturates.  byte * scale is exactly representable in bf16 (in fp16 while it stays in
+ * range), so the fp8 cache computes what the 16-bit kernels compute on K / V rounded to that grid.  D in {64, 128}; q, out stay `dt`.
+ * mh_kv8_fill (prefill): x [B*S, H, D] with row stride ldx elements (the k or the v section of the fused q|k|v buffer, ldx = 3 H D; 16-byte
+ *   aligned rows) -> rows [b, s < S] of c8 and scales [b, h, s]; rows >= S are not written.
+ * mh_decode_rope_append_kv8: mh_decode_rope_append with the quantiser behind it - qkv is rotated in place bit-identically, the rotated
+ *   16-bit k row and the v row as it lies in qkv are quantised into row pos[b].
+ * mh_attn_decode_kv8: mh_attn_decode on that cache - keys [0, min(lens[b], Smax)), the same workspace and split plan
+ *   (mh_attn_decode_splits; ws == NULL: one block per (b, h)), fp32 scores, softmax and accumulation, each scale applied once per key.
+ *   The split partials are always merged by the second launch: mh_attn_decode_fused_merge does not apply. */
+int mh_kv8_fill(const void* x, int64_t ldx, void* c8, float* scales, int B, int S, int H, int D, int Smax, int dt, void* stream);
+int mh_decode_rope_append_kv8(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* k8, void* v8, float* kscale,
+                              float* vscale, int B, int H, int D, int Smax, int dt, void* stream);
+int mh_attn_decode_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                       const int32_t* lens, int B, int H, int D, int Smax, float* ws, int dt, void* stream);
 
 /* ---- token selection for generate() (HF GenerationMixin as the reference's eval scripts drive it: eval_mmvet.py:101-120
  * `do_sample=True, temperature=0.2` or `num_beams=5`; site-packages transformers/generation/logits_process.py) ------------

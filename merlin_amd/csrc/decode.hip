@@ -16,6 +16,8 @@
 //   mh_attn_decode      block per (b, h, key split): pass 1 D/8 lanes per key (coalesced 256-B key rows, shuffle-reduced
 //                       dot products, 4 rows in flight per thread) -> scores in LDS -> block max / sum; pass 2 lane-per-channel
 //                       accumulation of p.V (coalesced value rows); split-KV partials merged by a second kernel.  Keys [0, len[b]).
+//   mh_kv8_fill / mh_decode_rope_append_kv8 / mh_attn_decode_kv8   the same step on an fp8 KV cache (e4m3 bytes + one power-of-two scale
+//                       per (sequence, head, token)): prefill quantiser, RoPE + quantised append, attention reading half the bytes per key.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include "mh_common.h"
 
@@ -31,6 +33,16 @@ __device__ __forceinline__ uint4 ld_stream16(const void* p) {
   return make_uint4(v[0], v[1], v[2], v[3]);
 #else
   return *(const uint4*)p;
+#endif
+}
+
+typedef unsigned int du32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint2 ld_stream8(const void* p) {  // a lane's 8 e4m3 values of an fp8 cache row
+#if MH_DECODE_NT
+  const du32x2 v = __builtin_nontemporal_load((const du32x2*)p);
+  return make_uint2(v[0], v[1]);
+#else
+  return *(const uint2*)p;
 #endif
 }
 
@@ -363,6 +375,54 @@ __device__ __forceinline__ void fp8x4_to_f32(uint32_t p, float* f) {
   typedef float f2_ __attribute__((ext_vector_type(2)));
   const f2_ lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p, true);
   f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+}
+
+// ---- fp8 KV cache: K / V rows stored as e4m3 bytes [B, Smax, H*D] with one POWER-OF-TWO fp32 scale per (sequence, head, token), scales
+// [B, H, Smax] (head-major: one (b, h) block of the attention kernel reads its scales contiguously).  scale = 2^e, e the smallest integer
+// with amax * 2^-e <= 448 over the D channels of the group (amax = m * 2^ex, m in [0.5, 1): e = ex - 9 if m <= 0.875 else ex - 8), clamped
+// to >= -126, 0 for an all-zero group; byte = e4m3_rne(x * 2^-e).  byte * 2^e is exact in bf16 (and in fp16 while in range), so the fp8
+// cache is the 16-bit path on K / V rounded to that grid.
+__device__ __forceinline__ int kv8_exp(float amax) {  // amax >= 0, finite
+  const uint32_t bits = __float_as_uint(amax);
+  const int ef = (int)(bits >> 23);
+  if (ef == 0) return bits ? -126 : 0;  // fp32 subnormal (a bf16 subnormal group): e < -126 clamps
+  return max(ef - 126 - ((bits & 0x7fffffu) <= 0x600000u ? 9 : 8), -126);
+}
+__device__ __forceinline__ float kv8_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }  // e in [-126, 127]
+__device__ __forceinline__ float amax8(const float* v) {
+  float mx = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) mx = fmaxf(mx, fabsf(v[e]));
+  return mx;
+}
+__device__ __forceinline__ uint2 kv8_pack8(const float* v, int e) {
+  const float inv = kv8_pow2(-e);  // e <= 120 for any fp32 amax: 2^-e is a normal number
+  int p0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
+  p0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, p0, true);
+  int p1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
+  p1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, p1, true);
+  return make_uint2((unsigned)p0, (unsigned)p1);
+}
+
+// prefill: x [B*S, H, D] (row stride ldx: a view into the fused q|k|v buffer) -> cache rows [b, s < S] and scales [b, h, s]; D/8 lanes per
+// group (16-byte loads, group maximum by shuffles, one 8-byte store per lane)
+template <int DT, int D>
+__global__ __launch_bounds__(256) void kv8_fill_k(const uint16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ c8, float* __restrict__ cs,
+                                                  int B, int S, int H, int Smax) {
+  constexpr int OCT = D / 8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * S * H * OCT) return;  // (whole groups: OCT divides 256)
+  const int part = (int)(i % OCT);
+  const int64_t g = i / OCT, row = g / H;
+  const int h = (int)(g - row * H), b = (int)(row / S), s = (int)(row - (int64_t)b * S);
+  float v[8];
+  unpack8<DT>(*(const uint4*)(x + row * ldx + (int64_t)h * D + part * 8), v);
+  float mx = amax8(v);
+#pragma unroll
+  for (int o2 = OCT / 2; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
+  const int e = kv8_exp(mx);
+  *(uint2*)(c8 + (((int64_t)b * Smax + s) * H + h) * D + part * 8) = kv8_pack8(v, e);
+  if (part == 0) cs[((int64_t)b * H + h) * Smax + s] = kv8_pow2(e);
 }
 
 // y[m, n] = sum_kb s[n, kb] * sum_{k in block} q[n, k] x[m, k] (+ resid): one wave per weight row, 16 fp8 (16 B) per lane
@@ -758,11 +818,29 @@ static int launch_gemv_mfma(const void* x, int64_t ldx, const void* W, int64_t l
   MH_LAUNCH_CHECK();
 }
 
-// qkv [B, 3, H, D] of the new tokens; tab [max_pos, D/2] (cos, sin); kc, vc [B, Smax, H*D]
+// the two 8-channel pieces (c.., c + D/2..) a lane of rope_append_k holds of one head's 16-bit row -> e4m3 at dst, dst + half; the head is
+// `vph` neighbouring lanes, whose first writes the group's scale
 template <int DT>
+__device__ __forceinline__ void kv8_store_pair(const uint4& plo, const uint4& phi, int vph, bool first, uint8_t* dst, int half, float* sdst) {
+  float lo[8], hi[8];
+  unpack8<DT>(plo, lo);
+  unpack8<DT>(phi, hi);
+  float mx = fmaxf(amax8(lo), amax8(hi));
+  for (int o2 = vph >> 1; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
+  const int e = kv8_exp(mx);
+  *(uint2*)dst = kv8_pack8(lo, e);
+  *(uint2*)(dst + half) = kv8_pack8(hi, e);
+  if (first) *sdst = kv8_pow2(e);
+}
+
+// qkv [B, 3, H, D] of the new tokens; tab [max_pos, D/2] (cos, sin); kc, vc [B, Smax, H*D]
+// KV8: kc_, vc_ are e4m3 bytes and ks, vs [B, H, Smax] receive the group scales (fp8 KV cache, above): q, k are rotated exactly as in the
+// 16-bit form, then the ROUNDED 16-bit k row and the v row as it lies in qkv are quantised; a head is D/16 neighbouring lanes (D 64 or 128).
+template <int DT, bool KV8>
 __global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv, const float2* __restrict__ tab,
                                                      const int32_t* __restrict__ pos, const int32_t* __restrict__ rpos,
-                                                     uint16_t* __restrict__ kc, uint16_t* __restrict__ vc, int B, int H, int D, int Smax) {
+                                                     void* __restrict__ kc_, void* __restrict__ vc_, float* __restrict__ ks,
+                                                     float* __restrict__ vs, int B, int H, int D, int Smax) {
   const int half = D >> 1, vph = half >> 3;
   const int64_t total = (int64_t)B * H * vph;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -776,8 +854,7 @@ __global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv,
   uint16_t* qb = qkv + (int64_t)b * 3 * H * D + hd;
   uint16_t* kb = qb + (int64_t)H * D;
   const uint16_t* vb = kb + (int64_t)H * D;
-  uint16_t* kdst = kc + ((int64_t)b * Smax + p) * H * D + hd;
-  uint16_t* vdst = vc + ((int64_t)b * Smax + p) * H * D + hd;
+  const int64_t cdst = ((int64_t)b * Smax + p) * H * D + hd, sdst = ((int64_t)b * H + h) * Smax + p;  // cache element, scale (KV8)
 #pragma unroll
   for (int which = 0; which < 2; ++which) {
     uint16_t* base = which ? kb : qb;
@@ -792,12 +869,21 @@ __global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv,
     *(uint4*)base = plo;
     *(uint4*)(base + half) = phi;
     if (which) {
-      *(uint4*)kdst = plo;
-      *(uint4*)(kdst + half) = phi;
+      if constexpr (KV8) kv8_store_pair<DT>(plo, phi, vph, v == 0, (uint8_t*)kc_ + cdst, half, ks + sdst);
+      else {
+        uint16_t* kdst = (uint16_t*)kc_ + cdst;
+        *(uint4*)kdst = plo;
+        *(uint4*)(kdst + half) = phi;
+      }
     }
   }
-  *(uint4*)vdst = *(const uint4*)vb;
-  *(uint4*)(vdst + half) = *(const uint4*)(vb + half);
+  if constexpr (KV8) {
+    kv8_store_pair<DT>(*(const uint4*)vb, *(const uint4*)(vb + half), vph, v == 0, (uint8_t*)vc_ + cdst, half, vs + sdst);
+  } else {
+    uint16_t* vdst = (uint16_t*)vc_ + cdst;
+    *(uint4*)vdst = *(const uint4*)vb;
+    *(uint4*)(vdst + half) = *(const uint4*)(vb + half);
+  }
 }
 
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -959,6 +1045,116 @@ __global__ __launch_bounds__(256) void attn_decode_k(const uint16_t* __restrict_
   }
 }
 
+// attn_decode_k on the fp8 KV cache (k8, v8 e4m3 bytes [B, Smax, H*D]; ks, vs fp32 scales [B, H, Smax]): the same launch plan, LDS use and
+// partial layout (attn_decode_combine_k merges the splits), half the bytes per key.  A key's scale is requested with its row;
+// s_j = (q . k8_j) ks_j scale, o += (p_j vs_j) v8_j: one multiply per key, none per element, and - the scales being powers of two - the
+// arithmetic of the 16-bit kernel on the dequantised cache.  A lane's piece of a row is 8 bytes, so twice the rows are in flight per thread.
+template <int DT, int D>
+__global__ __launch_bounds__(256) void attn_decode_kv8_k(const uint16_t* __restrict__ q, int64_t ldq, const uint8_t* __restrict__ k8,
+                                                         const uint8_t* __restrict__ v8, const float* __restrict__ ks,
+                                                         const float* __restrict__ vs, uint16_t* __restrict__ out,
+                                                         const int32_t* __restrict__ lens, int H, int Smax, float scale_log2, int splits,
+                                                         int chunk, float* __restrict__ ws) {
+  extern __shared__ float sc[];  // [chunk] scores, then [G][D] partial outputs
+  __shared__ float red[8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sp = blockIdx.x % splits;
+  const int h = (blockIdx.x / splits) % H, b = blockIdx.x / (splits * H);
+  const int key0 = sp * chunk;
+  const int len = max(0, min(min(lens[b], Smax) - key0, chunk));  // keys [key0, key0 + len) of this split
+  const int64_t HD = (int64_t)H * D;
+  k8 += ((int64_t)b * Smax + key0) * HD + (int64_t)h * D;
+  v8 += ((int64_t)b * Smax + key0) * HD + (int64_t)h * D;
+  ks += ((int64_t)b * H + h) * Smax + key0;
+  vs += ((int64_t)b * H + h) * Smax + key0;
+  constexpr int OCT = D / 8, G = 256 / OCT;  // lanes per row (8 values each), rows per block iteration
+  const int c = tid % OCT, gsl = tid / OCT;
+  constexpr int UNR = 8;
+  float q8[8];
+  unpack8<DT>(*(const uint4*)(q + (int64_t)b * ldq + (int64_t)h * D + c * 8), q8);
+  float mx = -1e30f;
+  for (int j0 = 0; j0 < len; j0 += G * UNR) {
+    uint2 kraw[UNR];
+    float ksc[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * G + gsl;
+      const bool ok = j < len;
+      kraw[u] = ok ? ld_stream8(k8 + (int64_t)j * HD + c * 8) : make_uint2(0, 0);
+      ksc[u] = ok ? ks[j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * G + gsl;
+      float kv[8];
+      fp8x4_to_f32(kraw[u].x, kv);
+      fp8x4_to_f32(kraw[u].y, kv + 4);
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s = fmaf(q8[e], kv[e], s);
+#pragma unroll
+      for (int o2 = OCT / 2; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2, 64);
+      s = s * ksc[u] * scale_log2;
+      if (j < len) {
+        if (c == 0) sc[j] = s;
+        mx = fmaxf(mx, s);
+      }
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int j = tid; j < len; j += 256) {
+    const float pj = fast_exp2(sc[j] - mx);
+    sc[j] = pj;
+    sum += pj;
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  for (int j0 = gsl; j0 < len; j0 += G * UNR) {
+    uint2 vraw[UNR];
+    float pj[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * G;
+      const bool ok = j < len;
+      vraw[u] = ok ? ld_stream8(v8 + (int64_t)j * HD + c * 8) : make_uint2(0, 0);
+      pj[u] = ok ? sc[j] * vs[j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float vv[8];
+      fp8x4_to_f32(vraw[u].x, vv);
+      fp8x4_to_f32(vraw[u].y, vv + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(pj[u], vv[e], o[e]);
+    }
+  }
+  __syncthreads();  // everyone is done reading the scores: reuse the buffer for the slice partials
+  float* part = sc;  // [G][D]
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[gsl * D + c * 8 + e] = o[e];
+  __syncthreads();
+  if (tid < D) {
+    float a = 0.f;
+    for (int g2 = 0; g2 < G; ++g2) a += part[g2 * D + tid];
+    if (splits == 1) {
+      out[(int64_t)b * HD + (int64_t)h * D + tid] = (uint16_t)st16<DT>(len > 0 ? a / sum : 0.f);
+    } else {
+      float* w = ws + ((int64_t)(b * H + h) * splits + sp) * (D + 2);
+      w[tid] = a;
+      if (tid == 0) { w[D] = mx; w[D + 1] = sum; }
+    }
+  }
+}
+
 // (splits <= 32: every partial is requested before any is used - the kernel is a handful of dependent L2 round trips otherwise)
 template <int DT, int D>
 __global__ __launch_bounds__(D) void attn_decode_combine_k(const float* __restrict__ ws, uint16_t* __restrict__ out, int H, int splits) {
@@ -1106,11 +1302,49 @@ extern "C" int mh_decode_rope_append(void* qkv, const float* cos_sin, const int3
   const int64_t total = (int64_t)B * H * (D / 16);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   if (dt == MH_BF16)
-    hipLaunchKernelGGL(rope_append_k<MH_BF16>, grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       (uint16_t*)kcache, (uint16_t*)vcache, B, H, D, Smax);
+    hipLaunchKernelGGL((rope_append_k<MH_BF16, false>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       kcache, vcache, (float*)nullptr, (float*)nullptr, B, H, D, Smax);
   else
-    hipLaunchKernelGGL(rope_append_k<MH_F16>, grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       (uint16_t*)kcache, (uint16_t*)vcache, B, H, D, Smax);
+    hipLaunchKernelGGL((rope_append_k<MH_F16, false>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       kcache, vcache, (float*)nullptr, (float*)nullptr, B, H, D, Smax);
+  MH_LAUNCH_CHECK();
+}
+
+// mh_decode_rope_append on the fp8 KV cache: qkv rotated in place exactly as above; the rotated k row and the v row are quantised (one
+// power-of-two scale per head) into k8 / v8 [B, Smax, H*D] at row pos[b], their scales into kscale / vscale [B, H, Smax].
+extern "C" int mh_decode_rope_append_kv8(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* k8, void* v8,
+                                         float* kscale, float* vscale, int B, int H, int D, int Smax, int dt, void* stream) {
+  if (!rope_pos) rope_pos = pos;
+  if (!qkv || !cos_sin || !pos || !k8 || !v8 || !kscale || !vscale || B <= 0 || H <= 0 || Smax <= 0) return MH_ERR_ARG;
+  if (!aligned16(qkv) || (((uintptr_t)k8 | (uintptr_t)v8) & 7u)) return MH_ERR_ARG;  // 16-byte row pieces in, 8-byte e4m3 stores out
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int64_t total = (int64_t)B * H * (D / 16);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (dt == MH_BF16)
+    hipLaunchKernelGGL((rope_append_k<MH_BF16, true>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       k8, v8, kscale, vscale, B, H, D, Smax);
+  else
+    hipLaunchKernelGGL((rope_append_k<MH_F16, true>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       k8, v8, kscale, vscale, B, H, D, Smax);
+  MH_LAUNCH_CHECK();
+}
+
+// prefill of the fp8 KV cache: x [B*S, H, D] (row stride ldx elements; the k or the v section of the fused q|k|v buffer) -> c8 rows
+// [b, s < S] of [B, Smax, H*D] and scales [b, h, s] of [B, H, Smax]; rows >= S are not written.
+extern "C" int mh_kv8_fill(const void* x, int64_t ldx, void* c8, float* scales, int B, int S, int H, int D, int Smax, int dt, void* stream) {
+  if (!x || !c8 || !scales || B <= 0 || S <= 0 || H <= 0 || S > Smax || (ldx & 7) || ldx < (int64_t)H * D || !aligned16(x)) return MH_ERR_ARG;
+  if (((uintptr_t)c8) & 7u) return MH_ERR_ARG;  // every lane stores 8 e4m3 bytes at once
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int64_t total = (int64_t)B * S * H * (D / 8);
+  if ((total + 255) / 256 > 0x7fffffff) return MH_ERR_SHAPE;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define GO(DT_, D_) \
+  hipLaunchKernelGGL((kv8_fill_k<DT_, D_>), grid, block, 0, as_stream(stream), (const uint16_t*)x, ldx, (uint8_t*)c8, scales, B, S, H, Smax)
+  if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
+  else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
+#undef GO
   MH_LAUNCH_CHECK();
 }
 
@@ -1153,6 +1387,40 @@ extern "C" int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, co
     hipLaunchKernelGGL((attn_decode_k<DT_, D_>), grid, block, lds, st, (const uint16_t*)q, ldq, (const uint16_t*)kcache, \
                        (const uint16_t*)vcache, (uint16_t*)out, lens, H, Smax, scale_log2, splits, chunk, ws, cnt);      \
     if (splits > 1 && !cnt)                                                                                              \
+      hipLaunchKernelGGL((attn_decode_combine_k<DT_, D_>), dim3(B * H), dim3(D_), 0, st, (const float*)ws, (uint16_t*)out, H, splits); \
+  } while (0)
+  if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
+  else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
+#undef GO
+  MH_LAUNCH_CHECK();
+}
+
+// mh_attn_decode on the fp8 KV cache (k8, v8 + kscale, vscale): same semantics, workspace and split plan (mh_attn_decode_splits; ws == NULL:
+// one block per (b, h)); the split partials are always merged by the second launch (mh_attn_decode_fused_merge does not apply).
+extern "C" int mh_attn_decode_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                                  const int32_t* lens, int B, int H, int D, int Smax, float* ws, int dt, void* stream) {
+  if (!q || !k8 || !v8 || !kscale || !vscale || !out || !lens || B <= 0 || H <= 0 || Smax <= 0 || (ldq & 7)) return MH_ERR_ARG;
+  if (((uintptr_t)k8 | (uintptr_t)v8) & 7u) return MH_ERR_ARG;  // the cache is read 8 bytes at a time
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  const int splits = ws ? mh_attn_decode_splits(B, H, Smax) : 1;
+  const int chunk = (Smax + splits - 1) / splits;
+  const int G = 256 / (D / 8);
+  const size_t lds = sizeof(float) * (size_t)((chunk > G * D) ? chunk : G * D);
+  if (lds > 150 * 1024) return MH_ERR_SHAPE;  // <= 38400 keys per split
+  const dim3 grid(B * H * splits), block(256);
+  hipStream_t st = as_stream(stream);
+#define GO(DT_, D_)                                                                                                          \
+  do {                                                                                                                        \
+    static bool attr = false;                                                                                                \
+    if (!attr) {                                                                                                              \
+      hipFuncSetAttribute((const void*)attn_decode_kv8_k<DT_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);  \
+      attr = true;                                                                                                            \
+    }                                                                                                                         \
+    hipLaunchKernelGGL((attn_decode_kv8_k<DT_, D_>), grid, block, lds, st, (const uint16_t*)q, ldq, (const uint8_t*)k8, (const uint8_t*)v8, \
+                       kscale, vscale, (uint16_t*)out, lens, H, Smax, scale_log2, splits, chunk, ws);                        \
+    if (splits > 1)                                                                                                           \
       hipLaunchKernelGGL((attn_decode_combine_k<DT_, D_>), dim3(B * H), dim3(D_), 0, st, (const float*)ws, (uint16_t*)out, H, splits); \
   } while (0)
   if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }

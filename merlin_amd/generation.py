@@ -106,14 +106,18 @@ def _resolve_options(generation_config, kw):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, seed=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, seed=None, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
-    other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped."""
+    other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
+    fp8_kv=True stores the KV cache as e4m3 bytes with one power-of-two scale per (sequence, head, token) (engine.KVCache fp8=True):
+    about half the cache bytes in every mode (greedy, sampling, beam search; with or without use_graph and fp8_weights)."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
     num_beams, length_penalty, early_stopping, use_cache = o["num_beams"], o["length_penalty"], o["early_stopping"], o["use_cache"]
+    if fp8_kv and not use_cache:
+        raise ValueError("fp8_kv=True stores the KV cache in fp8: it needs use_cache=True")
     cfg = model.config
     eos_ids = _as_list(cfg.eos_token_id if eos_token_id is None else eos_token_id)
     pad = pad_token_id if pad_token_id is not None else (cfg.pad_token_id if cfg.pad_token_id is not None else (eos_ids[0] if eos_ids else 0))
@@ -131,14 +135,14 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise ValueError("`streamer` cannot be used with beam search. Make sure that `num_beams` is set to 1.")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
-        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights)
+        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv)
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
     if streamer is not None:
         streamer.put(input_ids.cpu())
     if not use_cache:
         out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer)
     else:
-        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, streamer)
+        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer)
     if streamer is not None:
         streamer.end()
     return out
@@ -171,12 +175,12 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
             return ids
 
 
-def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, streamer=None):
+def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None):
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
-    logits, cache = eng.prefill(input_ids, attention_mask, images, max_new)
+    logits, cache = eng.prefill(input_ids, attention_mask, images, max_new, kv_fp8=fp8_kv)
     dev = logits.device
     graph = None
     if use_graph and logits.is_cuda and max_new > 2:
@@ -231,7 +235,7 @@ def _gather_beams(t, idx):
     return torch.gather(t, 1, idx.expand(-1, -1, *t.shape[2:]))
 
 
-def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights):
+def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
@@ -240,7 +244,7 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
-    logits0, cache0 = eng.prefill(input_ids, None, images, max_new)
+    logits0, cache0 = eng.prefill(input_ids, None, images, max_new, kv_fp8=fp8_kv)
     dev = logits0.device
     ids = input_ids.to(dev)
     expand = torch.arange(B, device=dev).repeat_interleave(nb)

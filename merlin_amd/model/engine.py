@@ -635,23 +635,33 @@ class HipEngine:
     # q|k|v - positions stay absolute, RoPE ran in the projection's epilogue) -> causal varlen attention over the packed tokens ->
     # pad_input (scatter back, zeros elsewhere), with the same two gathers around the backward.
     def _attn_fwd(self, qkv, B, S, H, D, lens, unpad, kv_out=None):
-        d = H * D
         if unpad is None:
             q, k, v = self._qkv(qkv)
             if kv_out is not None:  # prefill: rotated keys and values go to the decode cache [B, Smax, d]
-                kv_out[0][:, :S].copy_(k.view(B, S, d))
-                kv_out[1][:, :S].copy_(v.view(B, S, d))
+                self._fill_cache(kv_out, k, v, B, S, H, D)
             o, lse = O.attn_fwd2(q, k, v, B, S, H, D, causal=True, seqlens=lens)
             return o, lse, None
         fwd, inv, cnt = unpad
         qkv_c = O.gather_rows2d(qkv, fwd, torch.empty_like(qkv))
         q, k, v = self._qkv(qkv_c)
         if kv_out is not None:  # the cache keeps only the VALID keys (rows 0..count-1); their rotation already carries the position
-            kv_out[0][:, :S].copy_(k.view(B, S, d))
-            kv_out[1][:, :S].copy_(v.view(B, S, d))
+            self._fill_cache(kv_out, k, v, B, S, H, D)
         o_c, lse = O.attn_fwd2(q, k, v, B, S, H, D, causal=True, seqlens=cnt)
         o = O.gather_rows2d(o_c, inv, torch.empty_like(o_c))
         return o, lse, (qkv_c, o_c)
+
+    @staticmethod
+    def _fill_cache(kv_out, k, v, B, S, H, D):
+        """Rows [:, :S] of one layer's decode cache from the prompt's rotated keys and values (views of the q|k|v buffer): 16-bit copies
+        (k, v), or e4m3 bytes and their scales (k8, v8, ks, vs) for the fp8 cache - only what is STORED is quantised, the prompt's own
+        attention runs on the 16-bit k, v."""
+        if kv_out[0].dtype == torch.uint8:  # KVCache(fp8=True).layer(li)
+            k8, v8, ks, vs = kv_out
+            O.kv8_fill(k, k8, ks, B, S, H, D)
+            O.kv8_fill(v, v8, vs, B, S, H, D)
+        else:
+            kv_out[0][:, :S].copy_(k.view(B, S, H * D))
+            kv_out[1][:, :S].copy_(v.view(B, S, H * D))
 
     def _attn_bwd(self, qkv, o, do, lse, B, S, H, D, lens, unpad, packed):
         """-> dqkv [T, 3 H D] w.r.t. the UN-rotated q, k (inverse RoPE applied)."""
@@ -1010,7 +1020,7 @@ class HipEngine:
         else:
             layer = lambda li, x, kv: self._llama_layer_fwd(self.llama[li], x, B, S, lens, keep, kv_out=kv, unpad=unpad, need_x16=want_grad)  # noqa: E731
         for li in range(len(self.llama)):
-            x16, x, sv = layer(li, x, (kv_cache.k[li], kv_cache.v[li]) if kv_cache is not None else None)
+            x16, x, sv = layer(li, x, kv_cache.layer(li) if kv_cache is not None else None)
             if want_grad:
                 xs.append(x16)
             saves.append(sv)
@@ -1212,9 +1222,17 @@ class HipEngine:
     # KV-cache decode (llama_mmgpt.py:114-134, HF LlamaAttention with past_key_values)
     # ------------------------------------------------------------------------------------------
     class KVCache:
-        """Per-layer rotated keys and values, [B, Smax, H*D] each, plus the valid length of every sequence."""
+        """Per-layer rotated keys and values, [B, Smax, H*D] each, plus the valid length of every sequence.
+        fp8=True (H heads): k, v hold OCP e4m3 bytes (uint8) and ks, vs [B, H, Smax] one power-of-two fp32 scale per (sequence, head,
+        token) - include/merlin_hip.h "fp8 KV cache"; (1 + 4/D) / 2 of the 16-bit cache's bytes."""
 
-        def __init__(self, n_layers, B, Smax, d, dtype, device):
+        def __init__(self, n_layers, B, Smax, d, dtype, device, fp8=False, H=None):
+            self.fp8, self.H = bool(fp8), H
+            if fp8:
+                dtype = torch.uint8
+                self.ks = [torch.zeros(B, H, Smax, dtype=torch.float32, device=device) for _ in range(n_layers)]
+                self.vs = [torch.zeros(B, H, Smax, dtype=torch.float32, device=device) for _ in range(n_layers)]
+                self.ks_alt = self.vs_alt = None
             self.k = [torch.zeros(B, Smax, d, dtype=dtype, device=device) for _ in range(n_layers)]
             self.v = [torch.zeros(B, Smax, d, dtype=dtype, device=device) for _ in range(n_layers)]
             self.lens = torch.zeros(B, dtype=torch.int32, device=device)
@@ -1224,14 +1242,29 @@ class HipEngine:
             self.B, self.Smax = B, Smax
             self.k_alt = self.v_alt = None
 
-    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None):
+        def layer(self, li):
+            """The tensors of layer li: (k, v), or (k8, v8, ks, vs) of the fp8 cache."""
+            return (self.k[li], self.v[li], self.ks[li], self.vs[li]) if self.fp8 else (self.k[li], self.v[li])
+
+        def sets(self):
+            """The per-layer tensor lists that make up the cache: k, v, and the scales ks, vs of the fp8 cache."""
+            return [self.k, self.v, self.ks, self.vs] if self.fp8 else [self.k, self.v]
+
+        @property
+        def nbytes(self):
+            return sum(t.numel() * t.element_size() for lst in self.sets() for t in lst)
+
+    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False):
         """Full forward over the prompt that also fills a KV cache; returns (logits fp32 [B, V] at each sequence's last
-        valid position, cache).  Right-padded prompts (attention_mask) decode from their own length."""
+        valid position, cache).  Right-padded prompts (attention_mask) decode from their own length.
+        kv_fp8=True: the cache is stored as e4m3 bytes + power-of-two scales (KVCache fp8=True); the prompt's own attention still runs on
+        the unquantised keys and values, so these logits do not change."""
         self.ensure_arena()
         cfg = self.model.config
         B, S = (input_ids.shape if input_ids is not None else inputs_embeds.shape[:2])
         A = self.arena
-        cache = HipEngine.KVCache(len(self.llama), B, S + max_new_tokens, cfg.hidden_size, A.flat.dtype, A.flat.device)
+        cache = HipEngine.KVCache(len(self.llama), B, S + max_new_tokens, cfg.hidden_size, A.flat.dtype, A.flat.device, fp8=kv_fp8,
+                                  H=cfg.num_attention_heads)
         self._rope_table(S + max_new_tokens, A.flat.device)
         _, logits, ctx = self.forward(input_ids, attention_mask, None, images, inputs_embeds=inputs_embeds, kv_cache=cache,
                                       last_only=True)
@@ -1251,11 +1284,12 @@ class HipEngine:
         A = self.arena
         n = int(rows.numel())
         Smax, d = cache.Smax, cache.k[0].shape[-1]
-        out = HipEngine.KVCache(0, n, Smax, d, A.flat.dtype, A.flat.device)
+        out = HipEngine.KVCache(0, n, Smax, d, A.flat.dtype, A.flat.device, fp8=cache.fp8, H=cache.H)
         for li in range(len(cache.k)):
-            for src_l, dst_l in ((cache.k, out.k), (cache.v, out.v)):
-                dst = torch.empty(n, Smax, d, dtype=A.flat.dtype, device=A.flat.device)
-                O.gather_rows2d(src_l[li].view(cache.B, Smax * d), rows, dst.view(n, Smax * d))
+            for src_l, dst_l in zip(cache.sets(), out.sets()):
+                src = src_l[li]
+                dst = torch.empty(n, *src.shape[1:], dtype=src.dtype, device=src.device)
+                O.gather_rows2d(src.view(cache.B, -1), rows, dst.view(n, -1))
                 dst_l.append(dst)
         out.lens = cache.lens.index_select(0, rows).contiguous()  # B int32 values, once per generate() call
         out.rpos = cache.rpos.index_select(0, rows).contiguous() if cache.rpos is not None else None
@@ -1274,6 +1308,15 @@ class HipEngine:
             O.gather_rows2d(cache.v[li].view(n, -1), beam_idx, cache.v_alt[li].view(n, -1), cols=n_valid * d)
         cache.k, cache.k_alt = cache.k_alt, cache.k
         cache.v, cache.v_alt = cache.v_alt, cache.v
+        if cache.fp8:  # the scales too: head-major rows [H, Smax] have no valid prefix and move whole
+            if cache.ks_alt is None:
+                cache.ks_alt = [torch.empty_like(t) for t in cache.ks]
+                cache.vs_alt = [torch.empty_like(t) for t in cache.vs]
+            for li in range(len(cache.ks)):
+                O.gather_rows2d(cache.ks[li].view(n, -1), beam_idx, cache.ks_alt[li].view(n, -1))
+                O.gather_rows2d(cache.vs[li].view(n, -1), beam_idx, cache.vs_alt[li].view(n, -1))
+            cache.ks, cache.ks_alt = cache.ks_alt, cache.ks
+            cache.vs, cache.vs_alt = cache.vs_alt, cache.vs
 
     def quantize_decode_weights(self):
         """fp8 (OCP e4m3, one scale per 128 k) copies of the decoder's Linear weights for the decode step (BASELINE cfg 5's
@@ -1288,7 +1331,8 @@ class HipEngine:
     def decode_step(self, tokens, cache, fp8=False):
         """One new token per sequence (tokens int64 [B]) at position cache.lens[b]; returns logits fp32 [B, V] and
         advances the cache.  Every op is an HBM-bound kernel: weights and cache are streamed exactly once.
-        fp8=True uses the fp8 weight copies of quantize_decode_weights()."""
+        fp8=True uses the fp8 weight copies of quantize_decode_weights().  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its
+        own kernels (mh_decode_rope_append_kv8, mh_attn_decode_kv8), with either weight format."""
         cfg = self.model.config
         A = self.arena
         d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
@@ -1306,9 +1350,14 @@ class HipEngine:
         lens1 = pos + 1
         for li, (wqkv, wo, wgu, wd) in enumerate(layers):
             W = self.llama[li]
-            # input_layernorm + q|k|v projection + RoPE + K/V append: one launch
-            qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
-            o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
+            if cache.fp8:  # fp8 KV cache: the projection, then RoPE + quantised append as a launch of its own
+                qkv = gemv_norm(x, W.ln1, eps, wqkv)
+                O.decode_rope_append_kv8(qkv, self.rope, pos, *cache.layer(li), H, D, rope_pos=cache.rpos)
+                o = O.attn_decode_kv8(qkv[:, :d], *cache.layer(li), lens1, H, D)
+            else:
+                # input_layernorm + q|k|v projection + RoPE + K/V append: one launch
+                qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
+                o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
             x2 = gemv(o, wo, resid=x)
             act = gemv_norm(x2, W.ln2, eps, wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
             x = gemv(act, wd, resid=x2)

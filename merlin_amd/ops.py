@@ -286,6 +286,38 @@ def attn_decode(q, kcache, vcache, lens, H, D, out=None, split_kv=True):
     return out
 
 
+def kv8_fill(x, c8, scales, B, S, H, D):
+    """Prefill of the fp8 KV cache: x [B*S, H*D] (a view with row stride x.stride(0), e.g. the k section of the fused q|k|v buffer) ->
+    e4m3 rows [b, s < S] of c8 (uint8 [B, Smax, H*D]) and their power-of-two scales [b, h, s] (fp32 [B, H, Smax])."""
+    assert x.stride(1) == 1 and x.shape == (B * S, H * D) and c8.dtype == torch.uint8 and c8.is_contiguous() and scales.is_contiguous()
+    assert scales.shape == (c8.shape[0], H, c8.shape[1]) and scales.dtype == torch.float32
+    L.call("mh_kv8_fill", x, x.stride(0), c8, scales, B, S, H, D, c8.shape[1], dt_of(x), _stream())
+
+
+def decode_rope_append_kv8(qkv, table, pos, k8, v8, kscale, vscale, H, D, rope_pos=None):
+    """decode_rope_append on the fp8 KV cache: qkv rotated in place (bit-identical), the rotated k row and the v row quantised into
+    k8 / v8 (uint8 [B, Smax, H*D]) at row pos[b], their scales into kscale / vscale (fp32 [B, H, Smax])."""
+    B = qkv.shape[0]
+    assert qkv.is_contiguous() and pos.dtype == torch.int32 and k8.is_contiguous() and v8.is_contiguous() and k8.dtype == v8.dtype == torch.uint8
+    assert kscale.is_contiguous() and vscale.is_contiguous() and kscale.shape == vscale.shape == (B, H, k8.shape[1])
+    assert rope_pos is None or rope_pos.dtype == torch.int32
+    L.call("mh_decode_rope_append_kv8", qkv, table, pos, rope_pos, k8, v8, kscale, vscale, B, H, D, k8.shape[1], dt_of(qkv), _stream())
+
+
+def attn_decode_kv8(q, k8, v8, kscale, vscale, lens, H, D, out=None, split_kv=True):
+    """attn_decode against the fp8 KV cache (k8, v8 uint8 [B, Smax, H*D]; kscale, vscale fp32 [B, H, Smax]); keys [0, lens[b])."""
+    B = q.shape[0]
+    out = torch.empty(B, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    Smax = k8.shape[1]
+    assert k8.dtype == v8.dtype == torch.uint8 and k8.shape == v8.shape == (B, Smax, H * D) and k8.is_contiguous() and v8.is_contiguous()
+    assert kscale.dtype == vscale.dtype == torch.float32 and kscale.shape == vscale.shape == (B, H, Smax)
+    assert kscale.is_contiguous() and vscale.is_contiguous() and lens.dtype == torch.int32 and q.stride(1) == 1
+    splits = int(L.lib().mh_attn_decode_splits(B, H, Smax))
+    ws = torch.empty(B * H * splits * (D + 2), dtype=torch.float32, device=q.device) if (splits > 1 and split_kv) else None
+    L.call("mh_attn_decode_kv8", q, q.stride(0), k8, v8, kscale, vscale, out, lens, B, H, D, Smax, ws, dt_of(q), _stream())
+    return out
+
+
 def attn_decode_fused_merge(on: bool):
     """A/B switch: split-KV partials merged by a second launch (default) or by the last block of a (b, h) to finish."""
     L.lib().mh_attn_decode_fused_merge(1 if on else 0)

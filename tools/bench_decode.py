@@ -1,6 +1,12 @@
 """Decode-step timing of the KV-cache path at Llama-7B size (run on the GPU box): prefill a cfg-3 style prompt, then time
 decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token and the HBM rate the step sustains
-(weights + K/V cache streamed once per step)."""
+(weights + K/V cache streamed once per step).
+
+    python tools/bench_decode.py [B] [context] [--kv fp8]
+
+--kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
+in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
+from a HIP graph over the 32 layers' caches in turn so that no launch finds its keys in a cache."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,6 +24,14 @@ if os.environ.get("MH_GEMV_KSPLIT"):  # A/B: 0 = one wave per row pair in the sm
     _O.gemv_ksplit(os.environ["MH_GEMV_KSPLIT"] != "0")
 if os.environ.get("MH_DECODE_FUSED_MERGE"):  # A/B: 1 = split-KV partials merged by the last block of a (b, h) instead of a second launch
     _O.attn_decode_fused_merge(os.environ["MH_DECODE_FUSED_MERGE"] != "0")
+KV8 = False
+if "--kv" in sys.argv:
+    _i = sys.argv.index("--kv")
+    if sys.argv[_i + 1] not in ("fp8", "16"):
+        raise SystemExit("--kv takes fp8 or 16")
+    KV8 = sys.argv[_i + 1] == "fp8"
+    del sys.argv[_i:_i + 2]
+KV = "fp8" if KV8 else "16-bit"
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 NEW = 160
@@ -30,7 +44,7 @@ g = torch.Generator().manual_seed(0)
 ids = torch.randint(3, 32000, (B, S), generator=g).to(dev)
 with torch.no_grad():
     t0 = time.time()
-    logits, cache = model.engine.prefill(ids, None, None, NEW + 8)
+    logits, cache = model.engine.prefill(ids, None, None, NEW + 8, kv_fp8=KV8)
     torch.cuda.synchronize()
     print(f"prefill B={B} S={S}: {(time.time()-t0)*1e3:.1f} ms (first call, incl. arena setup)", flush=True)
     tok = logits.argmax(-1)
@@ -45,9 +59,34 @@ with torch.no_grad():
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / n
     wbytes = sum(p.numel() for n_, p in model.named_parameters() if n_.startswith("model.layers") or n_.startswith("lm_head") or n_ == "model.norm.weight") * 2
-    cbytes = 2 * 32 * B * (S + 20) * 4096 * 2
-    print(json.dumps({"decode": "eager", "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
+    cbytes = 2 * 32 * B * (S + 20) * ((4096 + 32 * 4) if KV8 else 4096 * 2)  # fp8: one byte per value + one fp32 scale per head
+    print(json.dumps({"decode": "eager", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
                       "hbm_gb_per_step": round((wbytes + cbytes) / 1e9, 2), "hbm_tb_s": round((wbytes + cbytes) / ms / 1e9, 2)}), flush=True)
+    # one decode-attention launch, from a graph of 32 (one per layer's cache: 2+ GB between two visits of the same keys)
+    qa = torch.randn(B, 4096, dtype=torch.bfloat16, device=dev)
+    lens_a = cache.lens.clone()
+    if KV8:
+        attn = lambda li: _O.attn_decode_kv8(qa, *cache.layer(li), lens_a, 32, 128)  # noqa: E731
+    else:
+        attn = lambda li: _O.attn_decode(qa, cache.k[li], cache.v[li], lens_a, 32, 128)  # noqa: E731
+    attn(0)
+    torch.cuda.synchronize()
+    ga = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(ga):
+        for li in range(32):
+            attn(li)
+    for _ in range(2):
+        ga.replay()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(8):
+        ga.replay()
+    e1.record(); torch.cuda.synchronize()
+    us = e0.elapsed_time(e1) / (8 * 32) * 1e3
+    abytes = 2 * B * int(lens_a[0]) * ((4096 + 32 * 4) if KV8 else 4096 * 2)
+    print(json.dumps({"attention_launch": "mh_attn_decode_kv8" if KV8 else "mh_attn_decode", "B": B, "keys": int(lens_a[0]), "us_per_launch": round(us, 2),
+                      "cache_mb_per_launch": round(abytes / 1e6, 1), "hbm_tb_s": round(abytes / us / 1e6, 2)}), flush=True)
+    del ga
     # the same step as one replayed HIP graph
     g, gtok, glog = model.engine.capture_decode_graph(cache)
     gtok.copy_(tok)
@@ -59,7 +98,7 @@ with torch.no_grad():
         g.replay(); gtok.copy_(glog.argmax(-1))
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / n
-    print(json.dumps({"decode": "hip-graph", "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
+    print(json.dumps({"decode": "hip-graph", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
                       "hbm_gb_per_step": round((wbytes + cbytes) / 1e9, 2), "hbm_tb_s": round((wbytes + cbytes) / ms / 1e9, 2)}), flush=True)
     # fp8 weights (e4m3, per-128-block scales), graph replay
     model.engine.quantize_decode_weights()
@@ -74,5 +113,5 @@ with torch.no_grad():
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / n
     w8 = wbytes // 2 + wbytes // 2 // 64  # fp8 bytes + fp32 scales (1 per 128)
-    print(json.dumps({"decode": "hip-graph fp8 weights", "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
+    print(json.dumps({"decode": "hip-graph fp8 weights", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
                       "hbm_gb_per_step": round((w8 + cbytes) / 1e9, 2), "hbm_tb_s": round((w8 + cbytes) / ms / 1e9, 2)}), flush=True)
