@@ -48,6 +48,8 @@ the same inputs in the same run; on the CPU shapes of tests/test_numerics_cpu.py
     gemm+swiglu gu                         0.995        0.995        0.988        0.988
     gemv 16-bit                            0.992        0.992        0.981        0.981
     gemv fp32                              0.112        0.044        0.192        0.043
+    gemv fp8w 16-bit                       0.993        0.993        0.982        0.982
+    gemv fp8w fp32                         0.042        0.057        0.080        0.062
     layernorm db                           0.222        0.222        0.221        0.221
     layernorm dw                           0.315        0.315        0.279        0.279
     layernorm dx                           0.441        0.441        0.445        0.445
@@ -67,6 +69,14 @@ the same inputs in the same run; on the CPU shapes of tests/test_numerics_cpu.py
 
 (Model and kernel mostly agree to three digits: the worst element is one whose error is the rounding of the output itself, and both round the
 same fp32 value.  Where the summation order matters - decode attention, fp32 stores - they differ.)
+
+(The two "gemv fp8w" rows: fp8 weights with per-128-block scales, worst over every arm of mh_gemv_fp8w and the shapes of
+tests/test_fp8_componentwise_gpu.py, 16-bit stores with and without a residual.)
+
+The scaled-fp8 GEMMs are held to |got - want| <= ulp_out(want) + C_ACC 2^-24 sum|ab| instead (see the fp8 section below).  Worst observed
+(|got - want| - ulp) / (2^-24 sum|ab|) on an MI355X, against C_ACC = 512: the 4-wave kernel ~140 (K = 256, fp32 store); the 8-wave kernel over
+the shapes, weight forms and epilogues of tests/test_fp8_componentwise_gpu.py 167 (bf16 store), 185 (fp16 store), 175 (fp32 store), 71 / 104
+(dgrad with block exponents, bf16 / fp16), 36 / 61 (wgrad over 1000 tokens).
 
 The mutants of tests/test_numerics_cpu.py (a tile of keys dropped, a causal mask off by one, AdamW without bias correction, ...) score
 c between 5 and several thousand against limits of 2 to 4; the max-norm metric of tests/test_ops_gpu.py lets most of them pass in bf16.
@@ -164,6 +174,218 @@ def gemm(a, b, *, bias=None, resid=None, c_old=None, gelu=False, a_t=False, b_t=
         cond = cond * ((math.sqrt(K) + 4) * EPS16[torch.float32] / EPS16[od])
         return acc, (cond if staged is None else cond + staged)
     return r16(acc, None if od == torch.float32 else od)
+
+
+# ---- fp8 (OCP e4m3) operands: exact dequantisers, the scaled-fp8 GEMM and the fp8-weight GEMV ---------------------------------------------
+# The scaled fp8 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4) sums a 128-k block's products at LESS than fp32 precision, so the fp8 GEMMs are not
+# held to the (sqrt(K) + 4) 2^-24 form of `gemm` but, per element, to
+#     |got - want| <= ulp_out(want) + C_ACC 2^-24 sum_k |a_k b_k| + epilogue terms
+# with want the float64 product of the EXACTLY dequantised operands (an e4m3 value times an fp32 scale needs 28 bits: `q.float() * s` is itself
+# rounded).  C_ACC is the project's figure for this MFMA (worst observed on an MI355X: ~140 on the 4-wave kernel, K = 256, fp32 store; see the
+# table in the module docstring for the 8-wave kernel); C_OP 2^-24 times the magnitude of the terms an fp32 element-wise op adds is that op's
+# own arithmetic, TINY_OP its flush-to-zero floor.  The fp8-weight GEMV multiplies in dot2 / 16-bit MFMA instructions (exact products, fp32
+# sums) and IS held to `componentwise` with the (sqrt(K) + 4) form.
+C_ACC = 512
+C_OP = 64
+TINY_OP = 2.0 ** -100
+U24 = 2.0 ** -24
+_MANT = {torch.bfloat16: 7, torch.float16: 10, torch.float32: 23}
+_ULP_FLOOR = {torch.bfloat16: 2.0 ** -133, torch.float16: 2.0 ** -24, torch.float32: 2.0 ** -149}
+E4M3_MAX = 448.0
+
+
+def ulp(x, dtype):
+    """Spacing of `dtype` at |x| (float64 tensor), floored at the subnormal spacing."""
+    _, e = torch.frexp(x.abs())
+    return torch.ldexp(torch.ones_like(x), (e - 1 - _MANT[dtype]).to(torch.int32)).clamp_min(_ULP_FLOOR[dtype])
+
+
+def bound_ratio(got, want, err, dtype):
+    """-> (worst |got - want| / (ulp_dtype(want) + err), flat index of that element)."""
+    r = (got.double() - want).abs() / (ulp(want, dtype) + err)
+    c, i = r.reshape(-1).max(0)
+    return float(c), int(i)
+
+
+def check(name, got, want, err, dtype):
+    """every element: |got - want| <= ulp_dtype(want) + err"""
+    d = (got.double() - want).abs()
+    tol = ulp(want, dtype) + err
+    assert torch.isfinite(got.float()).all(), name
+    bad = d > tol
+    if bool(bad.any()):
+        i = int(bad.flatten().nonzero()[0])
+        r, c = divmod(i, want.shape[1])
+        import pytest
+
+        pytest.fail(f"{name}: {int(bad.sum())} of {bad.numel()} elements outside the bound, first [{r}, {c}]: got {float(got.flatten()[i])} "
+                    f"want {float(want.flatten()[i])} bound {float(tol.flatten()[i]):.3e}")
+
+
+def e4m3(q):
+    """uint8 e4m3 bytes -> their values in float64 (exact)."""
+    return q.view(torch.float8_e4m3fn).double()
+
+
+def deq64(q8):
+    """(q uint8 [R, K], s fp32 [R]) of quant_fp8_rows / quant_fp8_rows_t -> float64 [R, K] = q s, exact."""
+    return e4m3(q8[0]) * q8[1].double()[:, None]
+
+
+def exp_group_bytes(K):
+    return ((K // 128) * 64 + 4095) // 4096 * 4096
+
+
+def exp_nibbles(ex, n_rows, K):
+    """Exponent image of quant_fp8_rows_e4 / _rows_t_e4 (include/merlin_hip.h: 16-byte header, then [row / 128][G bytes], a group = [K / 128
+    blocks][64 B], two rows per byte, low nibble = even row) -> int64 [n_rows, K / 128].  The header flag must say whether any exponent is
+    non-zero: the GEMM takes its constant-scale loop while it is 0."""
+    nkb, G = K // 128, exp_group_bytes(K)
+    assert int(ex[:4].view(torch.int32)) == int(bool(ex[16:].any())), "the header flag says whether any exponent is non-zero"
+    img = ex[16:].view(-1, G)
+    rows = torch.arange(n_rows, device=ex.device)
+    byte = img[(rows >> 7)[:, None], torch.arange(nkb, device=ex.device)[None, :] * 64 + ((rows & 127) >> 1)[:, None]]
+    return ((byte >> ((rows & 1) * 4)[:, None]) & 15).long()
+
+
+def exp_image(e, device=None):
+    """The inverse of exp_nibbles: int [N, K / 128] exponents in [0, 15] -> the uint8 image with its header, sized as ops._exp_image sizes it."""
+    Nr, nkb = e.shape
+    device = e.device if device is None else device
+    G = exp_group_bytes(nkb * 128)
+    img = torch.zeros(((Nr + 255) // 256) * 2, G, dtype=torch.uint8)
+    ec = e.cpu().to(torch.uint8)
+    rows = torch.arange(Nr)
+    col = torch.arange(nkb)[None, :] * 64 + ((rows & 127) >> 1)[:, None]
+    grp = (rows >> 7)[:, None].expand(Nr, nkb)
+    for par in (0, 1):  # even rows: low nibble, odd rows: high nibble (two passes: the two rows of a pair share every byte)
+        sel = (rows & 1) == par
+        img[grp[sel], col[sel]] |= ec[sel] << (4 * par)
+    head = torch.zeros(16, dtype=torch.uint8)
+    head[:4] = torch.tensor([int(bool(ec.any()))], dtype=torch.int32).view(torch.uint8)
+    return torch.cat([head, img.reshape(-1)]).to(device)
+
+
+def deq64_e4(q, s, ex, n_rows=None, K=None):
+    """(q [N, K], s [N], exponent image) -> (float64 [N, K] = q s 2^-e per 128-k block, e int64 [N, K / 128]), exact."""
+    n_rows = q.shape[0] if n_rows is None else n_rows
+    K = q.shape[1] if K is None else K
+    e = exp_nibbles(ex, n_rows, K)
+    scale = torch.ldexp(s.double()[:n_rows, None].expand(n_rows, K // 128).contiguous(), (-e).to(torch.int32))
+    return (e4m3(q[:n_rows, :K]).view(n_rows, K // 128, 128) * scale[:, :, None]).view(n_rows, K), e
+
+
+def deq64_any(b8):
+    """(q, s) or (q, s, exponent image or None) -> float64, exact."""
+    if len(b8) > 2 and b8[2] is not None:
+        return deq64_e4(b8[0], b8[1], b8[2])[0]
+    return deq64(b8)
+
+
+def deq64_b128(q, scales):
+    """(q [N, K], scales fp32 [N, ceil(K / 128)]) of quant_fp8_b128 -> float64 [N, K]; the last block may be partial."""
+    K = q.shape[1]
+    return e4m3(q) * scales.double().repeat_interleave(128, dim=1)[:, :K]
+
+
+def exact_block_exp(rowmax, bmax):
+    """floor(log2(rowmax / blockmax)) clamped to [0, 15], 15 for an all-zero block, from the binary exponents and significands (no log2):
+    rowmax [N, 1] and bmax [N, nkb] fp32, as csrc/fp8_quant.hip block_exp computes it."""
+    ma, ea = torch.frexp(rowmax.float())
+    mb, eb = torch.frexp(bmax.float())
+    e = (ea - eb - (ma < mb).to(ea.dtype)).clamp(0, 15)
+    return torch.where(bmax > 0, e, torch.full_like(e, 15)).long()
+
+
+def quant_rows(x):
+    """torch emulation of mh_quant_fp8_rows: s = max|row| (1 / 448) in fp32 (1 for a zero row), bytes = e4m3_rne(x (1 / s))."""
+    amax = x.float().abs().amax(1)
+    s = torch.where(amax > 0, amax * torch.tensor(1.0 / E4M3_MAX, dtype=torch.float32, device=x.device), torch.ones_like(amax))
+    return (x.float() * (1.0 / s)[:, None]).to(torch.float8_e4m3fn).view(torch.uint8), s
+
+
+def quant_b128(w):
+    """torch emulation of mh_quant_fp8_b128: one scale per 128 consecutive k (the last block may be partial)."""
+    Nr, K = w.shape
+    nb = (K + 127) // 128
+    wp = torch.nn.functional.pad(w.float(), (0, nb * 128 - K)).view(Nr, nb, 128)
+    amax = wp.abs().amax(2)
+    s = torch.where(amax > 0, amax * torch.tensor(1.0 / E4M3_MAX, dtype=torch.float32, device=w.device), torch.ones_like(amax))
+    q = (wp * (1.0 / s)[:, :, None]).to(torch.float8_e4m3fn).view(torch.uint8).view(Nr, nb * 128)[:, :K].contiguous()
+    return q, s
+
+
+def gemm_fp8(a8, b8, *, bias=None, gelu=False, resid=None, c_old=None, out_dtype=torch.bfloat16, model=False):
+    """mh_gemm_fp8: C = (sa qa) (sb 2^-e qb)^T (+ bias) (quick-GELU) (+ resid) (+ C_old), the epilogue order of mh_gemm.  a8 = (qa, sa), b8 = (qb,
+    sb[, exponent image]).  -> (want64, err): a kernel's output is held to |got - want64| <= ulp_out(want64) + err (`check`), err = C_ACC 2^-24
+    |A| |B|^T carried through the epilogue: every fp32 add of the store phase contributes C_OP 2^-24 times the magnitude of its two terms,
+    quick-GELU multiplies the error of its argument by QUICK_GELU_SLOPE and adds its own arithmetic - x / (1 + exp(-1.702 x)) with the
+    argument of exp rounded to fp32, which moves the result by |out| (1 - sigmoid) |1.702 x| 2^-24 - plus TINY_OP where it flushes.  C_old is added
+    in fp32 BEFORE the one rounding of the store (csrc/gemm_common.h epi_store4 / EpiStoreFast: `v += o` ahead of pack2 - the 8-wave and
+    128-tile kernels; the 4-wave kernel's staged form is `gemm(..., staged_accumulate=True)`).
+    model=True: the rounding model instead - the integer-valued products summed in fp32, the two row scales multiplied in fp32 and applied
+    once (csrc/gemm256.hip: `acc *= sm * sc_n`), the epilogue in fp32, ONE rounding to out_dtype."""
+    A, Bd = deq64(a8), deq64_any(b8)
+    if model:
+        qb = e4m3(b8[0])
+        if len(b8) > 2 and b8[2] is not None:
+            e = exp_nibbles(b8[2], *b8[0].shape)
+            qb = (qb.view(qb.shape[0], -1, 128) * torch.ldexp(torch.ones_like(e, dtype=torch.float64), (-e).to(torch.int32))[:, :, None]).view(qb.shape)
+        acc = (e4m3(a8[0]).float() @ qb.float().t()) * (a8[1].float()[:, None] * b8[1].float()[None, :])
+        if bias is not None:
+            acc = acc + bias.float()
+        if gelu:
+            acc = acc * torch.sigmoid(1.702 * acc)
+        for extra in (resid, c_old):
+            if extra is not None:
+                acc = acc + extra.float()
+        return r16(acc, None if out_dtype == torch.float32 else out_dtype)
+    want = A @ Bd.t()
+    err = C_ACC * U24 * (A.abs() @ Bd.abs().t())
+    if bias is not None:
+        b64 = bias.double()
+        err = err + C_OP * U24 * (want.abs() + b64.abs())
+        want = want + b64
+    if gelu:
+        z = 1.702 * want
+        sg = torch.sigmoid(z)
+        want = want * sg
+        err = QUICK_GELU_SLOPE * err + C_OP * U24 * want.abs() * (1 + z.abs() * (1 - sg)) + TINY_OP
+    for extra in (resid, c_old):
+        if extra is not None:
+            x64 = extra.double()
+            err = err + C_OP * U24 * (want.abs() + x64.abs())
+            want = want + x64
+    return want, err
+
+
+def _block_sums(X, Q):
+    """X [M, K], Q [N, K] -> [M, N, ceil(K / 128)]: sum of x q over each 128-k block (a partial last block padded with zeros)."""
+    K = X.shape[1]
+    nb = (K + 127) // 128
+    Xp, Qp = (torch.nn.functional.pad(t, (0, nb * 128 - K)) for t in (X, Q))
+    return torch.einsum("mbk,nbk->mnb", Xp.view(X.shape[0], nb, 128), Qp.view(Q.shape[0], nb, 128))
+
+
+def gemv_fp8w(x, q, scales, resid=None, *, out_dtype=None, model=None):
+    """mh_gemv_fp8w: y[m, n] = sum_kb s[n, kb] sum_{k in block kb} q[n, k] x[m, k] (+ resid), (q, scales) from quant_fp8_b128, the scale
+    applied to the block sum as the kernels do (csrc/decode.hip: `acc = fmaf(s, p, acc)`).  -> (ref64, B) for `componentwise`: the products
+    of an e4m3 value and a 16-bit activation are exact (the kernels widen the bytes to 16 bits and multiply in dot2 / MFMA instructions) and the
+    sums are fp32, so as in `gemm` B = (sum_kb |s| sum |q| |x| + |resid|) (sqrt(K) + 4) 2^-24 / eps(out).
+    model=dtype: fp32 block sums, fp32 scale and add, ONE rounding at the store."""
+    wt = torch.float64 if model is None else torch.float32
+    od = x.dtype if out_dtype is None else out_dtype
+    X, Q, S = x.to(wt), e4m3(q).to(wt), scales.to(wt)
+    K = X.shape[1]
+    acc = (_block_sums(X, Q) * S[None]).sum(-1)
+    if resid is not None:
+        acc = acc + resid.to(wt)
+    if model is not None:
+        return r16(acc, None if od == torch.float32 else od)
+    cond = (_block_sums(X.abs(), Q.abs()) * S.abs()[None]).sum(-1)
+    if resid is not None:
+        cond = cond + resid.to(wt).abs()
+    return acc, cond * ((math.sqrt(K) + 4) * EPS16[torch.float32] / EPS16[od])
 
 
 # ---- attention (one head) -----------------------------------------------------------------------------------------------------------------

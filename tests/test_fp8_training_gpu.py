@@ -5,10 +5,14 @@ per row): logits max|d| <= 0.15 (0.20 on the 2432-token interleave sequence: mea
 (>= 0.90 for the CLIP tower, whose gradients arrive through both fp8 dgrad chains) and norms within 10 %; kernels are exact
 against the fp32 product of the dequantised operands."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(__file__))
+import numerics as NUM  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -170,21 +174,14 @@ def test_fp8_gemm_4wave_form_matches_the_8wave_kernel(dtype, M, N, K):
 
 
 def _deq_e4(q, s, ex, n_rows, K):
-    """dequantise (q [N, K] e4m3 bytes, s [N], exponent image) -> fp32 [N, K]"""
-    nkb = K // 128
-    G = (nkb * 64 + 4095) // 4096 * 4096
-    assert int(ex[:4].view(torch.int32)) == int(bool(ex[16:].any())), "the header flag says whether any exponent is non-zero"
-    ex = ex[16:].view(-1, G)
-    rows = torch.arange(n_rows, device=q.device)
-    img = ex[(rows >> 7)].view(n_rows, G)[:, : nkb * 64].reshape(n_rows, nkb, 64)
-    byte = img[rows[:, None], torch.arange(nkb, device=q.device)[None, :], ((rows & 127) >> 1)[:, None]]
-    e = (byte >> ((rows & 1) * 4)[:, None]) & 15
-    scale = s[:, None] * torch.pow(2.0, -e.float())                                   # [N, nkb]
-    return q.view(torch.float8_e4m3fn).float().view(n_rows, nkb, 128) * scale[:, :, None], e
+    """dequantise (q [N, K] e4m3 bytes, s [N], exponent image) -> ([N, K / 128, 128] values, exponents); exact in float64 (tests/numerics.py),
+    rounded to fp32 for the max-norm references below"""
+    d, e = NUM.deq64_e4(q, s, ex, n_rows, K)
+    return d.float().view(n_rows, K // 128, 128), e
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("N,K", [(256, 256), (520, 384), (4096, 4096), (1000, 11008), (11008, 4096)])
+@pytest.mark.parametrize("N,K", [(256, 256), (520, 384), (4096, 4096), (1000, 11008), (11008, 4096), (264, 8320), (200, 512)])
 def test_weight_quantisation_with_per_128_block_exponents(dtype, N, K):
     """BASELINE cfg 5: "fp8-e4m3 weights (per-128-block scales)".  Row scale s[n] = rowmax / 448 and a 4-bit exponent per (row, 128-k
     block): e = floor(log2(rowmax / blockmax)) (so every block's scaled maximum lies in (224, 448]), q = e4m3(w 2^e / s); both the
@@ -200,8 +197,13 @@ def test_weight_quantisation_with_per_128_block_exponents(dtype, N, K):
     deq, e = _deq_e4(q, s, ex, N, K)
     bmax = w.float().abs().view(N, K // 128, 128).amax(dim=2)
     rmax = w.float().abs().amax(dim=1, keepdim=True)
-    e_ref = torch.where(bmax > 0, torch.floor(torch.log2(rmax / bmax.clamp_min(1e-38))).clamp(0, 15), torch.full_like(bmax, 15)).long()
-    assert int((e.long() - e_ref).abs().max()) <= 1 and float((e.long() != e_ref).float().mean()) < 1e-3  # (log2 at exact powers of two)
+    # the exact floor from the binary exponents and significands, as csrc/fp8_quant.hip block_exp takes it with frexpf: no log2, no tolerance
+    e_ref = NUM.exact_block_exp(rmax, bmax)
+    assert torch.equal(e.long(), e_ref)
+    # the bytes: torch's e4m3 rounding of w * (2^e / s), the kernel's own arithmetic (fp32 reciprocal, exact power of two, one fp32 product)
+    inv = torch.ldexp(1.0 / s, e.to(torch.int32).t()).t()                    # [N, K / 128]
+    q_ref = (w.float().view(N, K // 128, 128) * inv[:, :, None]).to(torch.float8_e4m3fn)
+    assert torch.equal(q.view(torch.float8_e4m3fn).float().view(N, K // 128, 128), q_ref.float())
     err = (deq.view(N, K) - w.float()).abs().view(N, K // 128, 128).amax(dim=2)
     ok = err <= bmax * 2.0 ** -4 + 1e-12                                     # e4m3: <= 2^-4 relative to the BLOCK maximum, small blocks included
     assert bool(ok.all())
@@ -210,9 +212,20 @@ def test_weight_quantisation_with_per_128_block_exponents(dtype, N, K):
     qt, st, ext = O.quant_fp8_rows_t_e4(w)
     Np = (N + 127) // 128 * 128
     assert qt.shape == (K, Np) and torch.allclose(st, w.float().abs().amax(dim=0) / 448.0, rtol=1e-6)
-    deqt, _ = _deq_e4(qt, st, ext, K, Np)
+    deqt, et = _deq_e4(qt, st, ext, K, Np)
     wt = torch.zeros(K, Np, device="cuda")
     wt[:, :N] = w.float().t()
+    # exponents: this kernel has the row maximum only as s * 448 (fp32), which can lie one ulp below the true maximum; where a block's maximum
+    # has the same significand as the row's, the exact floor then comes out one lower (the block is scaled to 224 instead of 448: no loss)
+    btmax = wt.abs().view(K, Np // 128, 128).amax(dim=2)
+    tmax = wt.abs().amax(dim=1, keepdim=True)
+    assert torch.equal(et.long(), NUM.exact_block_exp(st[:, None] * 448.0, btmax))
+    e_true = NUM.exact_block_exp(tmax, btmax)
+    low = et.long() != e_true
+    assert bool(((e_true - et.long())[low] == 1).all()) and bool(((st[:, None] * 448.0 < tmax).expand_as(low)[low]).all())
+    invt = torch.ldexp(1.0 / st, et.to(torch.int32).t()).t()                 # [K, Np / 128]
+    qt_ref = (wt.view(K, Np // 128, 128) * invt[:, :, None]).to(torch.float8_e4m3fn)
+    assert torch.equal(qt.view(torch.float8_e4m3fn).float().view(K, Np // 128, 128), qt_ref.float())
     errt = (deqt.view(K, Np) - wt).abs().view(K, Np // 128, 128).amax(dim=2)
     assert bool((errt <= wt.abs().view(K, Np // 128, 128).amax(dim=2) * 2.0 ** -4 + 1e-12).all())
 

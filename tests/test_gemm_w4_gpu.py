@@ -2,10 +2,16 @@
 SwiGLU-backward dgrad, fp32 outputs (plain / accumulating), split-K with fp32 partials, K tails of K-strided operands (rows >= K read as
 zeros through the buffer descriptor's range check) and the grouped weight-gradient launch - each against a plain fp32 torch reference of
 the same op on 16-bit-rounded inputs, and against the 8-wave kernel where that kernel has the same form."""
+import os
+import sys
+
 import pytest
 import torch
 
 from test_ops_gpu import DTYPES, EPS16, dev, relerr, rnd
+
+sys.path.insert(0, os.path.dirname(__file__))
+from numerics import C_ACC, C_OP, TINY_OP, U24, check as _check, deq64 as _deq64, ulp as _ulp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -259,25 +265,11 @@ def test_w4_half_tiles_are_bit_identical_to_the_256_row_tiles(ops, dtype, M):
 # sum|ab| (K = 256, fp32 store; 16 failed there).  A bound relative to the tensor's max would hide an error confined to a few accumulator
 # registers of every tile (the loop-exit copies of tests/test_kernel_hazards_cpu.py); this one does not: one MFMA's 128-k contribution
 # missing from an element is typically ~sqrt(128) rms|ab|, above 2.5e4 2^-24 sum|ab| (50 x the bound) at every shape below.
-C_ACC = 512
-C_OP = 64
-TINY_OP = 2.0 ** -100
-U24 = 2.0 ** -24
-_MANT = {torch.bfloat16: 7, torch.float16: 10, torch.float32: 23}
-_TINY = {torch.bfloat16: 2.0 ** -133, torch.float16: 2.0 ** -24, torch.float32: 2.0 ** -149}
+# (C_ACC, C_OP, TINY_OP and the helpers live in tests/numerics.py, shared with the 8-wave kernel's tests.)
 
 # (M, N, K): the smallest admitted K (256: two 128-byte K-tiles, one loop iteration), K = 4096 and K = 11008, with M and N on and off the 256-row /
 # column tile edges; the last one is 16 x 16 = 256 tiles (fills the chip)
 F8_SHAPES = [(256, 512, 256), (300, 264, 256), (520, 776, 4096), (300, 520, 11008), (4096, 4096, 4096)]
-
-
-def _ulp(x, dtype):
-    _, e = torch.frexp(x.abs())
-    return torch.ldexp(torch.ones_like(x), (e - 1 - _MANT[dtype]).to(torch.int32)).clamp_min(_TINY[dtype])
-
-
-def _deq64(q8):
-    return q8[0].view(torch.float8_e4m3fn).double() * q8[1].double()[:, None]
 
 
 def _f8_three(ops, fn):
@@ -287,19 +279,6 @@ def _f8_three(ops, fn):
         for a, b in zip(outs[0] if isinstance(outs[0], tuple) else (outs[0],), o if isinstance(o, tuple) else (o,)):
             assert torch.equal(a, b)
     return outs[0]
-
-
-def _check(name, got, want, err, dtype):
-    """every element: |got - want| <= ulp_dtype(want) + err"""
-    d = (got.double() - want).abs()
-    tol = _ulp(want, dtype) + err
-    assert torch.isfinite(got.float()).all(), name
-    bad = d > tol
-    if bool(bad.any()):
-        i = int(bad.flatten().nonzero()[0])
-        r, c = divmod(i, want.shape[1])
-        pytest.fail(f"{name}: {int(bad.sum())} of {bad.numel()} elements outside the bound, first [{r}, {c}]: got {float(got.flatten()[i])} "
-                    f"want {float(want.flatten()[i])} bound {float(tol.flatten()[i]):.3e}")
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -1,6 +1,14 @@
 """The per-element checker of tests/numerics.py against itself, without a GPU: for every operation it must ACCEPT the rounding model (the fp32
 evaluation with the kernels' 16-bit roundings) and REJECT every mutant - a plain fp64 reference with one deliberate defect, stored in the 16-bit
-type like a kernel's output - at c >= 2 x the limit the kernels are held to.  Every line printed is `mutant dtype: c vs limit`."""
+type like a kernel's output - at c >= 2 x the limit the kernels are held to.  Every line printed is `mutant dtype: c vs limit`.
+
+The fp8 cases also print what the metric they replace gives for the same mutant: relerr = max|got - ref| / max|ref| in units of eps16, which
+tests/test_fp8_training_gpu.py and tests/test_ops_gpu.py hold below 3 to 4.  Any error below 1.2 % of the LARGEST output of the tensor passes
+it in bf16.  Of the mutants below it lets through, in bf16, "bias added twice in one column" at the weight size its own tests use (sigma 0.3:
+1.1 eps16 against a limit of 4; 7.5 x the per-element bound) and comes within 10 % of passing it at sigma 0.05 (4.45 eps16; 44 x the bound); it
+scores "one lane's 16 values skipped" of the GEMV at 5.3 to 7.4 eps16 against its limit of 3 (c = 20 to 31 against 2).  The other
+mutants are built on weights whose block scales differ by powers of two and move a whole row or block by more than that metric's limit too;
+in fp16, whose eps is 8 times smaller, it catches all of them."""
 import math
 import os
 import sys
@@ -252,3 +260,145 @@ def test_adamw_reference_is_torch_adamw_in_fp64():
         out = N.adamw_step(p, g, m, v, step=step, gscale=0.5, **hp)
         p, m, v = out["p"], out["m"], out["v"]
         assert p.dtype == torch.float64 and float((p - tp.detach()).abs().max()) <= 1e-13 * float(tp.detach().abs().max()), step
+
+
+# ---- fp8: the scaled-fp8 GEMM (|got - want| <= ulp + err) and the fp8-weight GEMV (componentwise) ----------------------------------------------
+def old_metric(got, ref, dtype):
+    """max|got - ref| / max|ref| in units of eps16: what the max-norm tests hold below 3 to 4."""
+    return float((got.double() - ref).abs().max() / ref.abs().max()) / N.EPS16[dtype]
+
+
+def block_scaled(w, zero_row=None, zero_block=None):
+    """Block kb of row n scaled by 2^-((n + kb) % 4): adjacent rows and adjacent blocks differ by powers of two."""
+    Nr, K = w.shape
+    nb = (K + 127) // 128
+    f = torch.ldexp(torch.ones(Nr, nb), -((torch.arange(Nr)[:, None] + torch.arange(nb)[None, :]) % 4).to(torch.int32))
+    out = w.float() * f.repeat_interleave(128, dim=1)[:, :K]
+    if zero_row is not None:
+        out[zero_row] = 0
+    if zero_block is not None:
+        out[zero_block[0], zero_block[1] * 128:(zero_block[1] + 1) * 128] = 0
+    return out.to(w.dtype)
+
+
+def reject_bound(name, dtype, got, want, err, out_dtype=None, old_limit=4.0):
+    od = dtype if out_dtype is None else out_dtype
+    g = got.to(od) if got.dtype == torch.float64 else got
+    r, _ = N.bound_ratio(g, want, err, od)
+    om = old_metric(g, want, dtype)
+    print(f"mutant {name:44s} {str(dtype)[6:]:9s} |d| / bound = {r:10.1f}   old metric = {om:8.2f} eps16 (limit {old_limit}: {'PASSES' if om < old_limit else 'caught'})")
+    assert r >= 2.0, (name, dtype, r)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_fp8_gemm_model_accepted_and_mutants_rejected(dtype):
+    M, Nn, K = 64, 136, 8320  # 65 blocks: the exponent group is padded; N is no multiple of the 128-row group
+    nkb = K // 128
+    x, w = rnd(M, K, dtype=dtype), rnd(Nn, K, dtype=dtype, seed=1, scale=0.05)
+    bias, resid = rnd(Nn, dtype=dtype, seed=2), rnd(M, Nn, dtype=dtype, seed=3)
+    a8, (qb, sb) = N.quant_rows(x), N.quant_rows(w)
+    e = (torch.arange(Nn)[:, None] + torch.arange(nkb)[None, :]) % 4
+    ex = N.exp_image(e)
+    assert torch.equal(N.exp_nibbles(ex, Nn, K), e)  # the image builder and its reader are inverses
+    b8 = (qb, sb, ex)
+    for kw in ({}, {"bias": bias}, {"bias": bias, "gelu": True}, {"resid": resid}, {"bias": bias, "resid": resid}, {"c_old": resid}):
+        for od in (dtype, torch.float32):
+            if od == torch.float32 and kw and "c_old" not in kw:
+                continue
+            want, err = N.gemm_fp8(a8, b8, out_dtype=od, **kw)
+            r, _ = N.bound_ratio(N.gemm_fp8(a8, b8, out_dtype=od, model=True, **kw), want, err, od)
+            print(f"model  fp8 gemm {'+'.join(kw) or 'plain':16s} {str(dtype)[6:]:9s} -> {str(od)[6:]:9s} |d| / bound = {r:.3f}")
+            assert r <= 1.0, (kw, od, r)
+    A = N.deq64(a8)
+    Bd, _ = N.deq64_e4(qb, sb, ex)
+    Bq = N.deq64((qb, sb)).view(Nn, nkb, 128)  # without the exponents
+
+    def with_exps(e2):
+        return (Bq * torch.ldexp(torch.ones(Nn, nkb, dtype=torch.float64), (-e2).to(torch.int32))[:, :, None]).view(Nn, K)
+
+    want, err = N.gemm_fp8(a8, b8, out_dtype=dtype)
+    e2 = e.clone(); e2[5, 6] = 0  # (5 + 6) % 4 = 3
+    reject_bound("one (row, block) exponent taken as 0", dtype, A @ with_exps(e2).t(), want, err)
+    e2 = e.clone(); e2[[130, 131]] = e[[131, 130]]
+    reject_bound("nibbles of an even/odd row pair swapped", dtype, A @ with_exps(e2).t(), want, err)
+    short = want.clone(); short[48:64] -= A[48:64, -128:] @ Bd[:, -128:].t()
+    reject_bound("last 128-k block missing for 16 rows", dtype, short, want, err)
+    nb_sa = want.clone(); nb_sa[M - 1] *= float(a8[1][M - 2]) / float(a8[1][M - 1])
+    assert float(a8[1][M - 2]) != float(a8[1][M - 1])
+    reject_bound("last row of a tile uses its neighbour's sa", dtype, nb_sa, want, err)
+    want, err = N.gemm_fp8(a8, b8, bias=bias, out_dtype=dtype)
+    twice = want.clone(); twice[:, 77] += bias[77].double()
+    reject_bound("bias added twice in one column", dtype, twice, want, err)
+    # ... and with weights of the size the max-norm tests use (sigma 0.3: outputs of +-100, next to which one bias is 1 % of the largest)
+    b8w = (*N.quant_rows(rnd(Nn, K, dtype=dtype, seed=1, scale=0.3)), ex)
+    want, err = N.gemm_fp8(a8, b8w, bias=bias, out_dtype=dtype)
+    twice = want.clone(); twice[:, 77] += bias[77].double()
+    reject_bound("bias added twice in one column, sigma_w 0.3", dtype, twice, want, err)
+    want, err = N.gemm_fp8(a8, b8, bias=bias, gelu=True, out_dtype=dtype)
+    prod = A @ Bd.t()
+    reject_bound("quick-GELU applied before the bias", dtype, prod * torch.sigmoid(1.702 * prod) + bias.double(), want, err)
+    # C_old: N % 4 != 0 is the scalar store path
+    M2, N2, K2 = 72, 262, 256
+    x2, w2, old = rnd(M2, K2, dtype=dtype), rnd(N2, K2, dtype=dtype, seed=1, scale=0.05), rnd(M2, N2, dtype=dtype, seed=4)
+    a2, b2 = N.quant_rows(x2), N.quant_rows(w2)
+    want, err = N.gemm_fp8(a2, b2, c_old=old, out_dtype=dtype)
+    r, _ = N.bound_ratio(N.gemm_fp8(a2, b2, c_old=old, out_dtype=dtype, model=True), want, err, dtype)
+    assert r <= 1.0, r
+    lost = want.clone(); lost[:, N2 - N2 % 4:] -= old[:, N2 - N2 % 4:].double()
+    reject_bound("C_old ignored in the last N % 4 columns", dtype, lost, want, err)
+    # the OLD reference - q.float() * s, an fp32 product that rounds (4 + 24 significant bits) - stays inside the bound: it must be accepted
+    want, err = N.gemm_fp8(a8, b8, out_dtype=torch.float32)
+    A32 = (N.e4m3(a8[0]).float() * a8[1][:, None]).double()
+    B32 = (N.e4m3(qb).float().view(Nn, nkb, 128) * (sb[:, None] * torch.ldexp(torch.ones(Nn, nkb), (-e).to(torch.int32)))[:, :, None]).view(Nn, K).double()
+    assert not torch.equal(A32, A)
+    r, _ = N.bound_ratio(A32 @ B32.t(), want, err, torch.float32)
+    print(f"accept fp32-rounded dequantised reference    {str(dtype)[6:]:9s} |d| / bound = {r:.4f} (fp32 store: margin {1 / r:.0f} x)")
+    assert r <= 0.05, r  # two operand roundings of 2^-24 each against 512 2^-24 sum|ab|: at most 2 / 512
+
+
+GEMV_SHAPES = [(1, 264, 4096), (3, 515, 272), (2, 256, 11008), (13, 515, 2112), (8, 72, 144)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,Nn,K", GEMV_SHAPES)
+def test_fp8_weight_gemv_model_accepted_and_mutants_rejected(dtype, M, Nn, K):
+    nb = (K + 127) // 128
+    x, resid = rnd(M, K, dtype=dtype), rnd(M, Nn, dtype=dtype, seed=2)
+    w = block_scaled(rnd(Nn, K, dtype=dtype, seed=1, scale=0.5), zero_row=7, zero_block=(9, nb - 1))
+    q, sc = N.quant_b128(w)
+    assert float(sc[7].min()) == 1.0 == float(sc[9, nb - 1]) and int(q[7].max()) == 0
+    assert float((N.deq64_b128(q, sc) - w.double()).abs().max()) <= 2.0 ** -4 * float(w.float().abs().max())  # the dequantiser inverts the quantiser
+    lims = {}
+    for od, rs in ((dtype, None), (dtype, resid), (torch.float32, None), (torch.float32, resid)):
+        ref, Bc = N.gemv_fp8w(x, q, sc, rs, out_dtype=od)
+        c = N.componentwise(N.gemv_fp8w(x, q, sc, rs, out_dtype=od, model=dtype), ref, Bc, N.EPS16[od], N.TINY[od])[0]
+        print(f"model  gemv fp8w {M}x{Nn}x{K} {'+resid' if rs is not None else '      '} {str(dtype)[6:]:9s} -> {str(od)[6:]:9s} c = {c:.3f}")
+        assert c <= (1.0 if od == dtype else 0.5), (od, c)  # one rounding at a 16-bit store; fp32: B is the worst case of a K-term sum
+        lims[(od, rs is not None)] = N.limit(c)
+    X, Q, S = x.double(), N.e4m3(q), sc.double()
+    bs = N._block_sums(X, Q)  # [M, N, nb]
+    ref, Bc = N.gemv_fp8w(x, q, sc, resid)
+    lim = lims[(dtype, True)]
+
+    def rej(name, got, old_limit=3.0):
+        g = got.to(dtype)
+        c = score(g, ref, Bc, dtype)
+        om = old_metric(g, ref, dtype)
+        print(f"mutant {name:44s} {M}x{Nn}x{K} {str(dtype)[6:]:9s} c = {c:9.1f} limit = {lim:.2f}   old metric = {om:7.2f} eps16 "
+              f"(limit {old_limit}: {'PASSES' if om < old_limit else 'caught'})")
+        assert c >= 2 * lim, (name, c, lim)
+
+    if K % 128:
+        S2 = S.clone(); S2[:, nb - 1] = S[:, nb - 2]
+        rej("partial last block takes the previous scale", (bs * S2[None]).sum(-1) + resid.double())
+    n0 = 4  # a row whose first block has exponent 0
+    lane = ref.clone(); lane[:, n0] -= S[n0, 0] * (X[:, 16:32] @ Q[n0, 16:32])
+    rej("one lane's 16 values skipped", lane)
+    S2 = S.clone(); S2[n0] = S[n0 + 1]
+    rej("a row reads its neighbour's scales", (bs * S2[None]).sum(-1) + resid.double())
+    nores = ref.clone(); nores[M - 1] -= resid[M - 1].double()
+    rej("residual skipped for row M - 1", nores)
+    if K > 2048:
+        idx = torch.arange(nb)
+        idx = torch.where(idx >= 16, idx - 16, idx)
+        rej("second K chunk starts again at block 0", (bs * S[:, idx][None]).sum(-1) + resid.double())
