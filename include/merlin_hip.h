@@ -307,9 +307,18 @@ int mh_gemv(const void* x, int64_t ldx, const void* W, int64_t ldw, void* out, i
 int mh_quant_fp8_b128(const void* w, int64_t ldw, void* q, float* scales, int N, int K, int dt, void* stream);
 int mh_gemv_fp8w(const void* x, int64_t ldx, const void* q, const float* scales, void* out, int64_t ldo, const void* resid,
                  int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream);
+/* MXFP4 weight path of the decode step (OCP MX: e2m1 values, one power-of-two E8M0 scale per 32 consecutive k of a row; activations
+ * stay `dt`).  mh_quant_fp4_b32: q[N, K/2] bytes (byte j of a row = element 2j in the low nibble, 2j + 1 in the high one; code s e e m =
+ * magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) + scales[N, K/32] bytes (e + 127) from w[N, K] (`dt`), K % 32 == 0: e is the smallest integer
+ * with max|block| 2^-e <= 6 (>= -126; 0 for an all-zero block), the values round to nearest with ties to the even code, nothing
+ * saturates.  mh_gemv_fp4w: as mh_gemv_fp8w with the weight given as that pair, y = sum_kb 2^e sum_{k in block} q x (+ resid); up to 16
+ * rows (MFMA form from 3 rows on where K % 64 == 0, otherwise <= 8 rows). */
+int mh_quant_fp4_b32(const void* w, int64_t ldw, void* q, void* scales, int N, int K, int dt, void* stream);
+int mh_gemv_fp4w(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid,
+                 int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream);
 /* mh_gemv / mh_gemv_fp8w take up to 16 activation rows; from 3 rows on they run as an MFMA kernel (16-64 weight rows per block
  * streamed straight into the B-operand registers, activations straight into the A operand, K split over 8-16 waves) instead of one
- * wave per weight row.  A/B switch (sets the threshold for both weight formats; 17 = never, <= 0 = default): */
+ * wave per weight row.  A/B switch (sets the threshold for every weight format, mh_gemv_fp4w and its SwiGLU form included; 17 = never, <= 0 = default): */
 void mh_gemv_mfma_min_rows(int rows);
 /* Row count from which the decode projections with a paired epilogue (mh_gemv_swiglu, mh_gemv_qkv_rope, mh_gemv_fp8w_norm with ff > 0)
  * use the MFMA form: 16-bit weights (default 6) and fp8 weights (default 4); <= 0 = default. */
@@ -331,6 +340,9 @@ int mh_gemv_norm(const void* x, int64_t ldx, const void* norm_w, float eps, cons
 /* The same with fp8 (OCP e4m3, one fp32 scale per 128 k: mh_quant_fp8_b128) weights; norm_w == NULL: no norm (x is used as it is). */
 int mh_gemv_fp8w_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const float* scales, void* out, int64_t ldo,
                       int M, int N, int K, int ff, int dt, void* stream);
+/* The same with MXFP4 weights (mh_quant_fp4_b32); norm_w == NULL: no norm.  With norm_w: M <= 8, K <= 8192; without: M <= 16. */
+int mh_gemv_fp4w_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* out, int64_t ldo,
+                      int M, int N, int K, int ff, int dt, void* stream);
 /* The q|k|v projection of one decode step in ONE launch: optional input_layernorm (norm_w, may be NULL), projection with 16-bit weights W
  * [3 H D, K] or (W == NULL) fp8 weights q8 + scales, rotate-half RoPE of q and k at pos[m] (llama_flash_attn_monkey_patch.py:56-59 on one
  * token) and the append of k, v to kcache / vcache [M, Smax, H D] at row pos[m].  qkv [M, 3 H D] gets the rotated q, k and v.  Equal to
@@ -341,6 +353,11 @@ int mh_gemv_fp8w_norm(const void* x, int64_t ldx, const void* norm_w, float eps,
 int mh_gemv_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, const void* W, int64_t ldw, const void* q8, const float* scales,
                      void* qkv, int64_t ldo, int M, int K, int dt, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos,
                      void* kcache, void* vcache, int H, int D, int Smax, void* stream);
+/* mh_gemv_qkv_rope with MXFP4 weights q + scales (mh_quant_fp4_b32).  Equal to mh_rmsnorm_fwd + mh_gemv_fp4w + mh_decode_rope_append
+ * bit for bit.  M <= 8, K <= 8192. */
+int mh_gemv_fp4w_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* qkv,
+                          int64_t ldo, int M, int K, int dt, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos,
+                          void* kcache, void* vcache, int H, int D, int Smax, void* stream);
 /* qkv [B, 3, H, D] of the new tokens: rotate q and k in place at position rope_pos[b] (int32, device; NULL = pos), copy k and v into
  * kcache / vcache [B, Smax, H*D] at row pos[b]. */
 int mh_decode_rope_append(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kcache, void* vcache, int B,

@@ -18,6 +18,8 @@
 //                       accumulation of p.V (coalesced value rows); split-KV partials merged by a second kernel.  Keys [0, len[b]).
 //   mh_kv8_fill / mh_decode_rope_append_kv8 / mh_attn_decode_kv8   the same step on an fp8 KV cache (e4m3 bytes + one power-of-two scale
 //                       per (sequence, head, token)): prefill quantiser, RoPE + quantised append, attention reading half the bytes per key.
+//   mh_quant_fp4_b32 / mh_gemv_fp4w / mh_gemv_fp4w_norm / mh_gemv_fp4w_qkv_rope   the projections on MXFP4 weights (e2m1 values, two per byte, one
+//                       power-of-two scale byte per 32 k: 0.53 bytes per weight, 3.6 GB per token at 7B) - at the end of this file.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include "mh_common.h"
 
@@ -1191,11 +1193,15 @@ static int g_gemv_mfma_min_rows = 3, g_gemv_mfma_min_rows_fp8 = 3;
 // the forms with a paired epilogue (SwiGLU, RoPE + append) compete with one-wave-per-row-pair kernels that already fuse the same work
 // and stream at 4.3-4.5 TB/s up to ~5 rows: measured crossover 6 rows with 16-bit weights, 4 with fp8 (mh_gemv_mfma_pair_min_rows)
 static int g_gemv_mfma_pair_min = 6, g_gemv_mfma_pair_min_fp8 = 4;
+// MXFP4 weights (mh_gemv_fp4w*, at the end of this file): the same thresholds (see gemv_fp4w_impl)
+static int g_gemv_mfma_min_rows_fp4 = 3, g_gemv_mfma_pair_min_fp4 = 4;
 static int g_gemv_ksplit = 1;  // 1-2 rows, N <= 8192: K split over the four waves of a block (A-B switch: mh_gemv_ksplit)
 extern "C" void mh_gemv_ksplit(int on) { g_gemv_ksplit = on ? 1 : 0; }
 extern "C" void mh_gemv_mfma_min_rows(int rows) {
   if (rows <= 0) { g_gemv_mfma_min_rows = 3; g_gemv_mfma_min_rows_fp8 = 3; g_gemv_mfma_pair_min = 6; g_gemv_mfma_pair_min_fp8 = 4; }  // the defaults
   else g_gemv_mfma_min_rows = g_gemv_mfma_min_rows_fp8 = g_gemv_mfma_pair_min = g_gemv_mfma_pair_min_fp8 = rows;
+  if (rows <= 0) { g_gemv_mfma_min_rows_fp4 = 3; g_gemv_mfma_pair_min_fp4 = 4; }
+  else g_gemv_mfma_min_rows_fp4 = g_gemv_mfma_pair_min_fp4 = rows;
 }
 extern "C" void mh_gemv_mfma_pair_min_rows(int rows16, int rows_fp8) {
   g_gemv_mfma_pair_min = rows16 > 0 ? rows16 : 6;
@@ -1535,4 +1541,452 @@ extern "C" int mh_gemv_qkv_rope(const void* x, int64_t ldx, const void* norm_w, 
   const int N = 3 * H * D;
   if (W) return gemv_impl(x, ldx, W, ldw, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream);
   return gemv_fp8w_impl(x, ldx, q8, scales, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream);
+}
+
+// ---- MXFP4 weights (OCP MX: e2m1 values, one power-of-two E8M0 scale per 32 consecutive k), bf16/f16 activations -----------------------
+// The next halving of the weight stream after fp8: 0.53 bytes per weight.  Stored format (the contract, also what a later
+// v_mfma_scale_*_f8f6f4 prefill would read): q [N, K/2] bytes, byte j of a row = element 2j in the LOW nibble and 2j + 1 in the high
+// one, code s e e m = magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; scales [N, K/32] bytes = e + 127.
+// Scale: the rule of kv8_exp moved to a maximum of 6 - e the smallest integer with amax 2^-e <= 6 (amax = m 2^ex, m in [0.5, 1):
+// e = ex - 3 if m <= 0.75 else ex - 2), clamped to >= -126, 0 for an all-zero block: nothing saturates.  Value: w 2^-e (exact in fp32)
+// rounded to the e2m1 grid, ties to the code with an even mantissa bit - in plain compares, so the tie rule does not depend on what
+// v_cvt_scalef32_pk_fp4_f32 does (the quantiser runs once per weight change).  q 2^e is exact in bf16 (and in fp16 while in range): the
+// fp4 path is the 16-bit path on weights rounded to that grid.
+namespace {
+
+__device__ __forceinline__ int fp4_exp(float amax) {  // amax >= 0, finite
+  const uint32_t bits = __float_as_uint(amax);
+  const int ef = (int)(bits >> 23);
+  if (ef == 0) return bits ? -126 : 0;  // fp32 subnormal (a bf16 subnormal block): e < -126 clamps
+  return max(ef - 126 - ((bits & 0x7fffffu) <= 0x400000u ? 3 : 2), -126);
+}
+__device__ __forceinline__ uint32_t fp4_code(float v, float inv) {  // |v| inv <= 6
+  const float a = fabsf(v) * inv;
+  const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                     (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);  // ties: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4
+  return c | ((__float_as_uint(v) >> 28) & 8u);
+}
+__device__ __forceinline__ float e8m0_to_f32(uint32_t byte) { return __uint_as_float(byte << 23); }  // byte in [1, 254]; 0 (a masked block) -> 0.0
+
+// one launch: 4 lanes per 32-element block (16-byte loads, block maximum by two shuffles, one 4-byte store of 8 codes per lane)
+template <int DT>
+__global__ __launch_bounds__(256) void quant_fp4_b32_k(const uint16_t* __restrict__ w, int64_t ldw, uint8_t* __restrict__ q,
+                                                       uint8_t* __restrict__ sc, int N, int K) {
+  const int nb = K >> 5;
+  const int64_t blk = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+  if (blk >= (int64_t)N * nb) return;  // (whole groups of 4 lanes)
+  const int n = (int)(blk / nb), kb = (int)(blk % nb), part = threadIdx.x & 3;
+  const int k0 = kb * 32 + part * 8;
+  float v[8];
+  unpack8<DT>(*(const uint4*)(w + (int64_t)n * ldw + k0), v);
+  float mx = amax8(v);
+  mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+  const int e = fp4_exp(mx);
+  const float inv = kv8_pow2(-e);  // e in [-126, 126]
+  uint32_t p = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) p |= fp4_code(v[i], inv) << (4 * i);
+  *(uint32_t*)(q + (int64_t)n * (K >> 1) + (k0 >> 1)) = p;
+  if (part == 0) sc[(int64_t)n * nb + kb] = (uint8_t)(e + 127);
+}
+
+// eight e2m1 values (a dword) -> four packed 16-bit pairs, one instruction per pair (gfx950 v_cvt_scalef32_pk_*_fp4 with scale 1: the
+// third operand selects the byte, whose low nibble becomes the low half of the pair - the stored order, so no swap); exact in both types
+template <int DT>
+__device__ __forceinline__ void fp4x8_to_pk16(uint32_t p, uint32_t* w) {
+  if constexpr (DT == MH_BF16) {
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 0));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 1));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 2));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 3));
+  } else {
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 0));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 1));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 2));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 3));
+  }
+}
+
+// y[m, n] = sum_kb 2^e[n, kb] * sum_{k in block} q[n, k] x[m, k] (+ resid): gemv_fp8w_k with fp4 weights.  One wave per ROWS weight
+// rows; a lane's 16-byte load is 32 values = exactly one scale block, a wave step 2048 values.  The codes become packed 16-bit pairs
+// (exact) and meet the activations in dot2 instructions; the block's fp32 sum is scaled once (16 cvt + 16 x MM dot2 + MM fma per row
+// and load).  K % 32 == 0.  1-2 rows (and NORM): the K loop is not chunked and two steps of every row are requested before the first
+// is consumed; LDSX: chunks of GEMV_KC = one step.  (NORM / swi_ff / ra: the fused RMSNorm, SwiGLU and RoPE + append of gemv_k.)
+template <int DT, int MM, int ROWS, bool LDSX, bool NORM = false>
+__global__ __launch_bounds__(256) void gemv_fp4w_k(const uint16_t* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ q,
+                                                   const uint8_t* __restrict__ sc, void* __restrict__ out, int64_t ldo,
+                                                   const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32, int swi_ff,
+                                                   const uint16_t* __restrict__ norm_w, float eps, RopeAppend ra) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t xs4[];  // [MM][GEMV_KC] when LDSX (as in gemv_k), [MM][K] when NORM
+  __shared__ float red[NORM ? MM : 1][4];
+  constexpr bool CHUNK = LDSX && !NORM;
+  constexpr int NSTEP = CHUNK ? 1 : 2;
+  const int xstride = NORM ? K : GEMV_KC;
+  const int lane = threadIdx.x & 63;
+  const int NR = swi_ff > 0 ? ROWS / 2 : ROWS;  // output columns per wave
+  const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
+  const int nb = K >> 5;
+  float acc[ROWS][MM];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+    for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
+  const uint8_t* qrow[ROWS];
+  const uint8_t* srow[ROWS];
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) {
+    int n = swi_ff > 0 ? (r < NR ? min(n0 + r, N - 1) : swi_ff + min(n0 + r - NR, N - 1)) : min(n0 + r, N - 1);
+    if (ROWS == 2 && ra.tab) {  // rotary pair (as in gemv_k)
+      const int half = ra.D >> 1, pidx = min(n0 >> 1, (N >> 1) - 1), per_sec = ra.H * half;
+      const int sec = pidx / per_sec, rem = pidx - sec * per_sec, h = rem / half;
+      n = sec * ra.H * ra.D + h * ra.D + (rem - h * half) + r * half;
+    }
+    qrow[r] = q + (int64_t)n * (K >> 1);
+    srow[r] = sc + (int64_t)n * nb;
+  }
+  for (int kc = 0; kc < K; kc += GEMV_KC) {
+    const int klen = CHUNK ? min(GEMV_KC, K - kc) : K;
+    if constexpr (NORM) {
+      stage_rmsnorm<DT, MM>(x, ldx, norm_w, eps, K, xs4, red);
+    } else if constexpr (LDSX) {
+      if (kc) __syncthreads();
+      for (int i = threadIdx.x * 8; i < MM * klen; i += 256 * 8) {
+        const int m = i / klen, k = i - m * klen;
+        *(uint4*)(xs4 + m * GEMV_KC + k) = *(const uint4*)(x + (int64_t)m * ldx + kc + k);
+      }
+      __syncthreads();
+    }
+    if (n0 < N) {
+      for (int k0 = lane * 32; k0 < klen; k0 += 2048 * NSTEP) {
+        uint4 qv[NSTEP][ROWS];
+        uint32_t sb[NSTEP][ROWS];
+#pragma unroll
+        for (int u = 0; u < NSTEP; ++u)
+#pragma unroll
+          for (int r = 0; r < ROWS; ++r) {
+            const int kk = k0 + u * 2048;
+            const bool ok = kk < klen;
+            qv[u][r] = ok ? ld_stream16(qrow[r] + ((kc + kk) >> 1)) : make_uint4(0, 0, 0, 0);
+            sb[u][r] = ok ? srow[r][(kc + kk) >> 5] : 0u;
+          }
+#pragma unroll
+        for (int u = 0; u < NSTEP; ++u) {
+          const int kk = k0 + u * 2048;
+          if (kk < klen) {
+            float p[ROWS][MM];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+              for (int m = 0; m < MM; ++m) p[r][m] = 0.f;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {  // 8 values at a time
+              uint32_t w[ROWS][4];
+#pragma unroll
+              for (int r = 0; r < ROWS; ++r) fp4x8_to_pk16<DT>(d == 0 ? qv[u][r].x : d == 1 ? qv[u][r].y : d == 2 ? qv[u][r].z : qv[u][r].w, w[r]);
+#pragma unroll
+              for (int m = 0; m < MM; ++m) {
+                uint4 xa;
+                if constexpr (LDSX || NORM) xa = *(const uint4*)(xs4 + m * xstride + kk + 8 * d);
+                else xa = *(const uint4*)(x + (int64_t)m * ldx + kc + kk + 8 * d);
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                  float a = p[r][m];
+                  a = dot2_acc<DT>(w[r][0], xa.x, a);
+                  a = dot2_acc<DT>(w[r][1], xa.y, a);
+                  a = dot2_acc<DT>(w[r][2], xa.z, a);
+                  a = dot2_acc<DT>(w[r][3], xa.w, a);
+                  p[r][m] = a;
+                }
+              }
+            }
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+              const float s = e8m0_to_f32(sb[u][r]);
+#pragma unroll
+              for (int m = 0; m < MM; ++m) acc[r][m] = fmaf(s, p[r][m], acc[r][m]);
+            }
+          }
+        }
+      }
+    }
+    if constexpr (!CHUNK) break;
+  }
+  if (n0 >= N) return;
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+    for (int m = 0; m < MM; ++m) acc[r][m] = wave_sum(acc[r][m]);
+  if constexpr (ROWS == 2) {
+    if (ra.tab) {
+      if (lane == 0) rope_append_store<DT, MM>(ra, n0 >> 1, acc[0], acc[1], (uint16_t*)out, ldo);
+      return;
+    }
+  }
+  if (lane == 0 && swi_ff > 0) {
+#pragma unroll
+    for (int r = 0; r < ROWS / 2; ++r) {
+      const int n = n0 + r;
+      if (n >= N) break;
+#pragma unroll
+      for (int m = 0; m < MM; ++m) {
+        const float g_ = ld16<DT>((uint16_t)st16<DT>(acc[r][m])), u_ = ld16<DT>((uint16_t)st16<DT>(acc[r + ROWS / 2][m]));
+        ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(swiglu_fwd1(g_, u_));
+      }
+    }
+    return;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const int n = n0 + r;
+      if (n >= N) break;
+#pragma unroll
+      for (int m = 0; m < MM; ++m) {
+        float v = acc[r][m];
+        if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
+        if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
+        else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
+      }
+    }
+  }
+}
+
+// 3..16 activation rows: gemv_mfma_k with fp4 weights.  A block owns 16 x RG weight rows, its 8 waves split K in steps of 128.  Lane
+// l = (row j = l & 15, kq = l >> 4) loads 16 B = ONE WHOLE scale block (block kq of the step) of its row, but an MFMA's four k-chunks
+// of a column come from the four lanes kq = 0..3 and its result cannot be scaled per chunk.  So the 4 x 4 (lane kq) x (dword) tile is
+// transposed in registers first (two v_permlane32_swap + two v_permlane16_swap per load): afterwards dword i of lane (j, kq) is dword
+// kq of block i, MFMA i multiplies block i alone (k in its natural order: the A operand is x[k + 32 i + 8 kq ..]) and its fp32 tile is
+// scaled by that block's 2^e - the semantics of the wave form, conversion with scale 1.  The step's four scale bytes of a row are one
+// dword load where the scale rows are dword-aligned (K % 128 == 0), four byte loads otherwise.  16 cvt + 4 swaps + 4 MFMA + 16 fma
+// per KB of weights.  RG, PAIR = 1 (SwiGLU partner rows) and the fixed-order reduction through LDS as in gemv_mfma_k.
+template <int DT, int RG, int PAIR>
+__global__ __launch_bounds__(512) void gemv_fp4w_mfma_k(const uint16_t* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ q,
+                                                        const uint8_t* __restrict__ sc, void* __restrict__ out, int64_t ldo,
+                                                        const uint16_t* __restrict__ resid, int64_t ldr, int M, int N, int K, int out_f32,
+                                                        int swi_ff, int sc_dwords) {
+  static_assert(PAIR == 0 || RG == 2, "the paired epilogue takes two row groups");
+  constexpr int NW = 8, NS = 4, KS = 128, KP = NW * NS * KS;
+  __shared__ __attribute__((aligned(16))) float red[NW * RG * 64 * 4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, kq = lane >> 4;
+  int n0 = blockIdx.x * 16 * RG, goff = 16, nlim = N;
+  if constexpr (PAIR == 1) { n0 = blockIdx.x * 16; goff = swi_ff; nlim = N + swi_ff; }
+  const bool arow = j < M;
+  const int nb = K >> 5;
+  f32x4_t acc[RG];
+  const uint8_t* wr[RG];
+  const uint8_t* sr[RG];
+#pragma unroll
+  for (int g = 0; g < RG; ++g) {
+    const int n = PAIR == 1 ? min(n0 + j, N - 1) + g * goff : min(n0 + goff * g + j, nlim - 1);
+    acc[g] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    wr[g] = q + (int64_t)n * (K >> 1) + kq * 16;
+    sr[g] = sc + (int64_t)n * nb;
+  }
+  const uint16_t* xr = x + (int64_t)min(j, M - 1) * ldx + kq * 8;
+  for (int kp = 0; kp < K; kp += KP) {
+    uint4 wv[RG][NS], xv[NS][4];
+    uint32_t sv[RG][NS];  // the step's four scale bytes, block i in byte i
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+      const int k = kp + (wave + NW * u) * KS;
+#pragma unroll
+      for (int g = 0; g < RG; ++g) {
+        wv[g][u] = (k + kq * 32 < K) ? ld_stream16(wr[g] + (k >> 1)) : make_uint4(0, 0, 0, 0);
+        uint32_t s4 = 0;
+        if (sc_dwords) {
+          if (k < K) s4 = *(const uint32_t*)(sr[g] + (k >> 5));
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (k + 32 * i < K) s4 |= (uint32_t)sr[g][(k >> 5) + i] << (8 * i);
+        }
+        sv[g][u] = s4;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xv[u][i] = (k + 32 * i < K && arow) ? *(const uint4*)(xr + k + 32 * i) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+      if (kp + (wave + NW * u) * KS >= K) break;
+#pragma unroll
+      for (int g = 0; g < RG; ++g) {
+        uint32_t d[4] = {wv[g][u].x, wv[g][u].y, wv[g][u].z, wv[g][u].w};
+        // transpose: lanes 32 apart exchange dwords (0, 2) and (1, 3), then lanes 16 apart (0, 1) and (2, 3)
+        auto t = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false); d[0] = t[0]; d[2] = t[1];
+        t = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false); d[1] = t[0]; d[3] = t[1];
+        t = __builtin_amdgcn_permlane16_swap(d[0], d[1], false, false); d[0] = t[0]; d[1] = t[1];
+        t = __builtin_amdgcn_permlane16_swap(d[2], d[3], false, false); d[2] = t[0]; d[3] = t[1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t bw[4];
+          fp4x8_to_pk16<DT>(d[i], bw);
+          const f32x4_t part = mfma16<DT>(xv[u][i], make_uint4(bw[0], bw[1], bw[2], bw[3]), f32x4_t{0.f, 0.f, 0.f, 0.f});
+          const float s = e8m0_to_f32((sv[g][u] >> (8 * i)) & 255u);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[g][c] = fmaf(s, part[c], acc[g][c]);
+        }
+      }
+    }
+  }
+  // D lane l reg r = D[m = 4 * (l >> 4) + r][n = l & 15]: sum the NW waves' tiles in wave order
+#pragma unroll
+  for (int g = 0; g < RG; ++g) *(f32x4_t*)(red + ((wave * RG + g) * 64 + lane) * 4) = acc[g];
+  __syncthreads();
+  if constexpr (PAIR == 1) {
+    if (wave == 0) {
+      f32x4_t s0 = *(const f32x4_t*)(red + lane * 4), s1 = *(const f32x4_t*)(red + (64 + lane) * 4);
+#pragma unroll 4
+      for (int w = 1; w < NW; ++w) {
+        const f32x4_t t0 = *(const f32x4_t*)(red + ((w * 2) * 64 + lane) * 4), t1 = *(const f32x4_t*)(red + ((w * 2 + 1) * 64 + lane) * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { s0[r] += t0[r]; s1[r] += t1[r]; }
+      }
+      uint16_t* o16 = (uint16_t*)out;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 4 * kq + r;
+        if (m >= M) continue;
+        const float lo = ld16<DT>((uint16_t)st16<DT>(s0[r])), hi = ld16<DT>((uint16_t)st16<DT>(s1[r]));  // the projection as it would be stored
+        if (n0 + j < N) o16[(int64_t)m * ldo + n0 + j] = (uint16_t)st16<DT>(swiglu_fwd1(lo, hi));
+      }
+    }
+    return;
+  }
+  if (wave < RG) {
+    const int g = wave;
+    f32x4_t s4 = *(const f32x4_t*)(red + (g * 64 + lane) * 4);
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+      const f32x4_t t = *(const f32x4_t*)(red + ((w * RG + g) * 64 + lane) * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s4[r] += t[r];
+    }
+    const int n = n0 + 16 * g + j;
+    if (n < N) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = 4 * kq + r;
+        if (m >= M) continue;
+        float v = s4[r];
+        if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
+        if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
+        else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
+      }
+    }
+  }
+}
+
+template <int DT>
+int launch_gemv_fp4w_mfma(const void* x, int64_t ldx, const void* q, const void* sc, void* out, int64_t ldo, const void* resid, int64_t ldr, int M,
+                          int N, int K, int out_f32, int swi_ff, hipStream_t st) {
+  const int scd = (K % 128 == 0 && (((uintptr_t)sc) & 3u) == 0) ? 1 : 0;
+#define MH_GM4(RG_, PAIR_, BLOCKS_)                                                                                                       \
+  hipLaunchKernelGGL((gemv_fp4w_mfma_k<DT, RG_, PAIR_>), dim3(BLOCKS_), dim3(512), 0, st, (const uint16_t*)x, ldx, (const uint8_t*)q,     \
+                     (const uint8_t*)sc, out, ldo, (const uint16_t*)resid, ldr, M, N, K, out_f32, swi_ff, scd)
+  if (swi_ff) MH_GM4(2, 1, (N + 15) / 16);  // N = ff outputs
+  else if (N >= 30000) MH_GM4(4, 0, (N + 63) / 64);  // (rows per block by N: the thresholds of launch_gemv_mfma)
+  else if (N >= 12000) MH_GM4(2, 0, (N + 31) / 32);
+  else MH_GM4(1, 0, (N + 15) / 16);
+#undef MH_GM4
+  MH_LAUNCH_CHECK();
+}
+
+}  // namespace
+
+extern "C" int mh_quant_fp4_b32(const void* w, int64_t ldw, void* q, void* scales, int N, int K, int dt, void* stream) {
+  if (!w || !q || !scales || N <= 0 || K <= 0 || (K & 31) || (ldw & 7) || !aligned16(w) || (((uintptr_t)q) & 3u)) return MH_ERR_ARG;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int64_t blocks = (int64_t)N * (K >> 5);
+  const dim3 grid((unsigned)((blocks + 63) / 64)), block(256);
+  if (dt == MH_BF16)
+    hipLaunchKernelGGL(quant_fp4_b32_k<MH_BF16>, grid, block, 0, as_stream(stream), (const uint16_t*)w, ldw, (uint8_t*)q, (uint8_t*)scales, N, K);
+  else
+    hipLaunchKernelGGL(quant_fp4_b32_k<MH_F16>, grid, block, 0, as_stream(stream), (const uint16_t*)w, ldw, (uint8_t*)q, (uint8_t*)scales, N, K);
+  MH_LAUNCH_CHECK();
+}
+
+// Row thresholds of the MFMA form (g_gemv_mfma_min_rows_fp4 / g_gemv_mfma_pair_min_fp4): 3 rows for a plain projection and 4 for the
+// SwiGLU pair, the fp8 path's values.  Measured at Llama-7B size (profiles/decode_fp4_bench.txt, graph replay, context 613): with these
+// thresholds the fp4 step is 1.78 ms at 1 row (fp8 1.97), 3.01 ms at 5 rows (fp8 3.57) and 3.53 ms at 8 rows (fp8 3.79); the same
+// file holds the 3- and 5-row steps with the MFMA form switched off (mh_gemv_mfma_min_rows(17)).  The weights stream at ~2 TB/s at one
+// row, well below the 16-bit path's 4.7: per byte the wave form issues twice the fp8 form's converts and dot2s, and a 2 KB row is two
+// loads per lane - the step is faster than fp8 but not yet at the byte ratio.
+static int gemv_fp4w_impl(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid,
+                          int64_t ldr, int M, int N, int K, int dt, int out_f32, int swi_ff, const void* norm_w, float eps, const RopeAppend& ra,
+                          void* stream) {
+  if (!x || !q || !scales || !out || M <= 0 || M > 16 || N <= 0 || K <= 0 || (K & 31) || (ldx & 7)) return MH_ERR_ARG;
+  if (!aligned16(x) || !aligned16(q)) return MH_ERR_ARG;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  if (norm_w && (M > 8 || K > 8192 || !aligned16(norm_w))) return MH_ERR_ARG;
+  if (ra.tab && (swi_ff || (N & 1) || M > 8)) return MH_ERR_ARG;
+  if ((swi_ff || ra.tab) && (resid || out_f32)) return MH_ERR_ARG;
+  if (!norm_w && !ra.tab && M >= (swi_ff ? g_gemv_mfma_pair_min_fp4 : g_gemv_mfma_min_rows_fp4) && (K % 64) == 0) {
+    if (dt == MH_BF16) return launch_gemv_fp4w_mfma<MH_BF16>(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, as_stream(stream));
+    return launch_gemv_fp4w_mfma<MH_F16>(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, as_stream(stream));
+  }
+  if (M > 8 || ((swi_ff || ra.tab) && K > 8192)) return MH_ERR_ARG;
+  const int rows = (swi_ff || ra.tab) ? 2 : (M < 3 ? 1 : (N >= 8192 ? 2 : 1));  // weight rows per wave, as in gemv_fp8w_impl; SwiGLU / RoPE: one pair
+  const int cols = swi_ff ? rows / 2 : rows;
+  const dim3 grid((N + 4 * cols - 1) / (4 * cols)), block(256);
+  hipStream_t st = as_stream(stream);
+#define GO1(DT_, MM_, R_, L_, NRM_, LDS_)                                                                                           \
+  do {                                                                                                                              \
+    const size_t lds_ = (LDS_);                                                                                                     \
+    static bool attr_ = false;                                                                                                      \
+    if (lds_ && !attr_) {                                                                                                           \
+      hipFuncSetAttribute((const void*)gemv_fp4w_k<DT_, MM_, R_, L_, NRM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MM_ * 8192 * 2)); \
+      attr_ = true;                                                                                                                 \
+    }                                                                                                                               \
+    hipLaunchKernelGGL((gemv_fp4w_k<DT_, MM_, R_, L_, NRM_>), grid, block, lds_, st, (const uint16_t*)x, ldx, (const uint8_t*)q,     \
+                       (const uint8_t*)scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32, swi_ff, (const uint16_t*)norm_w, eps, ra); \
+  } while (0)
+#define GO(DT_, MM_, R_, L_)                                                                                                       \
+  do {                                                                                                                              \
+    if (norm_w) GO1(DT_, MM_, R_, true, true, (size_t)MM_ * K * 2);                                                                 \
+    else GO1(DT_, MM_, R_, L_, false, L_ ? (size_t)MM_ * GEMV_KC * 2 : 0);                                                          \
+  } while (0)
+#define GOR(DT_, MM_)                                                                        \
+  do {                                                                                       \
+    if (rows == 2) GO(DT_, MM_, 2, true); else GO(DT_, MM_, 1, true);                       \
+  } while (0)
+#define GOS(DT_, MM_)                                                                        \
+  do {                                                                                       \
+    if (rows == 2) GO(DT_, MM_, 2, false); else GO(DT_, MM_, 1, false);                     \
+  } while (0)
+#define GOM(DT_)                                                                                                   \
+  switch (M) {                                                                                                     \
+    case 1: GOS(DT_, 1); break; case 2: GOS(DT_, 2); break; case 3: GOR(DT_, 3); break;                           \
+    case 4: GOR(DT_, 4); break; case 5: GOR(DT_, 5); break; case 6: GOR(DT_, 6); break;                           \
+    case 7: GOR(DT_, 7); break; default: GOR(DT_, 8); break;                                                       \
+  }
+  if (dt == MH_BF16) { GOM(MH_BF16); } else { GOM(MH_F16); }
+#undef GOM
+#undef GOS
+#undef GOR
+#undef GO
+#undef GO1
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_gemv_fp4w(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid,
+                            int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream) {
+  return gemv_fp4w_impl(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream);
+}
+// mh_gemv_fp8w_norm with fp4 weights: out = rmsnorm(x; norm_w, eps) W^T (norm_w may be NULL: no norm), ff > 0: SwiGLU of the gate|up rows.
+// With norm_w: M <= 8, K <= 8192; without: M <= 16.
+extern "C" int mh_gemv_fp4w_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* out,
+                                 int64_t ldo, int M, int N, int K, int ff, int dt, void* stream) {
+  if (ff < 0) return MH_ERR_ARG;
+  return gemv_fp4w_impl(x, ldx, q, scales, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream);
+}
+// mh_gemv_qkv_rope with fp4 weights (= mh_rmsnorm_fwd + mh_gemv_fp4w + mh_decode_rope_append, bit for bit): one wave per rotary pair, M <= 8.
+extern "C" int mh_gemv_fp4w_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* qkv,
+                                     int64_t ldo, int M, int K, int dt, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos,
+                                     void* kcache, void* vcache, int H, int D, int Smax, void* stream) {
+  if (!cos_sin || !pos || !kcache || !vcache || H <= 0 || D <= 0 || (D & 1) || Smax <= 0 || M > 8) return MH_ERR_ARG;
+  RopeAppend ra;
+  ra.tab = (const float2*)cos_sin; ra.pos = pos; ra.rpos = rope_pos ? rope_pos : pos; ra.kc = (uint16_t*)kcache; ra.vc = (uint16_t*)vcache; ra.H = H; ra.D = D; ra.Smax = Smax;
+  return gemv_fp4w_impl(x, ldx, q, scales, qkv, ldo, nullptr, 0, M, 3 * H * D, K, dt, 0, 0, norm_w, eps, ra, stream);
 }

@@ -106,18 +106,26 @@ def _resolve_options(generation_config, kw):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, fp8_kv=False, seed=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, seed=None, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
     fp8_kv=True stores the KV cache as e4m3 bytes with one power-of-two scale per (sequence, head, token) (engine.KVCache fp8=True):
-    about half the cache bytes in every mode (greedy, sampling, beam search; with or without use_graph and fp8_weights)."""
+    about half the cache bytes in every mode (greedy, sampling, beam search; with or without use_graph and fp8_weights / fp4_weights).
+    fp4_weights=True runs the decode-step projections on MXFP4 copies of the decoder's Linear weights and lm_head (OCP e2m1 values, one
+    power-of-two scale per 32 k, engine.quantize_decode_weights_fp4: about 0.53 bytes per weight streamed per token instead of 2; the
+    prompt's prefill keeps the 16-bit weights), in every mode and with either cache format; the alternative to fp8_weights, not an
+    addition to it, and it needs use_cache=True (it applies to the decode step)."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
     num_beams, length_penalty, early_stopping, use_cache = o["num_beams"], o["length_penalty"], o["early_stopping"], o["use_cache"]
     if fp8_kv and not use_cache:
         raise ValueError("fp8_kv=True stores the KV cache in fp8: it needs use_cache=True")
+    if fp4_weights and fp8_weights:
+        raise ValueError("fp4_weights and fp8_weights are alternatives: pick one weight format for the decode step")
+    if fp4_weights and not use_cache:
+        raise ValueError("fp4_weights=True applies to the KV-cache decode step: it needs use_cache=True")
     cfg = model.config
     eos_ids = _as_list(cfg.eos_token_id if eos_token_id is None else eos_token_id)
     pad = pad_token_id if pad_token_id is not None else (cfg.pad_token_id if cfg.pad_token_id is not None else (eos_ids[0] if eos_ids else 0))
@@ -135,14 +143,14 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise ValueError("`streamer` cannot be used with beam search. Make sure that `num_beams` is set to 1.")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
-        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv)
+        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights)
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
     if streamer is not None:
         streamer.put(input_ids.cpu())
     if not use_cache:
         out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer)
     else:
-        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer)
+        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights)
     if streamer is not None:
         streamer.end()
     return out
@@ -175,7 +183,7 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
             return ids
 
 
-def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None):
+def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False):
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
@@ -184,7 +192,7 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
     dev = logits.device
     graph = None
     if use_graph and logits.is_cuda and max_new > 2:
-        graph, g_tok, g_logits = eng.capture_decode_graph(cache, fp8=fp8_weights)  # the decode step as one replayable HIP graph
+        graph, g_tok, g_logits = eng.capture_decode_graph(cache, fp8=fp8_weights, fp4=fp4_weights)  # the decode step as one replayable HIP graph
     am = attention_mask.to(dev).to(torch.bool) if attention_mask is not None else None
     # right-padded prompts (ones then zeros; an extension - HF wants left padding): each row continues from its own length.
     # Anything else (HF's left padding, holes) follows transformers: new tokens are appended after the padded prompt, keys are the
@@ -212,7 +220,7 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
             graph.replay()
             logits = g_logits
         else:
-            logits = eng.decode_step(nxt, cache, fp8=fp8_weights)
+            logits = eng.decode_step(nxt, cache, fp8=fp8_weights, fp4=fp4_weights)
     if padded:  # right-padded prompts (an extension; HF wants left padding): each row's continuation starts at its own length
         cur = _compact(ids, lens, torch.stack(new, dim=1), pad)
     return cur.to(input_ids.device)
@@ -235,7 +243,7 @@ def _gather_beams(t, idx):
     return torch.gather(t, 1, idx.expand(-1, -1, *t.shape[2:]))
 
 
-def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False):
+def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
@@ -304,6 +312,6 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
         if not go_on:
             break
         eng.reorder_cache(cache, beam_idx, cur - 1)
-        logits = eng.decode_step(running[:, :, cur - 1].reshape(-1).contiguous(), cache, fp8=fp8_weights)
+        logits = eng.decode_step(running[:, :, cur - 1].reshape(-1).contiguous(), cache, fp8=fp8_weights, fp4=fp4_weights)
     out_len = P + int(seq_len[:, 0].max())
     return sequences[:, 0, :out_len].to(input_ids.device)

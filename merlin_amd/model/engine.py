@@ -199,7 +199,7 @@ class HipEngine:
         """Parameter values changed (optimizer step, checkpoint load, init, repack): drop every derived copy."""
         self.weight_version += 1
         self._derived = {}
-        self._fp8 = self._fp8_fwd = None
+        self._fp8 = self._fp8_fwd = self._fp4 = None
 
     def _derive(self, key, make):
         hit = self._derived.get(key)
@@ -1328,16 +1328,37 @@ class HipEngine:
         self._fp8 = dict(layers=q, lm_head=O.quant_fp8_b128(self._lm_head_w()[:self.model.config.vocab_size]))
         return self._fp8
 
-    def decode_step(self, tokens, cache, fp8=False):
+    def quantize_decode_weights_fp4(self):
+        """MXFP4 (OCP e2m1, one power-of-two scale per 32 k: ops.quant_fp4_b32) copies of the decoder's Linear weights and of lm_head's
+        vocab_size rows for the decode step (activations stay 16-bit).  ~0.53 bytes per weight.  weights_changed() drops them."""
+        cfg = self.model.config
+        for name in ("hidden_size", "intermediate_size"):
+            if getattr(cfg, name) % 32:
+                raise ValueError(f"fp4 decode weights need {name} = {getattr(cfg, name)} to be a multiple of the 32-element scale block")
+        self.ensure_arena()
+        q = []
+        for W in self.llama:
+            q.append(dict(wqkv=O.quant_fp4_b32(W.wqkv), wo=O.quant_fp4_b32(W.wo), wgu=O.quant_fp4_b32(W.wgu), wd=O.quant_fp4_b32(W.wd)))
+        self._fp4 = dict(layers=q, lm_head=O.quant_fp4_b32(self._lm_head_w()[:cfg.vocab_size]))
+        return self._fp4
+
+    def decode_step(self, tokens, cache, fp8=False, fp4=False):
         """One new token per sequence (tokens int64 [B]) at position cache.lens[b]; returns logits fp32 [B, V] and
         advances the cache.  Every op is an HBM-bound kernel: weights and cache are streamed exactly once.
-        fp8=True uses the fp8 weight copies of quantize_decode_weights().  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its
-        own kernels (mh_decode_rope_append_kv8, mh_attn_decode_kv8), with either weight format."""
+        fp8=True uses the fp8 weight copies of quantize_decode_weights(), fp4=True the MXFP4 copies of quantize_decode_weights_fp4()
+        (one of the two).  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its own kernels (mh_decode_rope_append_kv8,
+        mh_attn_decode_kv8), with any weight format."""
+        if fp8 and fp4:
+            raise ValueError("decode_step: fp8 and fp4 weights are alternatives, not a combination")
         cfg = self.model.config
         A = self.arena
         d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
         eps = cfg.rms_norm_eps
-        if fp8:
+        if fp4:
+            F4 = getattr(self, "_fp4", None) or self.quantize_decode_weights_fp4()
+            gemv, gemv_norm, head = O.gemv_fp4w, O.gemv_fp4w_norm, F4["lm_head"]
+            layers = [(Q["wqkv"], Q["wo"], Q["wgu"], Q["wd"]) for Q in F4["layers"]]
+        elif fp8:
             F8 = getattr(self, "_fp8", None) or self.quantize_decode_weights()
             gemv, gemv_norm, head = O.gemv_fp8w, O.gemv_fp8w_norm, F8["lm_head"]
             layers = [(Q["wqkv"], Q["wo"], Q["wgu"], Q["wd"]) for Q in F8["layers"]]
@@ -1368,7 +1389,7 @@ class HipEngine:
             cache.rpos.add_(1)
         return logits
 
-    def capture_decode_graph(self, cache, fp8=False):
+    def capture_decode_graph(self, cache, fp8=False, fp4=False):
         """Capture one decode step (≈300 launches) into a HIP graph bound to `cache`: returns (graph, token buffer int64 [B],
         logits buffer fp32 [B, V]).  Positions live in cache.lens on the device and advance inside the graph, so every
         replay is the next token.  One eager warm-up step runs first (function attributes, symbol look-ups and allocator
@@ -1380,14 +1401,14 @@ class HipEngine:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            self.decode_step(tok, cache, fp8=fp8)
+            self.decode_step(tok, cache, fp8=fp8, fp4=fp4)
         torch.cuda.current_stream(dev).wait_stream(side)
         cache.lens.copy_(keep)
         if keep_r is not None:
             cache.rpos.copy_(keep_r)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            logits = self.decode_step(tok, cache, fp8=fp8)
+            logits = self.decode_step(tok, cache, fp8=fp8, fp4=fp4)
         cache.lens.copy_(keep)  # capture does not execute, but keep the invariant explicit
         if keep_r is not None:
             cache.rpos.copy_(keep_r)

@@ -246,11 +246,85 @@ def gemv_fp8w_norm(x, norm_w, eps, qw, swiglu=False, out=None):
     return out
 
 
+def is_fp4_pair(w):
+    """True for the (q, scales) pair of quant_fp4_b32 (E8M0 scale bytes); the pair of quant_fp8_b128 carries fp32 scales."""
+    return isinstance(w, (tuple, list)) and w[1].dtype == torch.uint8
+
+
+def quant_fp4_b32(w):
+    """w [N, K] (16-bit, K % 32 == 0) -> (q uint8 [N, K/2]: OCP MX e2m1 codes, element 2j in the low nibble of byte j; scales uint8
+    [N, K/32]: E8M0 exponents e + 127, one per 32 consecutive k)."""
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"quant_fp4_b32: K = {K} is not a multiple of the 32-element scale block")
+    q = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    sc = torch.empty(N, K // 32, dtype=torch.uint8, device=w.device)
+    L.call("mh_quant_fp4_b32", w, _rowmajor(w), q, sc, N, K, dt_of(w), _stream())
+    return q, sc
+
+
+def _gemv_fp4_rows_per_launch(K):
+    """Activation rows one mh_gemv_fp4w launch takes: 16 through the MFMA form (K % 64 == 0), 8 through the wave-per-row form."""
+    return 16 if (K % 64 == 0 and _gemv_mfma_min <= 9) else 8
+
+
+def gemv_fp4w(x, qw, out=None, resid=None, out_f32=False, n=None):
+    """out[M, N] = x[M, K] @ dequant(q, scales)^T (+ resid); qw = (q, scales) from quant_fp4_b32."""
+    q, sc = qw
+    M, K = x.shape
+    N = q.shape[0] if n is None else n
+    assert q.shape[1] * 2 == K and sc.dtype == torch.uint8
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    step = _gemv_fp4_rows_per_launch(K)
+    for m0 in range(0, M, step):
+        mm = min(step, M - m0)
+        xs, os_ = x[m0:m0 + mm], out[m0:m0 + mm]
+        rs = resid[m0:m0 + mm] if resid is not None else None
+        L.call("mh_gemv_fp4w", xs, _rowmajor(xs), q, sc, os_, _rowmajor(os_), rs, _rowmajor(rs) if rs is not None else 0, mm, N, K, dt_of(x),
+               int(out.dtype == torch.float32), _stream())
+    return out
+
+
+def gemv_fp4w_norm(x, norm_w, eps, qw, swiglu=False, out=None):
+    """gemv_norm with MXFP4 weights (qw = (q, scales) from quant_fp4_b32).  1-2 rows: norm, projection (and SwiGLU) in one launch;
+    3-16 rows: separate norm, SwiGLU still fused; more rows: separate launches."""
+    q, sc = qw
+    M, K = x.shape
+    N = q.shape[0]
+    ff = N // 2 if swiglu else 0
+    if not _gemv_fused_rows_ok(M, K) or K > 8192:
+        y = gemv_fp4w(rmsnorm_fwd(x, norm_w, eps), qw)
+        return swiglu_fwd(y, out=out) if swiglu else y
+    fuse_norm = M <= FUSED_NORM_MAX_ROWS
+    if not fuse_norm:
+        x = rmsnorm_fwd(x, norm_w, eps)
+        if not swiglu:
+            return gemv_fp4w(x, qw, out=out)
+    assert q.shape[1] * 2 == K and x.is_contiguous()
+    out = torch.empty(M, ff if swiglu else N, dtype=x.dtype, device=x.device) if out is None else out
+    L.call("mh_gemv_fp4w_norm", x, _rowmajor(x), norm_w if fuse_norm else None, eps, q, sc, out, _rowmajor(out), M, N, K, ff, dt_of(x), _stream())
+    return out
+
+
 def gemv_qkv_rope(x, norm_w, eps, w, table, pos, kcache, vcache, H, D, rope_pos=None):
-    """Decode-step q|k|v: (input_layernorm +) projection + RoPE at pos + K/V append in one launch; w = 16-bit weight [3HD, K] or the
-    (q, scales) pair of quant_fp8_b128.  Returns qkv [M, 3HD] (q, k rotated).  More than 16 rows: the separate launches."""
+    """Decode-step q|k|v: (input_layernorm +) projection + RoPE at pos + K/V append in one launch; w = 16-bit weight [3HD, K], the
+    (q, scales) pair of quant_fp8_b128 or that of quant_fp4_b32 (one launch up to 8 rows).  Returns qkv [M, 3HD] (q, k rotated).
+    More than 16 rows: the separate launches."""
     M, K = x.shape
     fp8 = isinstance(w, (tuple, list))
+    if is_fp4_pair(w):
+        if M > 8 or K > 8192:
+            qkv = gemv_fp4w(rmsnorm_fwd(x, norm_w, eps), w)
+            decode_rope_append(qkv, table, pos, kcache, vcache, H, D, rope_pos=rope_pos)
+            return qkv
+        if M > FUSED_NORM_MAX_ROWS:
+            x, norm_w = rmsnorm_fwd(x, norm_w, eps), None
+        assert x.is_contiguous() and pos.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
+        qkv = torch.empty(M, 3 * H * D, dtype=x.dtype, device=x.device)
+        L.call("mh_gemv_fp4w_qkv_rope", x, _rowmajor(x), norm_w, eps, w[0], w[1], qkv, _rowmajor(qkv), M, K, dt_of(x), table, pos, rope_pos,
+               kcache, vcache, H, D, kcache.shape[1], _stream())
+        return qkv
     if not _gemv_fused_rows_ok(M, K) or K > 8192 or (M > 8 and (D // 2) % 16):
         h = rmsnorm_fwd(x, norm_w, eps)
         qkv = gemv_fp8w(h, w) if fp8 else gemv(h, w)
@@ -1141,7 +1215,7 @@ _gemv_mfma_min = 3
 
 
 def gemv_mfma_min_rows(rows: int):
-    """A/B switch: row count from which gemv / gemv_fp8w use the MFMA kernel (<= 0 restores the measured default, 3; 17 = never)."""
+    """A/B switch: row count from which gemv / gemv_fp8w / gemv_fp4w use the MFMA kernel (<= 0 restores the measured default, 3; 17 = never)."""
     global _gemv_mfma_min
     _gemv_mfma_min = rows if rows > 0 else 3
     L.lib().mh_gemv_mfma_min_rows(rows)

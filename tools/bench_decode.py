@@ -1,6 +1,7 @@
 """Decode-step timing of the KV-cache path at Llama-7B size (run on the GPU box): prefill a cfg-3 style prompt, then time
 decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token and the HBM rate the step sustains
-(weights + K/V cache streamed once per step).
+(weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
+byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
     python tools/bench_decode.py [B] [context] [--kv fp8]
 
@@ -99,7 +100,8 @@ with torch.no_grad():
     e1.record(); torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / n
     print(json.dumps({"decode": "hip-graph", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
-                      "hbm_gb_per_step": round((wbytes + cbytes) / 1e9, 2), "hbm_tb_s": round((wbytes + cbytes) / ms / 1e9, 2)}), flush=True)
+                      "hbm_gb_per_step": round((wbytes + cbytes) / 1e9, 2), "hbm_tb_s": round((wbytes + cbytes) / ms / 1e9, 2),
+                      "weights_tb_s": round(wbytes / ms / 1e9, 2)}), flush=True)
     # fp8 weights (e4m3, per-128-block scales), graph replay
     model.engine.quantize_decode_weights()
     g8, gtok8, glog8 = model.engine.capture_decode_graph(cache, fp8=True)
@@ -114,4 +116,22 @@ with torch.no_grad():
     ms = e0.elapsed_time(e1) / n
     w8 = wbytes // 2 + wbytes // 2 // 64  # fp8 bytes + fp32 scales (1 per 128)
     print(json.dumps({"decode": "hip-graph fp8 weights", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
-                      "hbm_gb_per_step": round((w8 + cbytes) / 1e9, 2), "hbm_tb_s": round((w8 + cbytes) / ms / 1e9, 2)}), flush=True)
+                      "hbm_gb_per_step": round((w8 + cbytes) / 1e9, 2), "hbm_tb_s": round((w8 + cbytes) / ms / 1e9, 2),
+                      "weights_tb_s": round(w8 / ms / 1e9, 2)}), flush=True)
+    del g8
+    # MXFP4 weights (e2m1 values, one power-of-two scale byte per 32 k), graph replay
+    model.engine.quantize_decode_weights_fp4()
+    g4, gtok4, glog4 = model.engine.capture_decode_graph(cache, fp4=True)
+    gtok4.copy_(tok)
+    for _ in range(3):
+        g4.replay(); gtok4.copy_(glog4.argmax(-1))
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        g4.replay(); gtok4.copy_(glog4.argmax(-1))
+    e1.record(); torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / n
+    w4 = wbytes // 4 + wbytes // 2 // 32  # half a byte per weight + one scale byte per 32
+    print(json.dumps({"decode": "hip-graph fp4 weights", "kv": KV, "B": B, "context": S, "ms_per_step": round(ms, 3), "tokens_per_s": round(B * 1e3 / ms, 1),
+                      "hbm_gb_per_step": round((w4 + cbytes) / 1e9, 2), "hbm_tb_s": round((w4 + cbytes) / ms / 1e9, 2),
+                      "weights_tb_s": round(w4 / ms / 1e9, 2)}), flush=True)
