@@ -388,6 +388,35 @@ int mh_decode_rope_append_kv8(void* qkv, const float* cos_sin, const int32_t* po
                               float* vscale, int B, int H, int D, int Smax, int dt, void* stream);
 int mh_attn_decode_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                        const int32_t* lens, int B, int H, int D, int Smax, float* ws, int dt, void* stream);
+/* ---- T new tokens per sequence in one decode step, 1 <= T <= 16: the verify step of prompt-lookup speculative decoding
+ * (transformers generate(prompt_lookup_num_tokens=k): k drafted tokens are checked by one forward over k + 1 positions).  Rows are
+ * m = b*T + t throughout; the projections take the B*T rows through mh_gemv* as they are.
+ * mh_decode_rope_append_multi / _kv8: qkv [B*T, 3, H, D]; row m is rotated in place at rotary position rope_pos[b] + t (NULL = pos) and
+ *   its k, v are written to cache row pos[b] + t of sequence b (the fp8 form quantises with the rule above and writes kscale / vscale
+ *   [b, h, pos[b] + t]).  Equal, bit for bit, to T calls of mh_decode_rope_append / _kv8 at pos + t.  A row with pos[b] + t >= Smax is
+ *   left untouched (not rotated, not written).
+ * mh_attn_decode_multi / _kv8: q rows m (row stride ldq, 16-byte aligned), out [B*T, H*D]; query (b, t) attends keys
+ *   [0, min(lens[b] + t, Smax)) - lens[b] is what query 0 sees, its own key included.  One block per (b, h, key split) loads every key and
+ *   value row once for all T queries (scores on the matrix pipe, fp32 softmax per query, fp32 p.V).  ws != NULL: B*T*H*splits*(D+2)
+ *   floats with splits = mh_attn_decode_multi_splits(B, T, H, Smax) - the one-query plan, then more splits until the T x chunk fp32
+ *   scores of a block fit 64 KiB of LDS, 32 splits at the most (the merge kernel's limit; MH_ERR_SHAPE where 32 splits still leave more than
+ *   150 KiB of scores per block: Smax above 76 800 keys at T > 8, 153 600 at T > 4) - merged by a second launch (no ticket counters).  ws == NULL: one block per (b, h);
+ *   MH_ERR_SHAPE where its T' x Smax scores (T' = T rounded up to 4, 8 or 16) exceed the 150 KiB the one-query kernels may request. */
+int mh_decode_rope_append_multi(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kcache, void* vcache,
+                                int B, int T, int H, int D, int Smax, int dt, void* stream);
+int mh_decode_rope_append_multi_kv8(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* k8, void* v8,
+                                    float* kscale, float* vscale, int B, int T, int H, int D, int Smax, int dt, void* stream);
+int mh_attn_decode_multi_splits(int B, int T, int H, int Smax);
+int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens, int B, int T,
+                         int H, int D, int Smax, float* ws, int dt, void* stream);
+int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                             const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream);
+/* Prompt-lookup drafter (transformers PromptLookupCandidateGenerator.get_candidates without a logits processor): ids int64 [rows, ld],
+ * the first `len` of every row valid.  For n = min(max_ngram, len - 1) down to 1: the EARLIEST window equal to the last n tokens whose
+ * continuation ids[start : min(start + k, len, max_length)] is not empty; the first n that yields one wins.  out int64 [rows, k] gets
+ * the continuation, out_count int32 [rows] its length - 0 when there is none, or when max_length == len + 1 (one token left). */
+int mh_ngram_draft(const int64_t* ids, int64_t ld, int rows, int len, int max_ngram, int k, int max_length, int64_t* out, int32_t* out_count,
+                   void* stream);
 
 /* ---- token selection for generate() (HF GenerationMixin as the reference's eval scripts drive it: eval_mmvet.py:101-120
  * `do_sample=True, temperature=0.2` or `num_beams=5`; site-packages transformers/generation/logits_process.py) ------------

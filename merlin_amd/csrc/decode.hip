@@ -20,6 +20,9 @@
 //                       per (sequence, head, token)): prefill quantiser, RoPE + quantised append, attention reading half the bytes per key.
 //   mh_quant_fp4_b32 / mh_gemv_fp4w / mh_gemv_fp4w_norm / mh_gemv_fp4w_qkv_rope   the projections on MXFP4 weights (e2m1 values, two per byte, one
 //                       power-of-two scale byte per 32 k: 0.53 bytes per weight, 3.6 GB per token at 7B) - at the end of this file.
+//   mh_decode_rope_append_multi / mh_attn_decode_multi (+ _kv8) / mh_ngram_draft   T <= 16 new tokens of one sequence in one step (the verify
+//                       step of prompt-lookup decoding): append at T consecutive positions, attention with every key / value row loaded once
+//                       for all T queries (scores on the matrix pipe, causality inside the block), and the device-side drafter.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include "mh_common.h"
 
@@ -838,22 +841,16 @@ __device__ __forceinline__ void kv8_store_pair(const uint4& plo, const uint4& ph
 // qkv [B, 3, H, D] of the new tokens; tab [max_pos, D/2] (cos, sin); kc, vc [B, Smax, H*D]
 // KV8: kc_, vc_ are e4m3 bytes and ks, vs [B, H, Smax] receive the group scales (fp8 KV cache, above): q, k are rotated exactly as in the
 // 16-bit form, then the ROUNDED 16-bit k row and the v row as it lies in qkv are quantised; a head is D/16 neighbouring lanes (D 64 or 128).
+// One lane's share (the 8-channel pieces v of the two halves of head h) of qkv row m of sequence b: rotary position rp, cache row p.  The ONE
+// definition of the rotate / quantise / store sequence, shared by the one-token kernel and the T-token kernel.
 template <int DT, bool KV8>
-__global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv, const float2* __restrict__ tab,
-                                                     const int32_t* __restrict__ pos, const int32_t* __restrict__ rpos,
-                                                     void* __restrict__ kc_, void* __restrict__ vc_, float* __restrict__ ks,
-                                                     float* __restrict__ vs, int B, int H, int D, int Smax) {
+__device__ __forceinline__ void rope_append_lane(uint16_t* __restrict__ qkv, const float2* __restrict__ tab, void* __restrict__ kc_,
+                                                 void* __restrict__ vc_, float* __restrict__ ks, float* __restrict__ vs, int m, int b, int h,
+                                                 int v, int p, int rp, int H, int D, int Smax) {
   const int half = D >> 1, vph = half >> 3;
-  const int64_t total = (int64_t)B * H * vph;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int v = (int)(i % vph);
-  const int h = (int)((i / vph) % H);
-  const int b = (int)(i / ((int64_t)vph * H));
-  const int p = pos[b];
-  const float2* tb = tab + (int64_t)rpos[b] * half + v * 8;
+  const float2* tb = tab + (int64_t)rp * half + v * 8;
   const int64_t hd = (int64_t)h * D + v * 8;
-  uint16_t* qb = qkv + (int64_t)b * 3 * H * D + hd;
+  uint16_t* qb = qkv + (int64_t)m * 3 * H * D + hd;
   uint16_t* kb = qb + (int64_t)H * D;
   const uint16_t* vb = kb + (int64_t)H * D;
   const int64_t cdst = ((int64_t)b * Smax + p) * H * D + hd, sdst = ((int64_t)b * H + h) * Smax + p;  // cache element, scale (KV8)
@@ -886,6 +883,21 @@ __global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv,
     *(uint4*)vdst = *(const uint4*)vb;
     *(uint4*)(vdst + half) = *(const uint4*)(vb + half);
   }
+}
+
+template <int DT, bool KV8>
+__global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv, const float2* __restrict__ tab,
+                                                     const int32_t* __restrict__ pos, const int32_t* __restrict__ rpos,
+                                                     void* __restrict__ kc_, void* __restrict__ vc_, float* __restrict__ ks,
+                                                     float* __restrict__ vs, int B, int H, int D, int Smax) {
+  const int vph = D >> 4;
+  const int64_t total = (int64_t)B * H * vph;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int v = (int)(i % vph);
+  const int h = (int)((i / vph) % H);
+  const int b = (int)(i / ((int64_t)vph * H));
+  rope_append_lane<DT, KV8>(qkv, tab, kc_, vc_, ks, vs, b, b, h, v, pos[b], rpos[b], H, D, Smax);
 }
 
 __device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1185,6 +1197,265 @@ __global__ __launch_bounds__(D) void attn_decode_combine_k(const float* __restri
   out[(int64_t)bh * D + tid] = (uint16_t)st16<DT>(den > 0.f ? num / den : 0.f);
 }
 
+// ---- T new tokens per sequence in one step (prompt-lookup verify step of generate()): qkv rows m = b*T + t ----------------------------
+// rope_append_k over T consecutive positions: row m is rotated at rpos[b] + t and appended at cache row pos[b] + t by the same
+// rope_append_lane; rows whose cache row would lie at or beyond Smax are left untouched.
+template <int DT, bool KV8>
+__global__ __launch_bounds__(256) void rope_append_multi_k(uint16_t* __restrict__ qkv, const float2* __restrict__ tab,
+                                                           const int32_t* __restrict__ pos, const int32_t* __restrict__ rpos,
+                                                           void* __restrict__ kc_, void* __restrict__ vc_, float* __restrict__ ks,
+                                                           float* __restrict__ vs, int B, int T, int H, int D, int Smax) {
+  const int half = D >> 1, vph = half >> 3;
+  const int64_t total = (int64_t)B * T * H * vph;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int v = (int)(i % vph);
+  const int h = (int)((i / vph) % H);
+  const int m = (int)(i / ((int64_t)vph * H));
+  const int b = m / T, t = m - b * T;
+  const int p = pos[b] + t;
+  if (p >= Smax || p < 0) return;  // (the vph lanes of a head leave together: kv8_store_pair's shuffles stay inside the head)
+  rope_append_lane<DT, KV8>(qkv, tab, kc_, vc_, ks, vs, m, b, h, v, p, rpos[b] + t, H, D, Smax);
+}
+
+// Decode attention for T <= TQ queries of one (sequence, head): q rows m = b*T + t, query t sees keys [0, min(lens[b] + t, Smax)).
+// Block per (b, h, key split), the structure of attn_decode_k with every key and value row loaded ONCE for all the queries:
+//   pass 1  S = K Q^T on the matrix pipe: a wave takes 16 keys per MFMA tile, a lane loads 16 B (fp8 cache: 8 B, converted exactly to the
+//           16-bit type) of one key row straight into the A operand, the TQ query rows are the B operand (registers, loaded once), and the
+//           16 x 16 fp32 tile lands as lane (key 4*(l>>4) + r, query l & 15) - no cross-lane sums.  Scores go to LDS key-major,
+//           sc[j * TQ + t]; keys a query may not see yet are stored as they are and masked when they are exponentiated.
+//   softmax per query: its own limit, max and sum (a thread of the exp pass keeps one query: 256 % TQ == 0).
+//   pass 2  thread = (key slice, 8 channels) as in attn_decode_k; a value row is loaded once and accumulated into TQ x 8 fp32 registers
+//           with the key's TQ probabilities read from LDS as one broadcast row.  Key slices are summed by shuffles inside a wave, then the
+//           four waves through LDS.
+// Partials (splits > 1) go to ws rows ((b*T + t)*H + h, split) in attn_decode_k's layout: attn_decode_combine_k merges them with B*T rows.
+template <int DT, int D, int TQ, bool KV8>
+__global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
+                                                           const void* __restrict__ vc_, const float* __restrict__ ks,
+                                                           const float* __restrict__ vs, uint16_t* __restrict__ out,
+                                                           const int32_t* __restrict__ lens, int T, int H, int Smax, float scale_log2,
+                                                           int splits, int chunk, float* __restrict__ ws) {
+  static_assert(TQ == 4 || TQ == 8 || TQ == 16, "a probability row is read as 16-byte pieces; the MFMA tile holds 16 queries");
+  extern __shared__ __attribute__((aligned(16))) float sc[];  // [chunk][TQ] scores, then [4][TQ][D] partial outputs
+  __shared__ float red_mx[4][16], red_sum[4][16];
+  constexpr int ES = KV8 ? 1 : 2;            // bytes per cache element
+  constexpr int KK = D / 32;                 // MFMA k steps per key tile
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sp = blockIdx.x % splits;
+  const int h = (blockIdx.x / splits) % H, b = blockIdx.x / (splits * H);
+  const int key0 = sp * chunk;
+  const int len0 = lens[b];
+  // keys [key0, key0 + len) of this split that the LAST query sees; query t sees the first lim(t) of them
+  const int len = max(0, min(min(len0 + T - 1, Smax) - key0, chunk));
+  const int64_t HD = (int64_t)H * D;
+  const uint8_t* kc = (const uint8_t*)kc_ + (((int64_t)b * Smax + key0) * HD + (int64_t)h * D) * ES;
+  const uint8_t* vc = (const uint8_t*)vc_ + (((int64_t)b * Smax + key0) * HD + (int64_t)h * D) * ES;
+  if constexpr (KV8) {
+    ks += ((int64_t)b * H + h) * Smax + key0;
+    vs += ((int64_t)b * H + h) * Smax + key0;
+  }
+  // ---- pass 1
+  const int jj = lane & 15, kq = lane >> 4;
+  uint4 qf[KK];
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk)
+    qf[kk] = jj < T ? *(const uint4*)(q + (int64_t)(b * T + jj) * ldq + (int64_t)h * D + kk * 32 + kq * 8) : make_uint4(0, 0, 0, 0);
+  const int limq = max(0, min(min(len0 + jj, Smax) - key0, chunk));  // keys of this split that query jj sees (jj >= T: unused)
+  float mx = -1e30f;
+  constexpr int UNR = 4;  // key tiles requested per wave before any is used
+  const int ntile = (len + 15) >> 4;
+  for (int t0 = wave; t0 < ntile; t0 += 4 * UNR) {
+    uint4 kraw[UNR][KK];
+    float ksc[UNR][4];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = (t0 + 4 * u) * 16 + jj;
+      const bool ok = j < len;
+#pragma unroll
+      for (int kk = 0; kk < KK; ++kk) {
+        const uint8_t* src = kc + ((int64_t)j * HD + kk * 32 + kq * 8) * ES;
+        if constexpr (KV8) {
+          const uint2 r = ok ? ld_stream8(src) : make_uint2(0, 0);
+          kraw[u][kk] = make_uint4(r.x, r.y, 0, 0);
+        } else {
+          kraw[u][kk] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
+        }
+      }
+      if constexpr (KV8) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int jr = (t0 + 4 * u) * 16 + 4 * kq + r;
+          ksc[u][r] = jr < len ? ks[jr] : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int jt = (t0 + 4 * u) * 16;
+      if (jt >= len) break;
+      f32x4_t s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < KK; ++kk) {
+        uint4 a = kraw[u][kk];
+        if constexpr (KV8) {
+          const uint32_t lo = a.x, hi = a.y;
+          fp8x4_to_pk16<DT>(lo, a.x, a.y);
+          fp8x4_to_pk16<DT>(hi, a.z, a.w);
+        }
+        s4 = mfma16<DT>(a, qf[kk], s4);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = jt + 4 * kq + r;
+        float s = s4[r] * scale_log2;
+        if constexpr (KV8) s = s4[r] * ksc[u][r] * scale_log2;
+        if (j < len) {
+          if (jj < TQ) sc[j * TQ + jj] = s;
+          if (j < limq) mx = fmaxf(mx, s);
+        }
+      }
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  if (lane < 16) red_mx[wave][lane] = mx;
+  __syncthreads();
+  // ---- softmax per query: thread tid keeps query tq = tid % TQ through the whole pass
+  const int tq = tid & (TQ - 1);
+  const int lim = tq < T ? max(0, min(min(len0 + tq, Smax) - key0, chunk)) : 0;
+  const float mxq = fmaxf(fmaxf(red_mx[0][tq], red_mx[1][tq]), fmaxf(red_mx[2][tq], red_mx[3][tq]));
+  float sum = 0.f;
+  for (int idx = tid; idx < len * TQ; idx += 256) {
+    const int j = idx / TQ;
+    const float pj = j < lim ? fast_exp2(sc[idx] - mxq) : 0.f;
+    sc[idx] = pj;
+    sum += pj;
+  }
+#pragma unroll
+  for (int o2 = 32; o2 >= TQ; o2 >>= 1) sum += __shfl_xor(sum, o2, 64);
+  if (lane < TQ) red_sum[wave][lane] = sum;
+  __syncthreads();
+  // ---- pass 2
+  constexpr int OCT = D / 8;    // lanes per value row
+  constexpr int G = 256 / OCT;  // key slices of the block
+  constexpr int UNR2 = KV8 ? 4 : 2;
+  const int c = tid % OCT, gsl = tid / OCT;
+  float o[TQ][8];
+#pragma unroll
+  for (int t = 0; t < TQ; ++t)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[t][e] = 0.f;
+  for (int j0 = gsl; j0 < len; j0 += G * UNR2) {
+    uint4 vraw[UNR2];
+    float vsc[UNR2];
+#pragma unroll
+    for (int u = 0; u < UNR2; ++u) {
+      const int j = j0 + u * G;
+      const bool ok = j < len;
+      const uint8_t* src = vc + ((int64_t)j * HD + c * 8) * ES;
+      if constexpr (KV8) {
+        const uint2 r = ok ? ld_stream8(src) : make_uint2(0, 0);
+        vraw[u] = make_uint4(r.x, r.y, 0, 0);
+        vsc[u] = ok ? vs[j] : 0.f;
+      } else {
+        vraw[u] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
+        vsc[u] = 1.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR2; ++u) {
+      const int j = j0 + u * G;
+      if (j >= len) break;
+      float vv[8];
+      if constexpr (KV8) {
+        fp8x4_to_f32(vraw[u].x, vv);
+        fp8x4_to_f32(vraw[u].y, vv + 4);
+      } else {
+        unpack8<DT>(vraw[u], vv);
+      }
+      float pr[TQ];  // the key's probabilities for all the queries: one broadcast row of LDS
+#pragma unroll
+      for (int t4 = 0; t4 < TQ / 4; ++t4) {
+        const float4 p4 = *(const float4*)(sc + j * TQ + 4 * t4);
+        pr[4 * t4] = p4.x; pr[4 * t4 + 1] = p4.y; pr[4 * t4 + 2] = p4.z; pr[4 * t4 + 3] = p4.w;
+      }
+#pragma unroll
+      for (int t = 0; t < TQ; ++t) {
+        float pj = pr[t];
+        if constexpr (KV8) pj *= vsc[u];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[t][e] = fmaf(pj, vv[e], o[t][e]);
+      }
+    }
+  }
+  // key slices of a wave (lanes c, c + OCT, ...) summed by shuffles
+#pragma unroll
+  for (int o2 = 32; o2 >= OCT; o2 >>= 1)
+#pragma unroll
+    for (int t = 0; t < TQ; ++t)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[t][e] += __shfl_xor(o[t][e], o2, 64);
+  __syncthreads();  // everyone is done reading the probabilities: reuse the buffer for the waves' partials
+  float* part = sc;  // [4][TQ][D]
+  if (lane < OCT) {
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) {
+      float* dst = part + ((wave * TQ + t) * D + c * 8);
+      *(float4*)dst = make_float4(o[t][0], o[t][1], o[t][2], o[t][3]);
+      *(float4*)(dst + 4) = make_float4(o[t][4], o[t][5], o[t][6], o[t][7]);
+    }
+  }
+  __syncthreads();
+  for (int idx = tid; idx < T * D; idx += 256) {
+    const int t = idx / D, d = idx - t * D;
+    const float a = (part[(0 * TQ + t) * D + d] + part[(1 * TQ + t) * D + d]) + (part[(2 * TQ + t) * D + d] + part[(3 * TQ + t) * D + d]);
+    const float sm = (red_sum[0][t] + red_sum[1][t]) + (red_sum[2][t] + red_sum[3][t]);
+    const int64_t row = (int64_t)(b * T + t);
+    if (splits == 1) {
+      out[row * HD + (int64_t)h * D + d] = (uint16_t)st16<DT>(sm > 0.f ? a / sm : 0.f);
+    } else {
+      float* w = ws + ((row * H + h) * splits + sp) * (D + 2);
+      w[d] = a;
+      if (d == 0) {
+        w[D] = fmaxf(fmaxf(red_mx[0][t], red_mx[1][t]), fmaxf(red_mx[2][t], red_mx[3][t]));
+        w[D + 1] = sm;
+      }
+    }
+  }
+}
+
+// Prompt-lookup drafter (transformers PromptLookupCandidateGenerator.get_candidates, no logits processor): one block per row of ids
+// [rows, ld].  For n = min(max_ngram, len - 1) .. 1: the EARLIEST window ids[i .. i + n) equal to the last n tokens whose continuation
+// ids[i + n .. min(i + n + k, len, max_length)) is not empty; the first n that has one wins.  out [rows, k], out_count [rows] (0: none).
+__global__ __launch_bounds__(256) void ngram_draft_k(const int64_t* __restrict__ ids, int64_t ld, int len, int max_ngram, int k,
+                                                     int max_length, int64_t* __restrict__ out, int32_t* __restrict__ out_count) {
+  __shared__ int best;
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int64_t* x = ids + (int64_t)row * ld;
+  const int lim = min(len, max_length);  // a continuation starts before this index
+  int start = -1;
+  if (max_length != len + 1) {  // (one token left: the step that verifies a draft emits one more than it accepts)
+    for (int n = min(max_ngram, len - 1); n >= 1; --n) {
+      if (tid == 0) best = 0x7fffffff;
+      __syncthreads();
+      int mine = 0x7fffffff;
+      for (int i = tid; i + n < lim; i += 256) {
+        bool eq = true;
+        for (int e = 0; e < n && eq; ++e) eq = x[i + e] == x[len - n + e];
+        if (eq) { mine = i; break; }
+      }
+      if (mine != 0x7fffffff) atomicMin(&best, mine);
+      __syncthreads();
+      const int got = best;
+      __syncthreads();
+      if (got != 0x7fffffff) { start = got + n; break; }
+    }
+  }
+  const int cnt = start < 0 ? 0 : min(start + k, lim) - start;
+  if (tid == 0) out_count[row] = cnt;
+  for (int i = tid; i < cnt; i += 256) out[(int64_t)row * k + i] = x[start + i];
+}
+
 }  // namespace
 
 // activation-row count from which the MFMA form is used (measured, profiles/r02_gemv_ab.txt: 3 rows for both weight formats - below
@@ -1432,6 +1703,111 @@ extern "C" int mh_attn_decode_kv8(const void* q, int64_t ldq, const void* k8, co
   if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
   else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
 #undef GO
+  MH_LAUNCH_CHECK();
+}
+
+// ---- T new tokens per sequence (the verify step of prompt-lookup decoding) --------------------------------------------------------------
+template <int DT, bool KV8>
+static void launch_rope_append_multi(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kc, void* vc, float* ks,
+                                     float* vs, int B, int T, int H, int D, int Smax, void* stream) {
+  const int64_t total = (int64_t)B * T * H * (D / 16);
+  hipLaunchKernelGGL((rope_append_multi_k<DT, KV8>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), (uint16_t*)qkv,
+                     (const float2*)cos_sin, pos, rope_pos, kc, vc, ks, vs, B, T, H, D, Smax);
+}
+
+extern "C" int mh_decode_rope_append_multi(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kcache,
+                                           void* vcache, int B, int T, int H, int D, int Smax, int dt, void* stream) {
+  if (!rope_pos) rope_pos = pos;
+  if (!qkv || !cos_sin || !pos || !kcache || !vcache || B <= 0 || T < 1 || T > 16 || H <= 0 || D <= 0 || (D & 15) || Smax <= 0) return MH_ERR_ARG;
+  if (!aligned16(qkv) || !aligned16(kcache) || !aligned16(vcache)) return MH_ERR_ARG;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  if (dt == MH_BF16) launch_rope_append_multi<MH_BF16, false>(qkv, cos_sin, pos, rope_pos, kcache, vcache, nullptr, nullptr, B, T, H, D, Smax, stream);
+  else launch_rope_append_multi<MH_F16, false>(qkv, cos_sin, pos, rope_pos, kcache, vcache, nullptr, nullptr, B, T, H, D, Smax, stream);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_decode_rope_append_multi_kv8(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* k8, void* v8,
+                                               float* kscale, float* vscale, int B, int T, int H, int D, int Smax, int dt, void* stream) {
+  if (!rope_pos) rope_pos = pos;
+  if (!qkv || !cos_sin || !pos || !k8 || !v8 || !kscale || !vscale || B <= 0 || T < 1 || T > 16 || H <= 0 || Smax <= 0) return MH_ERR_ARG;
+  if (!aligned16(qkv) || (((uintptr_t)k8 | (uintptr_t)v8) & 7u)) return MH_ERR_ARG;  // 16-byte row pieces in, 8-byte e4m3 stores out
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  if (dt == MH_BF16) launch_rope_append_multi<MH_BF16, true>(qkv, cos_sin, pos, rope_pos, k8, v8, kscale, vscale, B, T, H, D, Smax, stream);
+  else launch_rope_append_multi<MH_F16, true>(qkv, cos_sin, pos, rope_pos, k8, v8, kscale, vscale, B, T, H, D, Smax, stream);
+  MH_LAUNCH_CHECK();
+}
+
+// queries a block of attn_decode_multi_k is compiled for (its score rows in LDS are this wide)
+static int attn_multi_tq(int T) { return T <= 4 ? 4 : (T <= 8 ? 8 : 16); }
+constexpr int ATTN_MULTI_LDS_MAX = 150 * 1024;  // what mh_attn_decode requests at most
+// score bytes per block the split plan aims for.  Up to 8 queries (<= 133 VGPRs) this leaves LDS room for two blocks per CU; the 16-query form
+// holds 16 x 8 accumulators per lane (256 VGPRs + AGPRs, one wave per SIMD: one block per CU whatever its LDS), where the aim only keeps a
+// block's key range short - profiles/decode_verify_bench.txt times it as it is.
+constexpr int ATTN_MULTI_LDS_AIM = 64 * 1024;
+
+// mh_attn_decode_splits, then more splits (up to the merge kernel's 32) until a split's T x chunk fp32 scores fit 64 KiB of LDS
+extern "C" int mh_attn_decode_multi_splits(int B, int T, int H, int Smax) {
+  if (B <= 0 || T < 1 || T > 16 || H <= 0 || Smax <= 0) return 0;
+  int s = mh_attn_decode_splits(B, H, Smax);  // (a block serves all T queries of its (b, h): the block count is the one-query plan's)
+  const int64_t tq = attn_multi_tq(T);
+  while (s < 32 && tq * ((Smax + s - 1) / s) * 4 > ATTN_MULTI_LDS_AIM) ++s;
+  return s;
+}
+
+template <int DT, int D, int TQ, bool KV8>
+static void launch_attn_multi(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                              const int32_t* lens, int B, int T, int H, int Smax, int splits, int chunk, size_t lds, float* ws, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)attn_decode_multi_k<DT, D, TQ, KV8>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_MULTI_LDS_MAX);
+    attr = true;
+  }
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  hipLaunchKernelGGL((attn_decode_multi_k<DT, D, TQ, KV8>), dim3(B * H * splits), dim3(256), lds, st, (const uint16_t*)q, ldq, kc, vc, ks, vs,
+                     (uint16_t*)out, lens, T, H, Smax, scale_log2, splits, chunk, ws);
+  if (splits > 1)
+    hipLaunchKernelGGL((attn_decode_combine_k<DT, D>), dim3(B * T * H), dim3(D), 0, st, (const float*)ws, (uint16_t*)out, H, splits);
+}
+
+template <bool KV8>
+static int attn_multi_impl(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                           const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream) {
+  if (!q || !kc || !vc || !out || !lens || B <= 0 || T < 1 || T > 16 || H <= 0 || Smax <= 0 || (ldq & 7) || !aligned16(q)) return MH_ERR_ARG;
+  if (KV8 && (!ks || !vs || (((uintptr_t)kc | (uintptr_t)vc) & 7u))) return MH_ERR_ARG;  // the fp8 cache is read 8 bytes at a time
+  if (!KV8 && (!aligned16(kc) || !aligned16(vc))) return MH_ERR_ARG;
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int tq = attn_multi_tq(T);
+  const int splits = ws ? mh_attn_decode_multi_splits(B, T, H, Smax) : 1;
+  const int chunk = (Smax + splits - 1) / splits;
+  const int64_t need = (int64_t)sizeof(float) * tq * (chunk > 4 * D ? chunk : 4 * D);  // scores [chunk][tq], then the four waves' [tq][D] partials
+  if (need > ATTN_MULTI_LDS_MAX) return MH_ERR_SHAPE;
+  if ((int64_t)B * T * H * splits > 0x7fffffff / (D + 2)) return MH_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+#define GO(DT_, D_, TQ_) launch_attn_multi<DT_, D_, TQ_, KV8>(q, ldq, kc, vc, ks, vs, out, lens, B, T, H, Smax, splits, chunk, (size_t)need, ws, st)
+#define GOT(DT_, D_) do { if (tq == 4) GO(DT_, D_, 4); else if (tq == 8) GO(DT_, D_, 8); else GO(DT_, D_, 16); } while (0)
+  if (dt == MH_BF16) { if (D == 128) GOT(MH_BF16, 128); else GOT(MH_BF16, 64); }
+  else { if (D == 128) GOT(MH_F16, 128); else GOT(MH_F16, 64); }
+#undef GOT
+#undef GO
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens, int B,
+                                    int T, int H, int D, int Smax, float* ws, int dt, void* stream) {
+  return attn_multi_impl<false>(q, ldq, kcache, vcache, nullptr, nullptr, out, lens, B, T, H, D, Smax, ws, dt, stream);
+}
+
+extern "C" int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale,
+                                        void* out, const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream) {
+  return attn_multi_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, T, H, D, Smax, ws, dt, stream);
+}
+
+extern "C" int mh_ngram_draft(const int64_t* ids, int64_t ld, int rows, int len, int max_ngram, int k, int max_length, int64_t* out,
+                              int32_t* out_count, void* stream) {
+  if (!ids || !out || !out_count || rows <= 0 || len <= 0 || ld < len || max_ngram <= 0 || k <= 0 || max_length <= 0) return MH_ERR_ARG;
+  hipLaunchKernelGGL(ngram_draft_k, dim3(rows), dim3(256), 0, as_stream(stream), ids, ld, len, max_ngram, k, max_length, out, out_count);
   MH_LAUNCH_CHECK();
 }
 

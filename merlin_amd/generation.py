@@ -67,7 +67,8 @@ def _resolve_lengths(prompt_len, max_new_tokens, max_length):
 
 # decoding options this module implements, with transformers' GenerationConfig defaults
 _DEFAULTS = dict(max_new_tokens=None, max_length=None, eos_token_id=None, pad_token_id=None, do_sample=False, temperature=1.0, top_k=50,
-                 top_p=1.0, num_beams=1, length_penalty=1.0, early_stopping=False, use_cache=True)
+                 top_p=1.0, num_beams=1, length_penalty=1.0, early_stopping=False, use_cache=True, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=2)
 # options that are accepted only at the value that leaves the implemented modes unchanged (anything else is a decoding mode the
 # reference's scripts never reach: refuse it instead of silently returning something different)
 _NEUTRAL = dict(repetition_penalty=(1.0, None), no_repeat_ngram_size=(0, None), num_return_sequences=(1, None), num_beam_groups=(1, None),
@@ -94,7 +95,7 @@ def _resolve_options(generation_config, kw):
                 raise NotImplementedError(f"generation_config.{k}={v!r} is not part of the decoding modes the reference's eval scripts use")
     for k, v in kw.items():
         if k in _DEFAULTS:
-            opt[k] = _DEFAULTS[k] if v is None and k not in ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id") else v
+            opt[k] = _DEFAULTS[k] if v is None and k not in ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "prompt_lookup_num_tokens") else v
         elif k in _NEUTRAL:
             ok = _NEUTRAL[k]
             if ok is not None and v not in ok and v != []:
@@ -126,6 +127,18 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         raise ValueError("fp4_weights and fp8_weights are alternatives: pick one weight format for the decode step")
     if fp4_weights and not use_cache:
         raise ValueError("fp4_weights=True applies to the KV-cache decode step: it needs use_cache=True")
+    lookup, max_ngram = o["prompt_lookup_num_tokens"], o["max_matching_ngram_size"]
+    if lookup is not None:  # prompt-lookup speculative decoding: refused before any device work where it does not apply
+        if num_beams > 1:
+            raise ValueError("prompt_lookup_num_tokens drafts for greedy search and sampling: it cannot be combined with num_beams > 1")
+        if not use_cache:
+            raise ValueError("assisted generate requires `use_cache=True`")
+        if input_ids.shape[0] > 1:
+            raise ValueError("assisted generate is only supported for batch_size = 1")
+        if not isinstance(lookup, int) or isinstance(lookup, bool) or not 1 <= lookup <= 15:
+            raise ValueError(f"prompt_lookup_num_tokens = {lookup!r}: the verify step takes 1..15 drafted tokens (16 rows with the token before them)")
+        if not isinstance(max_ngram, int) or max_ngram <= 0:
+            raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
     cfg = model.config
     eos_ids = _as_list(cfg.eos_token_id if eos_token_id is None else eos_token_id)
     pad = pad_token_id if pad_token_id is not None else (cfg.pad_token_id if cfg.pad_token_id is not None else (eos_ids[0] if eos_ids else 0))
@@ -147,10 +160,17 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
     if streamer is not None:
         streamer.put(input_ids.cpu())
-    if not use_cache:
+    stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
+    if getattr(model, "engine", None) is not None:
+        model.engine.last_generate_stats = stats
+    if lookup is not None:
+        out = _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
+                             fp4_weights, lookup, max_ngram, stats)
+    elif not use_cache:
         out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer)
     else:
         out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights)
+        stats["plain_steps"] = max(0, out.shape[1] - input_ids.shape[1] - 1)  # every new token but the first (the prefill's) is one decode step
     if streamer is not None:
         streamer.end()
     return out
@@ -223,6 +243,123 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
             logits = eng.decode_step(nxt, cache, fp8=fp8_weights, fp4=fp4_weights)
     if padded:  # right-padded prompts (an extension; HF wants left padding): each row's continuation starts at its own length
         cur = _compact(ids, lens, torch.stack(new, dim=1), pad)
+    return cur.to(input_ids.device)
+
+
+def _prompt_lookup(ids, k, max_ngram, max_length):
+    """transformers' PromptLookupCandidateGenerator.get_candidates (no logits processor, no EOS cut) on a list of token ids: for n from
+    min(max_ngram, len - 1) down to 1, the EARLIEST window equal to the last n tokens whose continuation
+    ids[start : min(start + k, len, max_length)] is not empty; [] when no n has one, or when only one more token fits (max_length ==
+    len + 1: the verifying step emits one token more than it accepts).  The restatement mh_ngram_draft is tested against."""
+    ids = [int(t) for t in ids]
+    n_ids = len(ids)
+    if max_length == n_ids + 1:
+        return []
+    for n in range(min(max_ngram, n_ids - 1), 0, -1):
+        tail = ids[n_ids - n:]
+        for i in range(n_ids - n + 1):
+            if ids[i:i + n] == tail:
+                start = i + n
+                end = min(start + k, n_ids, max_length)
+                if start < end:
+                    return ids[start:end]
+    return []
+
+
+def _accept(draft, selected, room, stops):
+    """The accept rule of one verify step, as a pure function.  draft: the c drafted tokens; selected: the tokens selected from the verify
+    step's c + 1 (or more) logits rows, selected[i] conditioned on draft[:i]; room: how many tokens still fit below max_length;
+    stops(i) -> bool: the stopping criteria and EOS test on the sequence with selected[:i + 1] appended (called in order, each prefix once,
+    never past a stop).  -> (emitted tokens, a = drafted tokens accepted, stopped).  The longest prefix on which draft and selection agree is
+    accepted and the a + 1 selected tokens are emitted - up to and including the first stop, and never more than `room`."""
+    a = 0
+    while a < len(draft) and int(draft[a]) == int(selected[a]):
+        a += 1
+    out, stopped = [], False
+    for i in range(min(a + 1, room)):
+        out.append(int(selected[i]))
+        if stops(i):
+            stopped = True
+            break
+    return out, a, stopped
+
+
+def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
+                   fp4_weights, k, max_ngram, stats):
+    """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
+    (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
+    once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
+    one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step."""
+    eng = model.engine
+    B, P = input_ids.shape
+    V = model.config.vocab_size
+    max_new = max_len - P
+    T = k + 1
+    logits, cache = eng.prefill(input_ids, attention_mask, images, max_new + k, kv_fp8=fp8_kv)  # k rows of room for a rejected draft's tail
+    dev = logits.device
+    graph = vgraph = None
+    if use_graph and logits.is_cuda and max_new > 2:
+        graph, g_tok, g_logits = eng.capture_decode_graph(cache, fp8=fp8_weights, fp4=fp4_weights)
+        vgraph, v_tok, v_logits = eng.capture_verify_graph(cache, T, fp8=fp8_weights, fp4=fp4_weights)
+    am = attention_mask.to(dev).to(torch.bool) if attention_mask is not None else None
+    padded = am is not None and not bool(am.all()) and cache.rpos is None  # right-padded prompt: as _sample_cached
+    lens = am.sum(dim=1) if padded else None
+    seq = torch.full((1, max_len), pad, dtype=torch.int64, device=dev)  # the sequence as the criteria and the drafter see it
+    seq[:, :P] = input_ids.to(dev)
+    n = P  # valid length of seq
+    sel_kw = {key: sel[key] for key in ("do_sample", "temperature", "top_k", "top_p", "seed")}
+
+    def emit(cand, draft):
+        """Append the accepted part of `cand` (selected tokens, on the host) to seq; -> (tokens emitted, accepted, stopped)."""
+        nonlocal n
+        base = n
+
+        def stops(i):
+            seq[0, base + i] = cand[i]
+            return bool(stop(seq[:, :base + i + 1], None)[0])
+
+        out, a, stopped = _accept(draft, cand, max_len - n, stops)
+        n = base + len(out)
+        if streamer is not None:
+            streamer.put(torch.tensor([out], dtype=torch.int64))
+        return out, a, stopped
+
+    first = _select(logits, V, sel, 0)
+    out, _, stopped = emit(first.tolist(), [])
+    while not stopped and n < max_len:
+        emitted = n - P
+        draft_dev, cnt = O.ngram_draft(seq, n, max_ngram, k, max_len)
+        c = int(cnt[0])
+        last = seq[:, n - 1]
+        if c == 0:
+            if graph is not None:
+                g_tok.copy_(last)
+                graph.replay()
+                logits = g_logits
+            else:
+                logits = eng.decode_step(last, cache, fp8=fp8_weights, fp4=fp4_weights)
+            stats["plain_steps"] += 1
+            out, _, stopped = emit(_select(logits, V, sel, emitted).tolist(), [])
+            continue
+        toks = v_tok if vgraph is not None else torch.empty(1, T, dtype=torch.int64, device=dev)
+        toks[:, 0] = last
+        toks[:, 1:] = pad  # a short draft is padded to the step's k + 1 rows; their logits are not looked at
+        toks[:, 1:1 + c] = draft_dev[:, :c]
+        if vgraph is not None:
+            vgraph.replay()
+            logits = v_logits
+        else:
+            logits = eng.verify_step(toks, cache, fp8=fp8_weights, fp4=fp4_weights)
+        picked = O.select_tokens_multi(logits, V, step0=emitted, **sel_kw)[:, 0]  # [T]
+        both = torch.cat([picked, draft_dev[0]]).tolist()  # one transfer
+        out, a, stopped = emit(both[:c + 1], both[T:T + c])
+        cache.advance(a + 1)  # the last token and the a accepted drafts are keys now; the stale rows behind them get overwritten
+        stats["verify_steps"] += 1
+        stats["drafted"] += c
+        stats["accepted"] += min(a, len(out))  # (a draft token that agreed beyond a stop or max_length was not emitted)
+    cur = seq[:, :n]
+    if padded:
+        cur = _compact(seq[:, :P], lens, seq[:, P:n], pad)
     return cur.to(input_ids.device)
 
 

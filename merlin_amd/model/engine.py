@@ -1254,6 +1254,13 @@ class HipEngine:
         def nbytes(self):
             return sum(t.numel() * t.element_size() for lst in self.sets() for t in lst)
 
+        def advance(self, n):
+            """lens += n (an int, or int32 [B] on the device), and rpos with it: the tokens of a verify_step that are kept.  Rows beyond the
+            new length are stale; the next step overwrites them - that is the whole roll-back of a rejected draft."""
+            self.lens.add_(n)
+            if self.rpos is not None:
+                self.rpos.add_(n)
+
     def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False):
         """Full forward over the prompt that also fills a KV cache; returns (logits fp32 [B, V] at each sequence's last
         valid position, cache).  Right-padded prompts (attention_mask) decode from their own length.
@@ -1348,8 +1355,27 @@ class HipEngine:
         fp8=True uses the fp8 weight copies of quantize_decode_weights(), fp4=True the MXFP4 copies of quantize_decode_weights_fp4()
         (one of the two).  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its own kernels (mh_decode_rope_append_kv8,
         mh_attn_decode_kv8), with any weight format."""
+        logits = self._decode_rows(tokens, cache, fp8, fp4, 0)
+        cache.lens.add_(1)  # in place (after every kernel that read it as `pos`): the captured graph sees the same buffer
+        if cache.rpos is not None:
+            cache.rpos.add_(1)
+        return logits
+
+    def verify_step(self, tokens, cache, fp8=False, fp4=False):
+        """T new tokens per sequence (tokens int64 [B, T], B*T <= 16) at positions cache.lens[b] .. + T - 1: the decode step's body on
+        B*T rows, one pass over the weights; returns logits fp32 [B, T, V], row (b, t) conditioned on the cache and tokens[b, :t + 1].
+        Writes cache rows lens .. lens + T - 1 (mh_decode_rope_append_multi*, attention by mh_attn_decode_multi* with causality inside
+        the block) and does NOT advance the cache: the caller keeps what it accepts with cache.advance(n); rows beyond the new length
+        are stale and the next step overwrites them.  The verify step of prompt-lookup decoding (generation.py)."""
+        B, T = tokens.shape
+        if B != cache.B or not 1 <= T or B * T > 16:
+            raise ValueError(f"verify_step takes tokens [B = {cache.B}, T] with B*T <= 16, got {tuple(tokens.shape)}")
+        return self._decode_rows(tokens.reshape(-1), cache, fp8, fp4, T).view(B, T, -1)
+
+    def _decode_rows(self, tokens, cache, fp8, fp4, T):
+        """The decode body: T = 0, one row per sequence (decode_step); T >= 1, rows b*T + t (verify_step).  Does not advance the cache."""
         if fp8 and fp4:
-            raise ValueError("decode_step: fp8 and fp4 weights are alternatives, not a combination")
+            raise ValueError(f"{'verify_step' if T else 'decode_step'}: fp8 and fp4 weights are alternatives, not a combination")
         cfg = self.model.config
         A = self.arena
         d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
@@ -1371,7 +1397,15 @@ class HipEngine:
         lens1 = pos + 1
         for li, (wqkv, wo, wgu, wd) in enumerate(layers):
             W = self.llama[li]
-            if cache.fp8:  # fp8 KV cache: the projection, then RoPE + quantised append as a launch of its own
+            if T:  # several positions per sequence: the projection, then RoPE + append and attention over the T rows of a sequence
+                qkv = gemv_norm(x, W.ln1, eps, wqkv)
+                if cache.fp8:
+                    O.decode_rope_append_multi_kv8(qkv, self.rope, pos, *cache.layer(li), T, H, D, rope_pos=cache.rpos)
+                    o = O.attn_decode_multi_kv8(qkv[:, :d], *cache.layer(li), lens1, T, H, D)
+                else:
+                    O.decode_rope_append_multi(qkv, self.rope, pos, cache.k[li], cache.v[li], T, H, D, rope_pos=cache.rpos)
+                    o = O.attn_decode_multi(qkv[:, :d], cache.k[li], cache.v[li], lens1, T, H, D)
+            elif cache.fp8:  # fp8 KV cache: the projection, then RoPE + quantised append as a launch of its own
                 qkv = gemv_norm(x, W.ln1, eps, wqkv)
                 O.decode_rope_append_kv8(qkv, self.rope, pos, *cache.layer(li), H, D, rope_pos=cache.rpos)
                 o = O.attn_decode_kv8(qkv[:, :d], *cache.layer(li), lens1, H, D)
@@ -1383,11 +1417,7 @@ class HipEngine:
             act = gemv_norm(x2, W.ln2, eps, wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
             x = gemv(act, wd, resid=x2)
         hn = O.rmsnorm_fwd(x, A.view("model.norm.weight"), eps)
-        logits = gemv(hn, head, out_f32=True, n=V)  # (the 16-bit weight view carries its zero pad rows; the fp8 copy has V rows)
-        cache.lens.add_(1)  # in place (after every kernel that read it as `pos`): the captured graph sees the same buffer
-        if cache.rpos is not None:
-            cache.rpos.add_(1)
-        return logits
+        return gemv(hn, head, out_f32=True, n=V)  # (the 16-bit weight view carries its zero pad rows; the fp8 copy has V rows)
 
     def capture_decode_graph(self, cache, fp8=False, fp4=False):
         """Capture one decode step (≈300 launches) into a HIP graph bound to `cache`: returns (graph, token buffer int64 [B],
@@ -1412,6 +1442,23 @@ class HipEngine:
         cache.lens.copy_(keep)  # capture does not execute, but keep the invariant explicit
         if keep_r is not None:
             cache.rpos.copy_(keep_r)
+        return g, tok, logits
+
+    def capture_verify_graph(self, cache, T, fp8=False, fp4=False):
+        """capture_decode_graph for verify_step: returns (graph, token buffer int64 [B, T], logits buffer fp32 [B, T, V]).  One eager
+        warm-up on a side stream, then the capture on a single stream (no parallel branches).  The step reads cache.lens / rpos from
+        the device and does not advance them, so the graph can be replayed next to the plain decode graph on the same cache; the
+        warm-up writes only rows at and beyond the current length, which the next real step rewrites."""
+        dev = self.arena.flat.device
+        tok = torch.zeros(cache.B, T, dtype=torch.int64, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self.verify_step(tok, cache, fp8=fp8, fp4=fp4)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            logits = self.verify_step(tok, cache, fp8=fp8, fp4=fp4)
         return g, tok, logits
 
     # standalone sub-module calls (reference module surface; not used by the fused forward)

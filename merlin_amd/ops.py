@@ -392,6 +392,82 @@ def attn_decode_kv8(q, k8, v8, kscale, vscale, lens, H, D, out=None, split_kv=Tr
     return out
 
 
+def decode_rope_append_multi(qkv, table, pos, kcache, vcache, T, H, D, rope_pos=None):
+    """decode_rope_append for T new tokens per sequence: qkv [B*T, 3*H*D], row b*T + t rotated in place at rope_pos[b] + t (default pos[b] + t)
+    and appended at cache row pos[b] + t; bit-identical to T single-token calls.  Rows that would land at or beyond Smax are left untouched."""
+    B = pos.shape[0]
+    assert qkv.shape == (B * T, 3 * H * D) and qkv.is_contiguous() and pos.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
+    assert rope_pos is None or rope_pos.dtype == torch.int32
+    L.call("mh_decode_rope_append_multi", qkv, table, pos, rope_pos, kcache, vcache, B, T, H, D, kcache.shape[1], dt_of(qkv), _stream())
+
+
+def decode_rope_append_multi_kv8(qkv, table, pos, k8, v8, kscale, vscale, T, H, D, rope_pos=None):
+    """decode_rope_append_multi on the fp8 KV cache (k8, v8 uint8 [B, Smax, H*D]; kscale, vscale fp32 [B, H, Smax])."""
+    B = pos.shape[0]
+    assert qkv.shape == (B * T, 3 * H * D) and qkv.is_contiguous() and pos.dtype == torch.int32
+    assert k8.is_contiguous() and v8.is_contiguous() and k8.dtype == v8.dtype == torch.uint8
+    assert kscale.is_contiguous() and vscale.is_contiguous() and kscale.shape == vscale.shape == (B, H, k8.shape[1])
+    assert rope_pos is None or rope_pos.dtype == torch.int32
+    L.call("mh_decode_rope_append_multi_kv8", qkv, table, pos, rope_pos, k8, v8, kscale, vscale, B, T, H, D, k8.shape[1], dt_of(qkv), _stream())
+
+
+def attn_decode_multi_splits(B, T, H, Smax):
+    """Key splits of attn_decode_multi / attn_decode_multi_kv8 with split_kv=True (mh_attn_decode_multi_splits)."""
+    return int(L.lib().mh_attn_decode_multi_splits(B, T, H, Smax))
+
+
+def attn_decode_multi(q, kcache, vcache, lens, T, H, D, out=None, split_kv=True):
+    """T queries per sequence: q [B*T, H*D] view (row stride ldq, row b*T + t) against the cache [B, Smax, H*D]; query (b, t) sees keys
+    [0, lens[b] + t).  split_kv=False: one block per (b, h) (refused where T x Smax scores do not fit the kernel's LDS)."""
+    B = lens.shape[0]
+    assert q.shape == (B * T, H * D) and q.stride(1) == 1 and lens.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
+    out = torch.empty(B * T, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    Smax = kcache.shape[1]
+    splits = attn_decode_multi_splits(B, T, H, Smax)
+    ws = torch.empty(B * T * H * splits * (D + 2), dtype=torch.float32, device=q.device) if (splits > 1 and split_kv) else None
+    L.call("mh_attn_decode_multi", q, q.stride(0), kcache, vcache, out, lens, B, T, H, D, Smax, ws, dt_of(q), _stream())
+    return out
+
+
+def attn_decode_multi_kv8(q, k8, v8, kscale, vscale, lens, T, H, D, out=None, split_kv=True):
+    """attn_decode_multi against the fp8 KV cache (k8, v8 uint8 [B, Smax, H*D]; kscale, vscale fp32 [B, H, Smax])."""
+    B = lens.shape[0]
+    out = torch.empty(B * T, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    Smax = k8.shape[1]
+    assert q.shape == (B * T, H * D) and q.stride(1) == 1 and lens.dtype == torch.int32
+    assert k8.dtype == v8.dtype == torch.uint8 and k8.shape == v8.shape == (B, Smax, H * D) and k8.is_contiguous() and v8.is_contiguous()
+    assert kscale.dtype == vscale.dtype == torch.float32 and kscale.shape == vscale.shape == (B, H, Smax)
+    assert kscale.is_contiguous() and vscale.is_contiguous()
+    splits = attn_decode_multi_splits(B, T, H, Smax)
+    ws = torch.empty(B * T * H * splits * (D + 2), dtype=torch.float32, device=q.device) if (splits > 1 and split_kv) else None
+    L.call("mh_attn_decode_multi_kv8", q, q.stride(0), k8, v8, kscale, vscale, out, lens, B, T, H, D, Smax, ws, dt_of(q), _stream())
+    return out
+
+
+def ngram_draft(ids, length, max_ngram, k, max_length):
+    """Prompt-lookup draft on the device (mh_ngram_draft; generation._prompt_lookup is its restatement): ids int64 [rows, >= length] ->
+    (draft int64 [rows, k], count int32 [rows]); only the first count[r] entries of a draft row are written."""
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and ids.shape[1] >= length
+    rows = ids.shape[0]
+    out = torch.empty(rows, k, dtype=torch.int64, device=ids.device)
+    cnt = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    L.call("mh_ngram_draft", ids, ids.stride(0), rows, length, max_ngram, k, max_length, out, cnt, _stream())
+    return out, cnt
+
+
+def select_tokens_multi(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step0=0):
+    """logits fp32 [B, T, >=V] -> int64 [T, B]: position t of sequence b is drawn as the plain path draws its token number step0 + t, i.e. with
+    mh_select_tokens' key (seed, step0 + t, row b) - one launch per t on the strided view logits[:, t]."""
+    B, T = logits.shape[:2]
+    V = logits.shape[2] if V is None else V
+    assert logits.dtype == torch.float32 and logits.stride(2) == 1
+    out = torch.empty(T, B, dtype=torch.int64, device=logits.device)
+    for t in range(T):
+        L.call("mh_select_tokens", logits[:, t], logits.stride(0), B, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step0 + t,
+               out[t], None, _stream())
+    return out
+
+
 def attn_decode_fused_merge(on: bool):
     """A/B switch: split-KV partials merged by a second launch (default) or by the last block of a (b, h) to finish."""
     L.lib().mh_attn_decode_fused_merge(1 if on else 0)

@@ -3,11 +3,16 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
-from a HIP graph over the 32 layers' caches in turn so that no launch finds its keys in a cache."""
+from a HIP graph over the 32 layers' caches in turn so that no launch finds its keys in a cache.
+
+--verify: the verify arm instead (prompt-lookup speculative decoding): for 16-bit, fp8 and MXFP4 weights, the plain decode step and the
+verify step (engine.verify_step, T rows of one sequence) at T = 2, 4, 8, 16, each replayed from its HIP graph on the same cache, with the
+break-even acceptance t_verify / t_plain - 1 (extra tokens a verify step must yield to pay for itself); then one mh_attn_decode_multi
+launch at T = 8 against eight one-query launches, both from graphs over the 32 layers' caches."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,6 +38,9 @@ if "--kv" in sys.argv:
     KV8 = sys.argv[_i + 1] == "fp8"
     del sys.argv[_i:_i + 2]
 KV = "fp8" if KV8 else "16-bit"
+VERIFY = "--verify" in sys.argv
+if VERIFY:
+    sys.argv.remove("--verify")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 NEW = 160
@@ -43,11 +51,72 @@ vision = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, nu
 model = build_synthetic_model(llama, vision, projector="mlp", conv_stride=1, dtype=torch.bfloat16, device="cuda", seed=0)
 g = torch.Generator().manual_seed(0)
 ids = torch.randint(3, 32000, (B, S), generator=g).to(dev)
+
+
+def _replay_ms(graph, n=24, warm=3):
+    for _ in range(warm):
+        graph.replay()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        graph.replay()
+    b.record(); torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def verify_arm(cache):
+    """Plain step vs verify step per weight format, then the multi-query attention launch against T one-query launches.  The plain graph
+    advances cache.lens by one per replay and the verify graph leaves it alone: lens is put back before each timing, so every figure is
+    taken at `context` keys (+ the 30 replays of a plain timing)."""
+    eng = model.engine
+    keep = cache.lens.clone()
+    for name, kw in (("16-bit", dict()), ("fp8", dict(fp8=True)), ("fp4", dict(fp4=True))):
+        g, gtok, _ = eng.capture_decode_graph(cache, **kw)
+        t_plain = _replay_ms(g)
+        cache.lens.copy_(keep)
+        del g
+        for T in (2, 4, 8, 16):
+            if B * T > 16:
+                continue
+            gv, vtok, _ = eng.capture_verify_graph(cache, T, **kw)
+            t_v = _replay_ms(gv)
+            del gv
+            print(json.dumps({"verify": name + " weights", "kv": KV, "B": B, "context": S, "T": T, "ms_plain_step": round(t_plain, 3),
+                              "ms_verify_step": round(t_v, 3), "break_even_extra_tokens": round(t_v / t_plain - 1, 3)}), flush=True)
+    if B == 1:
+        T = 8
+        q1 = torch.randn(B, 4096, dtype=torch.bfloat16, device=dev)
+        qT = torch.randn(B * T, 4096, dtype=torch.bfloat16, device=dev)
+        if KV8:
+            one = lambda li: _O.attn_decode_kv8(q1, *cache.layer(li), keep, 32, 128)  # noqa: E731
+            multi = lambda li: _O.attn_decode_multi_kv8(qT, *cache.layer(li), keep, T, 32, 128)  # noqa: E731
+        else:
+            one = lambda li: _O.attn_decode(q1, cache.k[li], cache.v[li], keep, 32, 128)  # noqa: E731
+            multi = lambda li: _O.attn_decode_multi(qT, cache.k[li], cache.v[li], keep, T, 32, 128)  # noqa: E731
+        one(0); multi(0)
+        torch.cuda.synchronize()
+        g1, gm = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g1):
+            for li in range(32):
+                for _ in range(T):
+                    one(li)
+        with torch.cuda.graph(gm):
+            for li in range(32):
+                multi(li)
+        us1, usm = _replay_ms(g1, n=8, warm=2) / 32 * 1e3, _replay_ms(gm, n=8, warm=2) / 32 * 1e3
+        print(json.dumps({"attention": "mh_attn_decode_multi" + ("_kv8" if KV8 else ""), "T": T, "keys": int(keep[0]), "us_multi_launch": round(usm, 2),
+                          "us_T_single_launches": round(us1, 2), "ratio": round(usm / us1, 3)}), flush=True)
+
+
 with torch.no_grad():
     t0 = time.time()
     logits, cache = model.engine.prefill(ids, None, None, NEW + 8, kv_fp8=KV8)
     torch.cuda.synchronize()
     print(f"prefill B={B} S={S}: {(time.time()-t0)*1e3:.1f} ms (first call, incl. arena setup)", flush=True)
+    if VERIFY:
+        verify_arm(cache)
+        sys.exit(0)
     tok = logits.argmax(-1)
     for _ in range(3):
         logits = model.engine.decode_step(tok, cache); tok = logits.argmax(-1)
