@@ -411,6 +411,33 @@ int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcache, const v
                          int H, int D, int Smax, float* ws, int dt, void* stream);
 int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                              const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream);
+/* ---- beam search on a shared prompt cache (generate(num_beams = nb, share_prompt_kv = True)).  The K/V of a prompt lie ONCE, where the
+ * prefill wrote them (the prefix: pre_k / pre_v [Bp, Pmax, H*D], fp8: + pre_kscale / pre_vscale [Bp, H, Pmax]; pre_lens[p] valid rows);
+ * beam row m = p*nb + i owns only rows of generated tokens (the suffix: suf_k / suf_v [Bp*nb, G, H*D], fp8: + scales [Bp*nb, H, G], the
+ * layouts of the cache above, so mh_gemv_qkv_rope / mh_decode_rope_append* append to it as they are with Smax = G, pos = tokens generated so
+ * far and rope_pos = pre_lens[p] + pos).  anc int32 [Bp*nb, G]: anc[m, g] is the suffix row that holds key / value g of beam m's history.
+ * mh_beam_ancestry: HF `_reorder_cache` on the table alone - anc_out[m, g] = anc_in[beam_idx[m], g] for g < gen[m] and anc_out[m, gen[m]] = m
+ *   (the row the next append writes is the beam's own); entries beyond gen[m] are not written.  beam_idx int64 [rows] and gen int32 [rows]
+ *   are read on the device; anc_in != anc_out (two buffers that the caller swaps); no atomics; <= 4*G bytes per beam, no K/V moved.
+ * mh_attn_decode_beams / _kv8: q rows m (row stride ldq, 16-byte aligned), out [Bp*nb, H*D], 1 <= nb <= 16, D in {64, 128}; beam m attends the
+ *   keys [0, min(pre_lens[p], Pmax)) of its prompt's prefix and the suffix keys g < min(slens[m], G), each read from suffix row anc[m, g]
+ *   (slens = generated keys the beam sees, its own new one included).  Prefix part: one block per (prompt, head, key split) loads every key
+ *   and value row once for all nb beams (mh_attn_decode_multi's kernel without a per-query limit); suffix part: one block per (beam row,
+ *   head, key split), mh_attn_decode's passes with the row indirection; one merge launch.  ws (required): Bp*nb*H*(P + S)*(D+2) floats,
+ *   P = mh_attn_decode_beams_splits(Bp, nb, H, Pmax, G) prefix splits - the one-query plan of Bp sequences, then more until nb' x chunk fp32
+ *   scores fit 64 KiB (nb' = nb rounded up to 4, 8 or 16), at most 32 - S - and S = mh_attn_decode_beams_suffix_splits(G) = ceil(G / 256),
+ *   at most 4.  MH_ERR_SHAPE (mh_attn_decode_beams_splits returns 0) where 32 - S splits still leave a block more than 150 KiB of scores:
+ *   Pmax above 2400 (32 - S) keys at nb > 8 (74 400 at G <= 256), 4800 (32 - S) at nb > 4, 9600 (32 - S) otherwise; and for G above 153 600. */
+int mh_beam_ancestry(const int32_t* anc_in, int32_t* anc_out, const int64_t* beam_idx, const int32_t* gen, int rows, int G, void* stream);
+int mh_attn_decode_beams_splits(int Bp, int nb, int H, int Pmax, int G);
+int mh_attn_decode_beams_suffix_splits(int G);
+int mh_attn_decode_beams(const void* q, int64_t ldq, const void* pre_k, const void* pre_v, const int32_t* pre_lens, const void* suf_k,
+                         const void* suf_v, const int32_t* anc, const int32_t* slens, void* out, int Bp, int nb, int H, int D, int Pmax, int G,
+                         float* ws, int dt, void* stream);
+int mh_attn_decode_beams_kv8(const void* q, int64_t ldq, const void* pre_k8, const void* pre_v8, const float* pre_kscale, const float* pre_vscale,
+                             const int32_t* pre_lens, const void* suf_k8, const void* suf_v8, const float* suf_kscale, const float* suf_vscale,
+                             const int32_t* anc, const int32_t* slens, void* out, int Bp, int nb, int H, int D, int Pmax, int G, float* ws,
+                             int dt, void* stream);
 /* Prompt-lookup drafter (transformers PromptLookupCandidateGenerator.get_candidates without a logits processor): ids int64 [rows, ld],
  * the first `len` of every row valid.  For n = min(max_ngram, len - 1) down to 1: the EARLIEST window equal to the last n tokens whose
  * continuation ids[start : min(start + k, len, max_length)] is not empty; the first n that yields one wins.  out int64 [rows, k] gets

@@ -20,6 +20,9 @@
 //                       per (sequence, head, token)): prefill quantiser, RoPE + quantised append, attention reading half the bytes per key.
 //   mh_quant_fp4_b32 / mh_gemv_fp4w / mh_gemv_fp4w_norm / mh_gemv_fp4w_qkv_rope   the projections on MXFP4 weights (e2m1 values, two per byte, one
 //                       power-of-two scale byte per 32 k: 0.53 bytes per weight, 3.6 GB per token at 7B) - at the end of this file.
+//   mh_beam_ancestry / mh_attn_decode_beams (+ _kv8)   beam search on a shared prompt cache: the prompt's keys once per prompt for all its
+//                       beams (the multi-query kernel, beams as queries), per-beam rows only for the generated tokens, found through an
+//                       ancestry table that the re-ordering of beams rewrites instead of moving any K/V.
 //   mh_decode_rope_append_multi / mh_attn_decode_multi (+ _kv8) / mh_ngram_draft   T <= 16 new tokens of one sequence in one step (the verify
 //                       step of prompt-lookup decoding): append at T consecutive positions, attention with every key / value row loaded once
 //                       for all T queries (scores on the matrix pipe, causality inside the block), and the device-side drafter.
@@ -1229,12 +1232,15 @@ __global__ __launch_bounds__(256) void rope_append_multi_k(uint16_t* __restrict_
 //           with the key's TQ probabilities read from LDS as one broadcast row.  Key slices are summed by shuffles inside a wave, then the
 //           four waves through LDS.
 // Partials (splits > 1) go to ws rows ((b*T + t)*H + h, split) in attn_decode_k's layout: attn_decode_combine_k merges them with B*T rows.
-template <int DT, int D, int TQ, bool KV8>
+// BEAMS (the prefix part of mh_attn_decode_beams): the T queries are the beams of prompt b and all of them see all min(lens[b], Smax)
+// keys - no per-query limit; the block always leaves partials, in slot sp of a ws row that is wsplits slots wide (the suffix part fills
+// the slots behind the prefix splits).  Nothing else differs, and nothing differs where BEAMS is false.
+template <int DT, int D, int TQ, bool KV8, bool BEAMS = false>
 __global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
                                                            const void* __restrict__ vc_, const float* __restrict__ ks,
                                                            const float* __restrict__ vs, uint16_t* __restrict__ out,
                                                            const int32_t* __restrict__ lens, int T, int H, int Smax, float scale_log2,
-                                                           int splits, int chunk, float* __restrict__ ws) {
+                                                           int splits, int chunk, float* __restrict__ ws, int wsplits) {
   static_assert(TQ == 4 || TQ == 8 || TQ == 16, "a probability row is read as 16-byte pieces; the MFMA tile holds 16 queries");
   extern __shared__ __attribute__((aligned(16))) float sc[];  // [chunk][TQ] scores, then [4][TQ][D] partial outputs
   __shared__ float red_mx[4][16], red_sum[4][16];
@@ -1246,7 +1252,7 @@ __global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __res
   const int key0 = sp * chunk;
   const int len0 = lens[b];
   // keys [key0, key0 + len) of this split that the LAST query sees; query t sees the first lim(t) of them
-  const int len = max(0, min(min(len0 + T - 1, Smax) - key0, chunk));
+  const int len = max(0, min(min(BEAMS ? len0 : len0 + T - 1, Smax) - key0, chunk));
   const int64_t HD = (int64_t)H * D;
   const uint8_t* kc = (const uint8_t*)kc_ + (((int64_t)b * Smax + key0) * HD + (int64_t)h * D) * ES;
   const uint8_t* vc = (const uint8_t*)vc_ + (((int64_t)b * Smax + key0) * HD + (int64_t)h * D) * ES;
@@ -1260,7 +1266,7 @@ __global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __res
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk)
     qf[kk] = jj < T ? *(const uint4*)(q + (int64_t)(b * T + jj) * ldq + (int64_t)h * D + kk * 32 + kq * 8) : make_uint4(0, 0, 0, 0);
-  const int limq = max(0, min(min(len0 + jj, Smax) - key0, chunk));  // keys of this split that query jj sees (jj >= T: unused)
+  const int limq = BEAMS ? len : max(0, min(min(len0 + jj, Smax) - key0, chunk));  // keys of this split that query jj sees (jj >= T: unused)
   float mx = -1e30f;
   constexpr int UNR = 4;  // key tiles requested per wave before any is used
   const int ntile = (len + 15) >> 4;
@@ -1322,7 +1328,7 @@ __global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __res
   __syncthreads();
   // ---- softmax per query: thread tid keeps query tq = tid % TQ through the whole pass
   const int tq = tid & (TQ - 1);
-  const int lim = tq < T ? max(0, min(min(len0 + tq, Smax) - key0, chunk)) : 0;
+  const int lim = tq < T ? (BEAMS ? len : max(0, min(min(len0 + tq, Smax) - key0, chunk))) : 0;
   const float mxq = fmaxf(fmaxf(red_mx[0][tq], red_mx[1][tq]), fmaxf(red_mx[2][tq], red_mx[3][tq]));
   float sum = 0.f;
   for (int idx = tid; idx < len * TQ; idx += 256) {
@@ -1411,16 +1417,162 @@ __global__ __launch_bounds__(256) void attn_decode_multi_k(const uint16_t* __res
     const float a = (part[(0 * TQ + t) * D + d] + part[(1 * TQ + t) * D + d]) + (part[(2 * TQ + t) * D + d] + part[(3 * TQ + t) * D + d]);
     const float sm = (red_sum[0][t] + red_sum[1][t]) + (red_sum[2][t] + red_sum[3][t]);
     const int64_t row = (int64_t)(b * T + t);
-    if (splits == 1) {
+    if (!BEAMS && splits == 1) {
       out[row * HD + (int64_t)h * D + d] = (uint16_t)st16<DT>(sm > 0.f ? a / sm : 0.f);
     } else {
-      float* w = ws + ((row * H + h) * splits + sp) * (D + 2);
+      float* w = ws + ((row * H + h) * wsplits + sp) * (D + 2);
       w[d] = a;
       if (d == 0) {
         w[D] = fmaxf(fmaxf(red_mx[0][t], red_mx[1][t]), fmaxf(red_mx[2][t], red_mx[3][t]));
         w[D + 1] = sm;
       }
     }
+  }
+}
+
+// ---- beam search on a shared prompt cache (generate(num_beams = n, share_prompt_kv = True)) ----------------------------------------------
+// The prompt's K/V rows lie once per prompt where the prefill wrote them (the prefix); a beam owns only the rows of the tokens generated
+// so far (the suffix, [rows, G, H*D]), and which row holds key g of beam m's history is the ancestry table anc [rows, G].
+// HF `_reorder_cache` on the table: anc_out[m, :gen[m]] = anc_in[beam_idx[m], :gen[m]] and anc_out[m, gen[m]] = m (the row the next
+// append writes is the beam's own).  Block per row; gen is read here, never on the host; two buffers that the caller swaps, no atomics.
+__global__ __launch_bounds__(256) void beam_ancestry_k(const int32_t* __restrict__ anc_in, int32_t* __restrict__ anc_out,
+                                                       const int64_t* __restrict__ beam_idx, const int32_t* __restrict__ gen, int rows, int G) {
+  const int m = blockIdx.x;
+  const int n = max(0, min(gen[m], G));
+  const int64_t src = beam_idx[m];
+  if (src >= 0 && src < rows)
+    for (int g = threadIdx.x; g < n; g += 256) anc_out[(int64_t)m * G + g] = anc_in[src * G + g];
+  if (threadIdx.x == 0 && n < G) anc_out[(int64_t)m * G + n] = m;
+}
+
+// The suffix part of mh_attn_decode_beams: attn_decode_k / attn_decode_kv8_k (block per (beam row m, head, key split), the same two
+// passes, LDS use and partial layout) with one indirection - key g of row m is read from suffix row anc[m, g] (its fp8 scale from
+// [anc[m, g], h, g]).  Keys [0, min(slens[m], G)).  Always leaves partials: slot `slot0 + split` of the ws row (m*H + h), wsplits wide.
+template <int DT, int D, bool KV8>
+__global__ __launch_bounds__(256) void attn_decode_beams_suffix_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
+                                                                  const void* __restrict__ vc_, const float* __restrict__ ks,
+                                                                  const float* __restrict__ vs, const int32_t* __restrict__ anc,
+                                                                  const int32_t* __restrict__ slens, int rows, int H, int G,
+                                                                  float scale_log2, int splits, int chunk, float* __restrict__ ws,
+                                                                  int slot0, int wsplits) {
+  extern __shared__ float sc[];  // [chunk] scores, then [NS][D] partial outputs
+  __shared__ float red[8];
+  constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int sp = blockIdx.x % splits;
+  const int h = (blockIdx.x / splits) % H, m = blockIdx.x / (splits * H);
+  const int key0 = sp * chunk;
+  const int len = max(0, min(min(slens[m], G) - key0, chunk));  // keys [key0, key0 + len) of this split
+  const int64_t HD = (int64_t)H * D;
+  const uint8_t* kc = (const uint8_t*)kc_;
+  const uint8_t* vc = (const uint8_t*)vc_;
+  anc += (int64_t)m * G + key0;
+  constexpr int OCT = D / 8, NS = 256 / OCT;  // lanes per row (8 values each), rows per block iteration
+  const int c = tid % OCT, gsl = tid / OCT;
+  constexpr int UNR = 4;
+  float q8[8];
+  unpack8<DT>(*(const uint4*)(q + (int64_t)m * ldq + (int64_t)h * D + c * 8), q8);
+  float mx = -1e30f;
+  for (int j0 = 0; j0 < len; j0 += NS * UNR) {
+    uint4 kraw[UNR];
+    float ksc[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * NS + gsl;
+      const bool ok = j < len;
+      const int r = ok ? min(max(anc[j], 0), rows - 1) : 0;
+      const uint8_t* src = kc + ((((int64_t)r * G + key0 + j) * HD) + (int64_t)h * D + c * 8) * ES;
+      if constexpr (KV8) {
+        const uint2 w = ok ? ld_stream8(src) : make_uint2(0, 0);
+        kraw[u] = make_uint4(w.x, w.y, 0, 0);
+        ksc[u] = ok ? ks[((int64_t)r * H + h) * G + key0 + j] : 0.f;
+      } else {
+        kraw[u] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
+        ksc[u] = 1.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * NS + gsl;
+      float kv[8];
+      if constexpr (KV8) {
+        fp8x4_to_f32(kraw[u].x, kv);
+        fp8x4_to_f32(kraw[u].y, kv + 4);
+      } else {
+        unpack8<DT>(kraw[u], kv);
+      }
+      float s = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s = fmaf(q8[e], kv[e], s);
+#pragma unroll
+      for (int o2 = OCT / 2; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2, 64);
+      if constexpr (KV8) s = s * ksc[u] * scale_log2;
+      else s *= scale_log2;
+      if (j < len) {
+        if (c == 0) sc[j] = s;
+        mx = fmaxf(mx, s);
+      }
+    }
+  }
+  mx = wave_max(mx);
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sum = 0.f;
+  for (int j = tid; j < len; j += 256) {
+    const float pj = fast_exp2(sc[j] - mx);
+    sc[j] = pj;
+    sum += pj;
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) red[4 + wave] = sum;
+  __syncthreads();
+  sum = (red[4] + red[5]) + (red[6] + red[7]);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = 0.f;
+  for (int j0 = gsl; j0 < len; j0 += NS * UNR) {
+    uint4 vraw[UNR];
+    float pj[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = j0 + u * NS;
+      const bool ok = j < len;
+      const int r = ok ? min(max(anc[j], 0), rows - 1) : 0;
+      const uint8_t* src = vc + ((((int64_t)r * G + key0 + j) * HD) + (int64_t)h * D + c * 8) * ES;
+      if constexpr (KV8) {
+        const uint2 w = ok ? ld_stream8(src) : make_uint2(0, 0);
+        vraw[u] = make_uint4(w.x, w.y, 0, 0);
+        pj[u] = ok ? sc[j] * vs[((int64_t)r * H + h) * G + key0 + j] : 0.f;
+      } else {
+        vraw[u] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
+        pj[u] = ok ? sc[j] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float vv[8];
+      if constexpr (KV8) {
+        fp8x4_to_f32(vraw[u].x, vv);
+        fp8x4_to_f32(vraw[u].y, vv + 4);
+      } else {
+        unpack8<DT>(vraw[u], vv);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(pj[u], vv[e], o[e]);
+    }
+  }
+  __syncthreads();  // everyone is done reading the scores: reuse the buffer for the slice partials
+  float* part = sc;  // [NS][D]
+#pragma unroll
+  for (int e = 0; e < 8; ++e) part[gsl * D + c * 8 + e] = o[e];
+  __syncthreads();
+  if (tid < D) {
+    float a = 0.f;
+    for (int g2 = 0; g2 < NS; ++g2) a += part[g2 * D + tid];
+    float* w = ws + ((int64_t)(m * H + h) * wsplits + slot0 + sp) * (D + 2);
+    w[tid] = a;
+    if (tid == 0) { w[D] = mx; w[D + 1] = sum; }
   }
 }
 
@@ -1765,7 +1917,7 @@ static void launch_attn_multi(const void* q, int64_t ldq, const void* kc, const 
   }
   const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
   hipLaunchKernelGGL((attn_decode_multi_k<DT, D, TQ, KV8>), dim3(B * H * splits), dim3(256), lds, st, (const uint16_t*)q, ldq, kc, vc, ks, vs,
-                     (uint16_t*)out, lens, T, H, Smax, scale_log2, splits, chunk, ws);
+                     (uint16_t*)out, lens, T, H, Smax, scale_log2, splits, chunk, ws, splits);
   if (splits > 1)
     hipLaunchKernelGGL((attn_decode_combine_k<DT, D>), dim3(B * T * H), dim3(D), 0, st, (const float*)ws, (uint16_t*)out, H, splits);
 }
@@ -1802,6 +1954,108 @@ extern "C" int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcac
 extern "C" int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale,
                                         void* out, const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream) {
   return attn_multi_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, T, H, D, Smax, ws, dt, stream);
+}
+
+// ---- beam search on a shared prompt cache ------------------------------------------------------------------------------------------------
+extern "C" int mh_beam_ancestry(const int32_t* anc_in, int32_t* anc_out, const int64_t* beam_idx, const int32_t* gen, int rows, int G,
+                                void* stream) {
+  if (!anc_in || !anc_out || anc_in == anc_out || !beam_idx || !gen || rows <= 0 || G <= 0) return MH_ERR_ARG;
+  hipLaunchKernelGGL(beam_ancestry_k, dim3(rows), dim3(256), 0, as_stream(stream), anc_in, anc_out, beam_idx, gen, rows, G);
+  MH_LAUNCH_CHECK();
+}
+
+// key splits of the suffix part: >= 256 generated keys per split, four at the most
+extern "C" int mh_attn_decode_beams_suffix_splits(int G) {
+  if (G <= 0) return 0;
+  const int s = (G + 255) / 256;
+  return s > 4 ? 4 : s;
+}
+
+// key splits of the prefix part: the one-query plan of the Bp prompts, then more until a split's TQ x chunk fp32 scores fit 64 KiB (the rule
+// of mh_attn_decode_multi_splits), within the 32 slots the merge kernel takes less the suffix part's; 0 where even that leaves a block more
+// scores than the 150 KiB it may request
+extern "C" int mh_attn_decode_beams_splits(int Bp, int nb, int H, int Pmax, int G) {
+  if (Bp <= 0 || nb < 1 || nb > 16 || H <= 0 || Pmax <= 0 || G <= 0) return 0;
+  const int most = 32 - mh_attn_decode_beams_suffix_splits(G);
+  int s = mh_attn_decode_splits(Bp, H, Pmax);
+  if (s > most) s = most;
+  const int64_t tq = attn_multi_tq(nb);
+  while (s < most && tq * ((Pmax + s - 1) / s) * 4 > ATTN_MULTI_LDS_AIM) ++s;
+  return tq * ((Pmax + s - 1) / s) * 4 > ATTN_MULTI_LDS_MAX ? 0 : s;
+}
+
+template <int DT, int D, int TQ, bool KV8>
+static void launch_attn_beams(const void* q, int64_t ldq, const void* pk, const void* pv, const float* pks, const float* pvs,
+                              const int32_t* pre_lens, const void* sk, const void* sv, const float* sks, const float* svs, const int32_t* anc,
+                              const int32_t* slens, void* out, int Bp, int nb, int H, int Pmax, int G, int psplits, int ssplits, float* ws,
+                              hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)attn_decode_multi_k<DT, D, TQ, KV8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_MULTI_LDS_MAX);
+    attr = true;
+  }
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  const int rows = Bp * nb, wsplits = psplits + ssplits;
+  const int pchunk = (Pmax + psplits - 1) / psplits, schunk = (G + ssplits - 1) / ssplits;
+  const size_t plds = sizeof(float) * (size_t)TQ * (pchunk > 4 * D ? pchunk : 4 * D);  // scores [chunk][TQ], then the four waves' [TQ][D] partials
+  const int NS = 256 / (D / 8);
+  const size_t slds = sizeof(float) * (size_t)(schunk > NS * D ? schunk : NS * D);
+  hipLaunchKernelGGL((attn_decode_multi_k<DT, D, TQ, KV8, true>), dim3(Bp * H * psplits), dim3(256), plds, st, (const uint16_t*)q, ldq, pk, pv,
+                     pks, pvs, (uint16_t*)out, pre_lens, nb, H, Pmax, scale_log2, psplits, pchunk, ws, wsplits);
+  hipLaunchKernelGGL((attn_decode_beams_suffix_k<DT, D, KV8>), dim3(rows * H * ssplits), dim3(256), slds, st, (const uint16_t*)q, ldq, sk, sv,
+                     sks, svs, anc, slens, rows, H, G, scale_log2, ssplits, schunk, ws, psplits, wsplits);
+  hipLaunchKernelGGL((attn_decode_combine_k<DT, D>), dim3(rows * H), dim3(D), 0, st, (const float*)ws, (uint16_t*)out, H, wsplits);
+}
+
+template <bool KV8>
+static int attn_beams_impl(const void* q, int64_t ldq, const void* pk, const void* pv, const float* pks, const float* pvs,
+                           const int32_t* pre_lens, const void* sk, const void* sv, const float* sks, const float* svs, const int32_t* anc,
+                           const int32_t* slens, void* out, int Bp, int nb, int H, int D, int Pmax, int G, float* ws, int dt, void* stream) {
+  if (!q || !pk || !pv || !pre_lens || !sk || !sv || !anc || !slens || !out || !ws) return MH_ERR_ARG;
+  if (Bp <= 0 || nb < 1 || nb > 16 || H <= 0 || Pmax <= 0 || G <= 0 || (ldq & 7) || !aligned16(q)) return MH_ERR_ARG;
+  if (KV8 && (!pks || !pvs || !sks || !svs || (((uintptr_t)pk | (uintptr_t)pv | (uintptr_t)sk | (uintptr_t)sv) & 7u))) return MH_ERR_ARG;
+  if (!KV8 && (!aligned16(pk) || !aligned16(pv) || !aligned16(sk) || !aligned16(sv))) return MH_ERR_ARG;
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int psplits = mh_attn_decode_beams_splits(Bp, nb, H, Pmax, G), ssplits = mh_attn_decode_beams_suffix_splits(G);
+  if (psplits <= 0) return MH_ERR_SHAPE;
+  const int schunk = (G + ssplits - 1) / ssplits;
+  if ((int64_t)schunk * 4 > ATTN_MULTI_LDS_MAX) return MH_ERR_SHAPE;  // G above 153 600 generated keys
+  if ((int64_t)Bp * nb * H * (psplits + ssplits) > 0x7fffffff / (D + 2)) return MH_ERR_SHAPE;
+  {  // the suffix kernel's LDS beyond the default 64 KiB (G above 65 536)
+    static bool attr = false;
+    if (!attr && (int64_t)schunk * 4 > 64 * 1024) {
+#define GO(DT_, D_) hipFuncSetAttribute((const void*)attn_decode_beams_suffix_k<DT_, D_, KV8>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_MULTI_LDS_MAX)
+      GO(MH_BF16, 128); GO(MH_BF16, 64); GO(MH_F16, 128); GO(MH_F16, 64);
+#undef GO
+      attr = true;
+    }
+  }
+  const int tq = attn_multi_tq(nb);
+  hipStream_t st = as_stream(stream);
+#define GO(DT_, D_, TQ_) \
+  launch_attn_beams<DT_, D_, TQ_, KV8>(q, ldq, pk, pv, pks, pvs, pre_lens, sk, sv, sks, svs, anc, slens, out, Bp, nb, H, Pmax, G, psplits, ssplits, ws, st)
+#define GOT(DT_, D_) do { if (tq == 4) GO(DT_, D_, 4); else if (tq == 8) GO(DT_, D_, 8); else GO(DT_, D_, 16); } while (0)
+  if (dt == MH_BF16) { if (D == 128) GOT(MH_BF16, 128); else GOT(MH_BF16, 64); }
+  else { if (D == 128) GOT(MH_F16, 128); else GOT(MH_F16, 64); }
+#undef GOT
+#undef GO
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_attn_decode_beams(const void* q, int64_t ldq, const void* pre_k, const void* pre_v, const int32_t* pre_lens, const void* suf_k,
+                                    const void* suf_v, const int32_t* anc, const int32_t* slens, void* out, int Bp, int nb, int H, int D,
+                                    int Pmax, int G, float* ws, int dt, void* stream) {
+  return attn_beams_impl<false>(q, ldq, pre_k, pre_v, nullptr, nullptr, pre_lens, suf_k, suf_v, nullptr, nullptr, anc, slens, out, Bp, nb, H, D,
+                                Pmax, G, ws, dt, stream);
+}
+
+extern "C" int mh_attn_decode_beams_kv8(const void* q, int64_t ldq, const void* pre_k8, const void* pre_v8, const float* pre_kscale,
+                                        const float* pre_vscale, const int32_t* pre_lens, const void* suf_k8, const void* suf_v8,
+                                        const float* suf_kscale, const float* suf_vscale, const int32_t* anc, const int32_t* slens, void* out,
+                                        int Bp, int nb, int H, int D, int Pmax, int G, float* ws, int dt, void* stream) {
+  return attn_beams_impl<true>(q, ldq, pre_k8, pre_v8, pre_kscale, pre_vscale, pre_lens, suf_k8, suf_v8, suf_kscale, suf_vscale, anc, slens, out,
+                               Bp, nb, H, D, Pmax, G, ws, dt, stream);
 }
 
 extern "C" int mh_ngram_draft(const int64_t* ids, int64_t ld, int rows, int len, int max_ngram, int k, int max_length, int64_t* out,

@@ -107,7 +107,7 @@ def _resolve_options(generation_config, kw):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, seed=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
@@ -116,7 +116,12 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     fp4_weights=True runs the decode-step projections on MXFP4 copies of the decoder's Linear weights and lm_head (OCP e2m1 values, one
     power-of-two scale per 32 k, engine.quantize_decode_weights_fp4: about 0.53 bytes per weight streamed per token instead of 2; the
     prompt's prefill keeps the 16-bit weights), in every mode and with either cache format; the alternative to fp8_weights, not an
-    addition to it, and it needs use_cache=True (it applies to the decode step)."""
+    addition to it, and it needs use_cache=True (it applies to the decode step).
+    share_prompt_kv=True (beam search only: num_beams > 1) keeps the prompt's keys and values once per prompt, where the prefill wrote
+    them, instead of one copy per beam (engine.BeamKVCache): a beam owns only the rows of its generated tokens, re-ordering the beams
+    rewrites an int32 ancestry table (mh_beam_ancestry) and moves no K/V, and the attention loads every prompt key once for all the beams
+    (mh_attn_decode_beams).  The same search in the same arithmetic up to the order of the attention's partial sums; composes with fp8_kv,
+    fp8_weights and fp4_weights.  The default (False) is the copying path."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
@@ -127,6 +132,10 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         raise ValueError("fp4_weights and fp8_weights are alternatives: pick one weight format for the decode step")
     if fp4_weights and not use_cache:
         raise ValueError("fp4_weights=True applies to the KV-cache decode step: it needs use_cache=True")
+    if share_prompt_kv and num_beams <= 1:
+        raise ValueError("share_prompt_kv=True shares the prompt's KV cache among the beams of beam search: it needs num_beams > 1")
+    if share_prompt_kv and num_beams > 16:
+        raise ValueError("share_prompt_kv=True takes num_beams <= 16 (the beams of a prompt are one query tile of the attention kernel)")
     lookup, max_ngram = o["prompt_lookup_num_tokens"], o["max_matching_ngram_size"]
     if lookup is not None:  # prompt-lookup speculative decoding: refused before any device work where it does not apply
         if num_beams > 1:
@@ -156,7 +165,8 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise ValueError("`streamer` cannot be used with beam search. Make sure that `num_beams` is set to 1.")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
-        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights)
+        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights,
+                            share_prompt_kv=bool(share_prompt_kv))
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
     if streamer is not None:
         streamer.put(input_ids.cpu())
@@ -380,21 +390,27 @@ def _gather_beams(t, idx):
     return torch.gather(t, 1, idx.expand(-1, -1, *t.shape[2:]))
 
 
-def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False):
+def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False,
+                 share_prompt_kv=False):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
-    re-ordered by the surviving beams' parents (HF `_reorder_cache`) with one gather kernel per layer."""
+    re-ordered by the surviving beams' parents (HF `_reorder_cache`) with one gather kernel per layer.
+    share_prompt_kv: the prefilled cache stays the one copy of the prompt's K/V (engine.share_cache) and the re-ordering is a table step."""
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
-    logits0, cache0 = eng.prefill(input_ids, None, images, max_new, kv_fp8=fp8_kv)
+    # (the shared prompt cache appends to the beams' own rows: its prefill gets no spare rows, so the prefix holds the prompt and nothing else)
+    logits0, cache0 = eng.prefill(input_ids, None, images, 0 if share_prompt_kv else max_new, kv_fp8=fp8_kv)
     dev = logits0.device
     ids = input_ids.to(dev)
     expand = torch.arange(B, device=dev).repeat_interleave(nb)
-    cache = eng.expand_cache(cache0, expand)
-    del cache0
+    if share_prompt_kv:
+        cache = eng.share_cache(cache0, nb, max_new)  # cache0 lives on inside it: it is the prefix
+    else:
+        cache = eng.expand_cache(cache0, expand)
+        del cache0
     logits = torch.empty(B * nb, logits0.shape[1], dtype=torch.float32, device=dev)
     O.gather_rows2d(logits0, expand, logits)
 
@@ -448,7 +464,10 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
         go_on = bool(unsat.any()) and not (bool(finished.all()) and early_stopping is True) and not bool(hits.all())
         if not go_on:
             break
-        eng.reorder_cache(cache, beam_idx, cur - 1)
+        if share_prompt_kv:
+            cache.reorder(beam_idx)
+        else:
+            eng.reorder_cache(cache, beam_idx, cur - 1)
         logits = eng.decode_step(running[:, :, cur - 1].reshape(-1).contiguous(), cache, fp8=fp8_weights, fp4=fp4_weights)
     out_len = P + int(seq_len[:, 0].max())
     return sequences[:, 0, :out_len].to(input_ids.device)

@@ -1261,6 +1261,82 @@ class HipEngine:
             if self.rpos is not None:
                 self.rpos.add_(n)
 
+    class BeamKVCache:
+        """Beam search on a shared prompt cache (generate(num_beams=n, share_prompt_kv=True); include/merlin_hip.h "beam search on a shared
+        prompt cache").  prefix: the prefilled KVCache of the Bp prompts itself - its tensors are used where they lie, never copied;
+        pre_lens = prefix.lens.  Suffix: per-layer k, v [Bp*nb, G, H*D] (fp8: + ks, vs [Bp*nb, H, G]) in the prefix's dtype and layout, one
+        row per generated token and beam.  gen int32 [Bp*nb]: suffix rows written (the append kernels' pos); apos = rotary position of
+        the next token (their rope_pos); anc int32 [Bp*nb, G]: anc[m, g] is the suffix row that holds key / value g of beam m's history.
+        Everything a step reads lives on the device."""
+
+        def __init__(self, prefix, nb, G):
+            Bp, dev = prefix.B, prefix.lens.device
+            self.prefix, self.nb, self.Bp, self.G = prefix, int(nb), Bp, int(G)
+            self.fp8, self.H = prefix.fp8, prefix.H
+            self.B = n = Bp * self.nb
+            self.pre_lens = prefix.lens
+            d = prefix.k[0].shape[-1]
+            self.k = [torch.zeros(n, G, d, dtype=t.dtype, device=dev) for t in prefix.k]
+            self.v = [torch.zeros(n, G, d, dtype=t.dtype, device=dev) for t in prefix.v]
+            if self.fp8:
+                self.ks = [torch.zeros(n, self.H, G, dtype=torch.float32, device=dev) for _ in prefix.ks]
+                self.vs = [torch.zeros(n, self.H, G, dtype=torch.float32, device=dev) for _ in prefix.vs]
+            self.gen = torch.zeros(n, dtype=torch.int32, device=dev)
+            base = prefix.rpos if prefix.rpos is not None else prefix.lens
+            self.apos = base.repeat_interleave(self.nb).contiguous()
+            # every column of a row starts as the row itself: a beam that is never re-ordered reads its own rows
+            self.anc = torch.arange(n, dtype=torch.int32, device=dev)[:, None].repeat(1, G).contiguous()
+            self._anc_alt = self.anc.clone()
+
+        def layer(self, li):
+            """The suffix tensors of layer li: (k, v), or (k8, v8, ks, vs) of the fp8 cache."""
+            return (self.k[li], self.v[li], self.ks[li], self.vs[li]) if self.fp8 else (self.k[li], self.v[li])
+
+        def sets(self):
+            """The per-layer suffix tensor lists: k, v, and the scales ks, vs of the fp8 cache."""
+            return [self.k, self.v, self.ks, self.vs] if self.fp8 else [self.k, self.v]
+
+        @property
+        def nbytes(self):
+            """Resident K/V bytes: the prefix once plus the suffix rows (the two ancestry tables, 8 G bytes per beam, are not K/V)."""
+            return self.prefix.nbytes + sum(t.numel() * t.element_size() for lst in self.sets() for t in lst)
+
+        def reorder(self, beam_idx):
+            """HF `_reorder_cache`: beam m continues beam beam_idx[m] (int64 [Bp*nb] on the device, in-group).  One table kernel
+            (mh_beam_ancestry); no key or value moves."""
+            O.beam_ancestry(self.anc, self._anc_alt, beam_idx, self.gen)
+            self.anc, self._anc_alt = self._anc_alt, self.anc
+
+        def materialize(self):
+            """An ordinary KVCache of Bp*nb rows and Smax = Pmax + G: row m holds its prompt's prefix followed by its ancestry's suffix
+            rows.  For tests and debugging only (host loops, copies everything); not on the decode path."""
+            pre, n, G = self.prefix, self.B, self.G
+            d = pre.k[0].shape[-1]
+            out = HipEngine.KVCache(len(pre.k), n, pre.Smax + G, d, pre.k[0].dtype, pre.lens.device, fp8=self.fp8, H=self.H)
+            gen, pl, anc = self.gen.tolist(), pre.lens.tolist(), self.anc.long()
+            for m in range(n):
+                p, g, at = m // self.nb, gen[m], pl[m // self.nb]
+                col = torch.arange(g, device=anc.device)
+                for src_pre, src_suf, dst in zip(pre.sets()[:2], self.sets()[:2], out.sets()[:2]):
+                    for li in range(len(dst)):
+                        dst[li][m, :at] = src_pre[li][p, :at]
+                        dst[li][m, at:at + g] = src_suf[li][anc[m, :g], col]
+                for src_pre, src_suf, dst in zip(pre.sets()[2:], self.sets()[2:], out.sets()[2:]):
+                    for li in range(len(dst)):
+                        dst[li][m, :, :at] = src_pre[li][p, :, :at]
+                        dst[li][m, :, at:at + g] = src_suf[li][anc[m, :g], :, col].t()
+            out.lens = (pre.lens.repeat_interleave(self.nb) + self.gen).contiguous()
+            out.rpos = (self.apos.clone() if pre.rpos is not None else None)
+            return out
+
+    def share_cache(self, cache, num_beams, max_new):
+        """BeamKVCache on the prefilled `cache` of Bp prompts: num_beams beams per prompt, room for max_new generated tokens each.  The
+        prompt's K/V are not copied (expand_cache is the copying form)."""
+        if not 1 <= num_beams <= 16 or max_new < 1:
+            raise ValueError(f"share_cache takes 1 <= num_beams <= 16 (the attention kernel's query tile) and max_new >= 1, got {num_beams}, {max_new}")
+        self._rope_table(cache.Smax + max_new, cache.lens.device)  # the prefill may have been given no room to append (its rows stay the prompt's)
+        return HipEngine.BeamKVCache(cache, num_beams, max_new)
+
     def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False):
         """Full forward over the prompt that also fills a KV cache; returns (logits fp32 [B, V] at each sequence's last
         valid position, cache).  Right-padded prompts (attention_mask) decode from their own length.
@@ -1356,6 +1432,10 @@ class HipEngine:
         (one of the two).  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its own kernels (mh_decode_rope_append_kv8,
         mh_attn_decode_kv8), with any weight format."""
         logits = self._decode_rows(tokens, cache, fp8, fp4, 0)
+        if isinstance(cache, HipEngine.BeamKVCache):  # (a shared prompt cache: tokens [Bp*nb]; the prefix does not grow)
+            cache.gen.add_(1)
+            cache.apos.add_(1)
+            return logits
         cache.lens.add_(1)  # in place (after every kernel that read it as `pos`): the captured graph sees the same buffer
         if cache.rpos is not None:
             cache.rpos.add_(1)
@@ -1393,8 +1473,13 @@ class HipEngine:
             layers = [(W.wqkv, W.wo, W.wgu, W.wd) for W in self.llama]
         emb = A.view("model.embed_tokens.weight", shape=(V, d))
         x = O.gather_rows(emb, tokens.to(A.flat.device).view(-1))
-        pos = cache.lens
+        beams = isinstance(cache, HipEngine.BeamKVCache)
+        if beams and T:
+            raise ValueError("verify_step takes a KVCache: a BeamKVCache decodes one token per beam (decode_step)")
+        # a shared prompt cache appends to the beams' suffix rows (row gen, rotary position apos) and attends prefix + suffix
+        pos, rpos = (cache.gen, cache.apos) if beams else (cache.lens, cache.rpos)
         lens1 = pos + 1
+        pre = cache.prefix if beams else None
         for li, (wqkv, wo, wgu, wd) in enumerate(layers):
             W = self.llama[li]
             if T:  # several positions per sequence: the projection, then RoPE + append and attention over the T rows of a sequence
@@ -1407,12 +1492,18 @@ class HipEngine:
                     o = O.attn_decode_multi(qkv[:, :d], cache.k[li], cache.v[li], lens1, T, H, D)
             elif cache.fp8:  # fp8 KV cache: the projection, then RoPE + quantised append as a launch of its own
                 qkv = gemv_norm(x, W.ln1, eps, wqkv)
-                O.decode_rope_append_kv8(qkv, self.rope, pos, *cache.layer(li), H, D, rope_pos=cache.rpos)
-                o = O.attn_decode_kv8(qkv[:, :d], *cache.layer(li), lens1, H, D)
+                O.decode_rope_append_kv8(qkv, self.rope, pos, *cache.layer(li), H, D, rope_pos=rpos)
+                if beams:
+                    o = O.attn_decode_beams_kv8(qkv[:, :d], *pre.layer(li), pre.lens, *cache.layer(li), cache.anc, lens1, cache.nb, H, D)
+                else:
+                    o = O.attn_decode_kv8(qkv[:, :d], *cache.layer(li), lens1, H, D)
             else:
                 # input_layernorm + q|k|v projection + RoPE + K/V append: one launch
-                qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=cache.rpos)
-                o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
+                qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=rpos)
+                if beams:
+                    o = O.attn_decode_beams(qkv[:, :d], pre.k[li], pre.v[li], pre.lens, cache.k[li], cache.v[li], cache.anc, lens1, cache.nb, H, D)
+                else:
+                    o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
             x2 = gemv(o, wo, resid=x)
             act = gemv_norm(x2, W.ln2, eps, wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
             x = gemv(act, wd, resid=x2)

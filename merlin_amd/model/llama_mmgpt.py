@@ -268,6 +268,7 @@ class MMGPTLlamaForCausalLM(nn.Module):
         the cross-check), use_graph (decode step as one HIP graph), fp8_weights (fp8 weight copies for the decode GEMVs),
         fp4_weights (MXFP4 copies instead: e2m1 values + one power-of-two scale per 32 k, about a quarter of the 16-bit bytes; needs use_cache),
         fp8_kv (KV cache stored as e4m3 bytes + power-of-two scales: about half the cache bytes; needs use_cache),
+        share_prompt_kv (beam search only: the prompt's K/V once per prompt instead of once per beam, beams re-ordered through a table),
         seed (counter-based sampling stream; default drawn from torch's global generator)."""
         from ..generation import generate as _generate
 

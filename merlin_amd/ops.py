@@ -444,6 +444,60 @@ def attn_decode_multi_kv8(q, k8, v8, kscale, vscale, lens, T, H, D, out=None, sp
     return out
 
 
+def beam_ancestry(anc_in, anc_out, beam_idx, gen):
+    """The table step of HF `_reorder_cache` on a shared prompt cache (mh_beam_ancestry): anc_out[m, :gen[m]] = anc_in[beam_idx[m], :gen[m]],
+    anc_out[m, gen[m]] = m; anc int32 [rows, G] (two buffers), beam_idx int64 [rows], gen int32 [rows], all on the device."""
+    rows, G = anc_in.shape
+    assert anc_in.dtype == anc_out.dtype == gen.dtype == torch.int32 and beam_idx.dtype == torch.int64
+    assert anc_out.shape == (rows, G) and beam_idx.shape == gen.shape == (rows,)
+    assert anc_in.is_contiguous() and anc_out.is_contiguous() and beam_idx.is_contiguous() and gen.is_contiguous()
+    L.call("mh_beam_ancestry", anc_in, anc_out, beam_idx, gen, rows, G, _stream())
+
+
+def attn_decode_beams_splits(Bp, nb, H, Pmax, G):
+    """(prefix key splits, suffix key splits) of attn_decode_beams / _kv8 (mh_attn_decode_beams_splits, mh_attn_decode_beams_suffix_splits);
+    0 prefix splits: no plan within the merge kernel's 32 slots and a block's LDS (the call is refused)."""
+    return int(L.lib().mh_attn_decode_beams_splits(Bp, nb, H, Pmax, G)), int(L.lib().mh_attn_decode_beams_suffix_splits(G))
+
+
+def _beams_ws(q, Bp, nb, H, D, Pmax, G):
+    ps, ss = attn_decode_beams_splits(Bp, nb, H, Pmax, G)
+    return torch.empty(Bp * nb * H * (max(ps, 1) + ss) * (D + 2), dtype=torch.float32, device=q.device)
+
+
+def attn_decode_beams(q, pre_k, pre_v, pre_lens, suf_k, suf_v, anc, slens, nb, H, D, out=None):
+    """Beam-search decode attention on a shared prompt cache: q [Bp*nb, H*D] view (row p*nb + i) against the prompt's keys pre_k / pre_v
+    [Bp, Pmax, H*D] (rows < pre_lens[p], loaded once for all nb beams) and the beams' own suf_k / suf_v [Bp*nb, G, H*D], where key g < slens[m]
+    of row m lies in row anc[m, g] (int32 [Bp*nb, G])."""
+    Bp, Pmax = pre_k.shape[:2]
+    rows, G = anc.shape
+    assert rows == Bp * nb and q.shape == (rows, H * D) and q.stride(1) == 1 and pre_k.shape == pre_v.shape == (Bp, Pmax, H * D)
+    assert suf_k.shape == suf_v.shape == (rows, G, H * D) and pre_k.dtype == suf_k.dtype == q.dtype
+    assert all(t.is_contiguous() for t in (pre_k, pre_v, suf_k, suf_v, anc, pre_lens, slens))
+    assert anc.dtype == pre_lens.dtype == slens.dtype == torch.int32 and pre_lens.shape == (Bp,) and slens.shape == (rows,)
+    out = torch.empty(rows, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    L.call("mh_attn_decode_beams", q, q.stride(0), pre_k, pre_v, pre_lens, suf_k, suf_v, anc, slens, out, Bp, nb, H, D, Pmax, G,
+           _beams_ws(q, Bp, nb, H, D, Pmax, G), dt_of(q), _stream())
+    return out
+
+
+def attn_decode_beams_kv8(q, pre_k8, pre_v8, pre_ks, pre_vs, pre_lens, suf_k8, suf_v8, suf_ks, suf_vs, anc, slens, nb, H, D, out=None):
+    """attn_decode_beams on the fp8 KV cache: uint8 rows as above with fp32 scales pre_ks / pre_vs [Bp, H, Pmax], suf_ks / suf_vs [Bp*nb, H, G]
+    (the scale of key g of row m is read at [anc[m, g], h, g])."""
+    Bp, Pmax = pre_k8.shape[:2]
+    rows, G = anc.shape
+    assert rows == Bp * nb and q.shape == (rows, H * D) and q.stride(1) == 1 and pre_k8.shape == pre_v8.shape == (Bp, Pmax, H * D)
+    assert suf_k8.shape == suf_v8.shape == (rows, G, H * D) and pre_k8.dtype == pre_v8.dtype == suf_k8.dtype == suf_v8.dtype == torch.uint8
+    assert pre_ks.shape == pre_vs.shape == (Bp, H, Pmax) and suf_ks.shape == suf_vs.shape == (rows, H, G)
+    assert pre_ks.dtype == pre_vs.dtype == suf_ks.dtype == suf_vs.dtype == torch.float32
+    assert all(t.is_contiguous() for t in (pre_k8, pre_v8, pre_ks, pre_vs, suf_k8, suf_v8, suf_ks, suf_vs, anc, pre_lens, slens))
+    assert anc.dtype == pre_lens.dtype == slens.dtype == torch.int32 and pre_lens.shape == (Bp,) and slens.shape == (rows,)
+    out = torch.empty(rows, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    L.call("mh_attn_decode_beams_kv8", q, q.stride(0), pre_k8, pre_v8, pre_ks, pre_vs, pre_lens, suf_k8, suf_v8, suf_ks, suf_vs, anc, slens, out,
+           Bp, nb, H, D, Pmax, G, _beams_ws(q, Bp, nb, H, D, Pmax, G), dt_of(q), _stream())
+    return out
+
+
 def ngram_draft(ids, length, max_ngram, k, max_length):
     """Prompt-lookup draft on the device (mh_ngram_draft; generation._prompt_lookup is its restatement): ids int64 [rows, >= length] ->
     (draft int64 [rows, k], count int32 [rows]); only the first count[r] entries of a draft row are written."""

@@ -3,7 +3,7 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
@@ -12,7 +12,14 @@ from a HIP graph over the 32 layers' caches in turn so that no launch finds its 
 --verify: the verify arm instead (prompt-lookup speculative decoding): for 16-bit, fp8 and MXFP4 weights, the plain decode step and the
 verify step (engine.verify_step, T rows of one sequence) at T = 2, 4, 8, 16, each replayed from its HIP graph on the same cache, with the
 break-even acceptance t_verify / t_plain - 1 (extra tokens a verify step must yield to pay for itself); then one mh_attn_decode_multi
-launch at T = 8 against eight one-query launches, both from graphs over the 32 layers' caches."""
+launch at T = 8 against eight one-query launches, both from graphs over the 32 layers' caches.
+
+--beams: the beam-search arm instead (num_beams = 5, one prompt, eager steps as generate() runs them): for 16-bit, fp8 and MXFP4 weights, a
+beam step = re-order + decode_step, on the expanded cache (engine.expand_cache + reorder_cache: share_prompt_kv=False, the yardstick) and
+on the shared prompt cache (engine.share_cache + BeamKVCache.reorder: share_prompt_kv=True), same box, same process, same beam_idx per
+step.  Per arm: median ms of the step and of its re-order and decode parts, one attention launch (from a graph over the 32 layers, as
+above), and the resident cache bytes.  --new G (default 24): room for G generated tokens per beam, as max_new_tokens = G gives it; above
+24 the timed steps are the LAST 16 of such a run (G - 20 generated keys are taken as written, whatever they hold)."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -41,6 +48,14 @@ KV = "fp8" if KV8 else "16-bit"
 VERIFY = "--verify" in sys.argv
 if VERIFY:
     sys.argv.remove("--verify")
+BEAMS = "--beams" in sys.argv
+if BEAMS:
+    sys.argv.remove("--beams")
+BEAMS_NEW = 24
+if "--new" in sys.argv:  # --beams: room for this many generated tokens per beam (max_new_tokens); above 24 the steps are timed at its end
+    _i = sys.argv.index("--new")
+    BEAMS_NEW = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 NEW = 160
@@ -109,13 +124,83 @@ def verify_arm(cache):
                           "us_T_single_launches": round(us1, 2), "ratio": round(usm / us1, 3)}), flush=True)
 
 
+def _median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def beams_arm(cache0, cache_s, nb=5, G=BEAMS_NEW, warm=3, steps=13):
+    """Expanded against shared beam steps per weight format (module docstring).  Every step is timed by its own events; medians.
+    cache0: the prompt prefilled with G spare rows (what the copying path expands); cache_s: the same prompt prefilled with none (what
+    generate(share_prompt_kv=True) shares)."""
+    eng = model.engine
+    gen = torch.Generator().manual_seed(1)
+    idx = [torch.randint(0, nb, (nb,), generator=gen).to(dev) for _ in range(warm + steps)]  # in-group (one prompt), duplicates and drops
+    toks = torch.randint(3, 32000, (warm + steps, nb), generator=gen).to(dev)
+    P = int(cache0.lens[0])
+    gen0 = G - 20 if G > 24 else 0  # generated keys taken as already written
+    for name, kw in (("16-bit", dict()), ("fp8", dict(fp8=True)), ("fp4", dict(fp4=True))):
+        for shared in (False, True):
+            if shared:
+                c = eng.share_cache(cache_s, nb, G)
+                c.gen.add_(gen0)
+                c.apos.add_(gen0)
+                reorder = lambda t: c.reorder(idx[t])  # noqa: E731
+            else:
+                c = eng.expand_cache(cache0, torch.zeros(nb, dtype=torch.int64, device=dev))
+                c.lens.add_(gen0)
+                reorder = lambda t: eng.reorder_cache(c, idx[t], P + gen0 + t)  # noqa: E731
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(warm + steps)]
+            for t in range(warm + steps):
+                ev[t][0].record()
+                reorder(t)
+                ev[t][1].record()
+                eng.decode_step(toks[t], c, **kw)
+                ev[t][2].record()
+            torch.cuda.synchronize()
+            ms_r = _median([e[0].elapsed_time(e[1]) for e in ev[warm:]])
+            ms_d = _median([e[1].elapsed_time(e[2]) for e in ev[warm:]])
+            ms = _median([e[0].elapsed_time(e[2]) for e in ev[warm:]])
+            # one attention launch of this arm, from a graph over the 32 layers' caches
+            q = torch.randn(nb, 4096, dtype=torch.bfloat16, device=dev)
+            if shared:
+                sl = c.gen.clone()
+                if KV8:
+                    attn = lambda li: _O.attn_decode_beams_kv8(q, *cache_s.layer(li), cache_s.lens, *c.layer(li), c.anc, sl, nb, 32, 128)  # noqa: E731
+                else:
+                    attn = lambda li: _O.attn_decode_beams(q, *cache_s.layer(li), cache_s.lens, *c.layer(li), c.anc, sl, nb, 32, 128)  # noqa: E731
+                resident = c.nbytes
+            else:
+                ln = c.lens.clone()
+                if KV8:
+                    attn = lambda li: _O.attn_decode_kv8(q, *c.layer(li), ln, 32, 128)  # noqa: E731
+                else:
+                    attn = lambda li: _O.attn_decode(q, c.k[li], c.v[li], ln, 32, 128)  # noqa: E731
+                resident = 2 * c.nbytes  # the second buffer set of reorder_cache (k_alt, v_alt and the scales')
+            attn(0)
+            torch.cuda.synchronize()
+            ga = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(ga):
+                for li in range(32):
+                    attn(li)
+            us = _replay_ms(ga, n=8, warm=2) / 32 * 1e3
+            del ga
+            print(json.dumps({"beams": name + " weights", "kv": KV, "num_beams": nb, "context": P, "max_new": G, "share_prompt_kv": shared, "ms_per_beam_step": round(ms, 3),
+                              "ms_reorder": round(ms_r, 3), "ms_decode_step": round(ms_d, 3), "us_attention_launch": round(us, 2),
+                              "resident_cache_gb": round(resident / 1e9, 3)}), flush=True)
+            del c
+
+
 with torch.no_grad():
     t0 = time.time()
-    logits, cache = model.engine.prefill(ids, None, None, NEW + 8, kv_fp8=KV8)
+    logits, cache = model.engine.prefill(ids, None, None, BEAMS_NEW if BEAMS else NEW + 8, kv_fp8=KV8)
     torch.cuda.synchronize()
     print(f"prefill B={B} S={S}: {(time.time()-t0)*1e3:.1f} ms (first call, incl. arena setup)", flush=True)
     if VERIFY:
         verify_arm(cache)
+        sys.exit(0)
+    if BEAMS:
+        beams_arm(cache, model.engine.prefill(ids, None, None, 0, kv_fp8=KV8)[1])
         sys.exit(0)
     tok = logits.argmax(-1)
     for _ in range(3):
