@@ -411,6 +411,19 @@ int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcache, const v
                          int H, int D, int Smax, float* ws, int dt, void* stream);
 int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                              const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream);
+/* ---- n new query rows per sequence over a kept cache, any n >= 1 (engine.extend: a prompt tail run on a session's KV cache after its
+ * keys and values were appended).  Rows are m = b*n + t; cache layouts are those of mh_attn_decode / _kv8.
+ * mh_attn_extend / _kv8: q rows m (row stride ldq, 16-byte aligned), out [B*n, H*D] (16-byte aligned); query (b, t) attends keys
+ *   [0, min(lens[b] + t, Smax)) - lens[b] is what query 0 sees, its own key included (mh_attn_decode_multi's convention; lens is read on
+ *   the device).  D in {64, 128}.  One block per (b, h, tile of 64 queries) streams 32-key tiles with an online softmax: scores and P.V on
+ *   the matrix pipe (P rounded to the 16-bit type, as in the prefill kernels), fp32 scores, softmax and accumulation; a block loads no
+ *   key at or above its last query's horizon and a wave skips the tiles above its own.  No score buffer, workspace, split plan or merge
+ *   launch, so no limit on Smax.  fp8 form: the key scale multiplies the fp32 score; the value scale is applied once per key where the
+ *   block stages the value tile (exact in the 16-bit type).  No split-KV: a small n on a long cache keeps one wave per (b, h) busy. */
+int mh_attn_extend(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens, int B, int n, int H,
+                   int D, int Smax, int dt, void* stream);
+int mh_attn_extend_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                       const int32_t* lens, int B, int n, int H, int D, int Smax, int dt, void* stream);
 /* ---- beam search on a shared prompt cache (generate(num_beams = nb, share_prompt_kv = True)).  The K/V of a prompt lie ONCE, where the
  * prefill wrote them (the prefix: pre_k / pre_v [Bp, Pmax, H*D], fp8: + pre_kscale / pre_vscale [Bp, H, Pmax]; pre_lens[p] valid rows);
  * beam row m = p*nb + i owns only rows of generated tokens (the suffix: suf_k / suf_v [Bp*nb, G, H*D], fp8: + scales [Bp*nb, H, G], the

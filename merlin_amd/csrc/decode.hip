@@ -26,6 +26,8 @@
 //   mh_decode_rope_append_multi / mh_attn_decode_multi (+ _kv8) / mh_ngram_draft   T <= 16 new tokens of one sequence in one step (the verify
 //                       step of prompt-lookup decoding): append at T consecutive positions, attention with every key / value row loaded once
 //                       for all T queries (scores on the matrix pipe, causality inside the block), and the device-side drafter.
+//   mh_attn_extend (+ _kv8)   any number of new query rows of a sequence over a kept cache (generate(session=...), engine.extend): flash-style,
+//                       64-query tiles, 32-key tiles with an online softmax, scores and P.V on the matrix pipe; no limit on Smax.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include "mh_common.h"
 
@@ -1954,6 +1956,228 @@ extern "C" int mh_attn_decode_multi(const void* q, int64_t ldq, const void* kcac
 extern "C" int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale,
                                         void* out, const int32_t* lens, int B, int T, int H, int D, int Smax, float* ws, int dt, void* stream) {
   return attn_multi_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, T, H, D, Smax, ws, dt, stream);
+}
+
+// ---- n new query rows per sequence over a kept cache (engine.extend: a prompt tail on a session's KV cache) ------------------------------
+// mh_attn_extend / _kv8: q rows m = b*n + t, query t sees keys [0, min(lens[b] + t, Smax)) - mh_attn_decode_multi's convention for any n.
+// Flash-style: block per (b, h, tile of EXT_TQ = 64 queries), wave w owns queries 16 w .. 16 w + 15 of the tile; key tiles of EXT_TK = 32
+// are streamed with an online softmax, so nothing in LDS or in the launch depends on Smax.  Per key tile and wave:
+//   S^T = K Q^T  two 16-key sub-tiles: a lane loads 16 B (fp8 cache: 8 B, converted exactly) of key row (l & 15) straight into the A
+//                operand, the wave's 16 query rows are the B operand (registers, loaded once); lane l holds keys 4 (l >> 4) + r of both
+//                sub-tiles for query l & 15, so max and sum of a query are 8 values in a lane and two shuffles (xor 16, 32).
+//   O^T += V^T P^T  the MFMA's k index is free to be permuted as long as both operands agree: k slot 8 g + e stands for key 4 g + e of
+//                sub-tile 0 (e < 4) and key 4 g + e - 4 of sub-tile 1 (e >= 4), which makes the B operand the lane's own 8 probabilities
+//                (rounded to the 16-bit type like the prefill kernels' P) - no cross-lane movement - and the output tile lands as
+//                (channel 4 g + r, query l & 15): the running max, sum and rescale of a query live in the lanes that hold its outputs.
+//                The A operand is V transposed: the block stages the tile once in LDS as vt[channel][k slot] (a thread loads 16 B of two
+//                consecutive keys and writes 8 dwords, two slots each), and a lane reads one 16-byte row piece per 16-channel block.
+//   LDS banks    a vt row is 32 slots + 8 of padding = 80 B: the 16 lanes of a read phase start at 20-dword steps, which visit all 64
+//                banks once (conflict-free); the staging writes of a wave hit 16 distinct dwords per row and rows 8 channels apart lie 32
+//                banks apart, a 2-way conflict on 8 dword writes per thread and tile (rows must stay 16-byte aligned, so no stride fixes it).
+//   fp8 cache    the key scale multiplies the fp32 score, once per key and query like the neighbours; the value scale is applied once per
+//                key when the tile is staged (e4m3 * 2^e is exact in the 16-bit type), because P is a 16-bit MFMA operand here and
+//                fp16 probabilities cannot carry a 2^-13 scale.
+// Keys at or above the block's last horizon are never loaded (zeros are staged instead); a wave skips the tiles above its own last query's
+// horizon (it still takes part in the staging).  Split-KV is not done: n <= 16 on a long cache runs B * H blocks with one busy wave each.
+constexpr int EXT_TQ = 64, EXT_TK = 32, EXT_VLD = 40;  // queries per block, keys per tile, 16-bit elements per vt row
+
+template <int DT, int D, bool KV8>
+__global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
+                                                     const void* __restrict__ vc_, const float* __restrict__ ks, const float* __restrict__ vs,
+                                                     uint16_t* __restrict__ out, const int32_t* __restrict__ lens, int n, int H, int Smax,
+                                                     int nqt, float scale_log2) {
+  __shared__ __attribute__((aligned(16))) uint16_t vt[D * EXT_VLD];
+  constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
+  constexpr int KK = D / 32;       // MFMA k steps of a score tile
+  constexpr int NDB = D / 16;      // 16-channel output blocks
+  constexpr int OCT = D / 8;       // 8-channel pieces of a value row
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int jq = lane & 15, g = lane >> 4;
+  const int qt = blockIdx.x % nqt, h = (blockIdx.x / nqt) % H, b = blockIdx.x / (nqt * H);
+  const int len0 = max(0, min(lens[b], Smax));
+  const int q0 = qt * EXT_TQ, w0 = q0 + wave * 16;
+  const int kend = min(len0 + min(q0 + EXT_TQ, n) - 1, Smax);         // keys the block's last query sees
+  const int wend = w0 < n ? min(len0 + min(w0 + 16, n) - 1, Smax) : 0;  // keys the wave's last query sees
+  const int t = w0 + jq;                                               // this lane's query
+  const int lim = t < n ? min(len0 + t, Smax) : 0;
+  const int64_t HD = (int64_t)H * D;
+  const uint8_t* kc = (const uint8_t*)kc_ + ((int64_t)b * Smax * HD + (int64_t)h * D) * ES;
+  const uint8_t* vc = (const uint8_t*)vc_ + ((int64_t)b * Smax * HD + (int64_t)h * D) * ES;
+  if constexpr (KV8) {
+    ks += ((int64_t)b * H + h) * Smax;
+    vs += ((int64_t)b * H + h) * Smax;
+  }
+  uint4 qf[KK];
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk)
+    qf[kk] = t < n ? *(const uint4*)(q + ((int64_t)b * n + t) * ldq + (int64_t)h * D + kk * 32 + g * 8) : make_uint4(0, 0, 0, 0);
+  // staging item of this thread: key pair vkp of the tile (keys 2 vkp, 2 vkp + 1), channels 8 vc8 .. 8 vc8 + 7 (D = 64: waves 0 and 1 stage)
+  const int vkp = lane >> 2, vc8 = wave * 4 + (lane & 3);
+  const bool vstage = vc8 < OCT;
+  const int vslot = 8 * ((vkp & 7) >> 1) + 4 * (vkp >> 3) + 2 * (vkp & 1);  // k slot of key 2 vkp; key 2 vkp + 1 is the next slot
+  f32x4_t acc[NDB];
+#pragma unroll
+  for (int db = 0; db < NDB; ++db) acc[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m = -1e30f, l = 0.f;
+  for (int j0 = 0; j0 < kend; j0 += EXT_TK) {
+    uint4 vr[2];
+    float vsc[2] = {1.f, 1.f};
+    if (vstage) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int j = j0 + 2 * vkp + u;
+        const bool ok = j < kend;
+        const uint8_t* src = vc + ((int64_t)j * HD + vc8 * 8) * ES;
+        if constexpr (KV8) {
+          const uint2 r = ok ? *(const uint2*)src : make_uint2(0, 0);
+          vr[u] = make_uint4(r.x, r.y, 0, 0);
+          vsc[u] = ok ? vs[j] : 0.f;
+        } else {
+          vr[u] = ok ? *(const uint4*)src : make_uint4(0, 0, 0, 0);
+        }
+      }
+    }
+    const bool active = j0 < wend;  // (wave-uniform)
+    float alpha = 1.f;
+    uint4 pb = make_uint4(0, 0, 0, 0);
+    if (active) {
+      uint4 kr[2][KK];
+      float ksc[2][4];
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        const int j = j0 + sub * 16 + jq;
+        const bool ok = j < kend;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+          const uint8_t* src = kc + ((int64_t)j * HD + kk * 32 + g * 8) * ES;
+          if constexpr (KV8) {
+            const uint2 r = ok ? *(const uint2*)src : make_uint2(0, 0);
+            kr[sub][kk] = make_uint4(r.x, r.y, 0, 0);
+          } else {
+            kr[sub][kk] = ok ? *(const uint4*)src : make_uint4(0, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          ksc[sub][r] = 1.f;
+          if constexpr (KV8) {
+            const int jr = j0 + sub * 16 + 4 * g + r;
+            ksc[sub][r] = jr < kend ? ks[jr] : 0.f;
+          }
+        }
+      }
+      float s[2][4];
+      float tm = -1e30f;
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+        f32x4_t s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+          uint4 a = kr[sub][kk];
+          if constexpr (KV8) {
+            const uint32_t lo = a.x, hi = a.y;
+            fp8x4_to_pk16<DT>(lo, a.x, a.y);
+            fp8x4_to_pk16<DT>(hi, a.z, a.w);
+          }
+          s4 = mfma16<DT>(a, qf[kk], s4);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[sub][r] = KV8 ? s4[r] * ksc[sub][r] * scale_log2 : s4[r] * scale_log2;
+          if (j0 + sub * 16 + 4 * g + r < lim) tm = fmaxf(tm, s[sub][r]);
+        }
+      }
+      tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
+      tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+      const float mn = fmaxf(m, tm);
+      alpha = fast_exp2(m - mn);  // (nothing seen yet: m = mn = -1e30, alpha = 1 on zeros)
+      m = mn;
+      float p[2][4], psum = 0.f;
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          p[sub][r] = (j0 + sub * 16 + 4 * g + r < lim) ? fast_exp2(s[sub][r] - mn) : 0.f;
+          psum += p[sub][r];
+        }
+      l = fmaf(l, alpha, psum);  // (this lane's four keys per sub-tile; the four lanes of a query are summed at the end)
+      pb = make_uint4(pack2<DT>(p[0][0], p[0][1]), pack2<DT>(p[0][2], p[0][3]), pack2<DT>(p[1][0], p[1][1]), pack2<DT>(p[1][2], p[1][3]));
+    }
+    __syncthreads();  // the previous tile's vt has been read by every wave
+    if (vstage) {
+      uint32_t e0[8], e1[8];  // the 8 channels of key 2 vkp and of key 2 vkp + 1 as 16-bit patterns
+      if constexpr (KV8) {
+        float f0[8], f1[8];
+        fp8x4_to_f32(vr[0].x, f0); fp8x4_to_f32(vr[0].y, f0 + 4);
+        fp8x4_to_f32(vr[1].x, f1); fp8x4_to_f32(vr[1].y, f1 + 4);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          e0[i] = st16<DT>(f0[i] * vsc[0]) & 0xffffu;
+          e1[i] = st16<DT>(f1[i] * vsc[1]) & 0xffffu;
+        }
+      } else {
+        const uint32_t w0_[4] = {vr[0].x, vr[0].y, vr[0].z, vr[0].w}, w1_[4] = {vr[1].x, vr[1].y, vr[1].z, vr[1].w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          e0[i] = (w0_[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+          e1[i] = (w1_[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) *(uint32_t*)(vt + (vc8 * 8 + i) * EXT_VLD + vslot) = e0[i] | (e1[i] << 16);
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int db = 0; db < NDB; ++db) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[db][r] *= alpha;
+        const uint4 a = *(const uint4*)(vt + (db * 16 + jq) * EXT_VLD + g * 8);
+        acc[db] = mfma16<DT>(a, pb, acc[db]);
+      }
+    }
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (t < n) {
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    uint16_t* dst = out + ((int64_t)b * n + t) * HD + (int64_t)h * D + 4 * g;
+#pragma unroll
+    for (int db = 0; db < NDB; ++db)
+      *(uint2*)(dst + db * 16) = make_uint2(pack2<DT>(acc[db][0] * inv, acc[db][1] * inv), pack2<DT>(acc[db][2] * inv, acc[db][3] * inv));
+  }
+}
+
+template <bool KV8>
+static int attn_extend_impl(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                            const int32_t* lens, int B, int n, int H, int D, int Smax, int dt, void* stream) {
+  if (!q || !kc || !vc || !out || !lens || B <= 0 || n < 1 || H <= 0 || Smax <= 0 || (ldq & 7) || !aligned16(q) || !aligned16(out)) return MH_ERR_ARG;
+  if (KV8 && (!ks || !vs || (((uintptr_t)kc | (uintptr_t)vc) & 7u))) return MH_ERR_ARG;  // the fp8 cache is read 8 bytes at a time
+  if (!KV8 && (!aligned16(kc) || !aligned16(vc))) return MH_ERR_ARG;
+  if ((int64_t)Smax + n > 0x7fffffff) return MH_ERR_ARG;  // lens[b] + t is an int
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int nqt = (n + EXT_TQ - 1) / EXT_TQ;
+  if ((int64_t)B * H * nqt > 0x7fffffff) return MH_ERR_SHAPE;
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  const dim3 grid((unsigned)(B * H * nqt)), block(256);
+#define GO(DT_, D_)                                                                                                                    \
+  hipLaunchKernelGGL((attn_extend_k<DT_, D_, KV8>), grid, block, 0, as_stream(stream), (const uint16_t*)q, ldq, kc, vc, ks, vs, (uint16_t*)out, \
+                     lens, n, H, Smax, nqt, scale_log2)
+  if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
+  else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
+#undef GO
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_attn_extend(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens, int B, int n,
+                              int H, int D, int Smax, int dt, void* stream) {
+  return attn_extend_impl<false>(q, ldq, kcache, vcache, nullptr, nullptr, out, lens, B, n, H, D, Smax, dt, stream);
+}
+
+extern "C" int mh_attn_extend_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                                  const int32_t* lens, int B, int n, int H, int D, int Smax, int dt, void* stream) {
+  return attn_extend_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, n, H, D, Smax, dt, stream);
 }
 
 // ---- beam search on a shared prompt cache ------------------------------------------------------------------------------------------------

@@ -57,6 +57,106 @@ class _Stopper:
         return done
 
 
+def _image_spans(ids, im_start, im_end):
+    """[(start, end)] of the image spans in a list of token ids: <im_start> at `start`, its <im_end> at `end - 1`; span i is image i of
+    the prompt.  An <im_start> without an <im_end> behind it opens no span."""
+    spans, open_at = [], None
+    if im_start is None or im_end is None:
+        return spans
+    for i, t in enumerate(ids):
+        if t == im_start:
+            open_at = i
+        elif t == im_end and open_at is not None:
+            spans.append((open_at, i + 1))
+            open_at = None
+    return spans
+
+
+def _reusable_prefix(cached_ids, cached_spans, cached_images, new_ids, new_spans, new_images):
+    """How many leading tokens of the new prompt a session's cache already holds: the longest common token prefix, at most
+    len(new_ids) - 1 (one position must run to give the logits that select the first new token), moved back to the start of an image span
+    it would cut and to the start of the first image span inside it whose pixels differ (torch.equal on shape and values: equal
+    placeholder ids do not mean equal images).  Ids are lists of ints, spans lists of (start, end), images one tensor per span.
+    0: nothing to keep, a plain prefill.  A pure function of host data."""
+    lim = min(len(cached_ids), len(new_ids) - 1)
+    keep = 0
+    while keep < lim and int(cached_ids[keep]) == int(new_ids[keep]):
+        keep += 1
+    for i, (s, e) in enumerate(new_spans):
+        if s >= keep:
+            break
+        if e > keep:  # the prefix ends inside the span
+            return s
+        same = i < len(cached_spans) and tuple(cached_spans[i]) == (s, e) and i < len(cached_images) and i < len(new_images)
+        if same:
+            a, b = cached_images[i], new_images[i]
+            same = a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.to(b.device), b)
+        if not same:
+            return s
+    return max(keep, 0)
+
+
+class Session:
+    """One sequence's KV cache kept between generate() calls (model.new_session(); generate(..., session=s)), and what it holds, on the
+    host: `tokens` (the ids of the cached rows, len(tokens) == cache.lens), `spans` (the image spans among them) and `images` (the tensor
+    each span was encoded from).  A call keeps the longest reusable prefix (_reusable_prefix), truncates the cache to it, grows the cache
+    when the call needs more rows than it has (to a multiple of 256) and runs only the tail: engine.prefill into this cache when nothing is
+    kept, engine.extend otherwise.  `last`: reused_tokens, run_tokens and images_encoded of the last call.  capacity: rows of the cache
+    (default config.max_position_embeddings), allocated at the first call."""
+
+    def __init__(self, model, capacity=None, fp8_kv=False):
+        self.model, self.fp8_kv = model, bool(fp8_kv)
+        self.capacity = int(capacity) if capacity is not None else int(model.config.max_position_embeddings)
+        if self.capacity < 1:
+            raise ValueError(f"new_session(capacity={capacity}): a session needs at least one cache row")
+        self.cache = None
+        self.last = dict(reused_tokens=0, run_tokens=0, images_encoded=0)
+        self.reset()
+
+    def reset(self):
+        """Forget everything: the next call prefills its whole prompt.  The cache's memory is kept."""
+        self.tokens, self.spans, self.images = [], [], []
+        if self.cache is not None:
+            self.cache.truncate(0)
+
+    def _prefill(self, input_ids, images, room):
+        """The session's form of engine.prefill(input_ids, None, images, room): -> (logits fp32 [1, V] at the prompt's last position,
+        the session's cache holding the prompt, with `room` free rows behind it)."""
+        m = self.model
+        eng = m.engine
+        ids = [int(t) for t in input_ids[0].tolist()]
+        new_spans = _image_spans(ids, getattr(m, "im_start_token", None), getattr(m, "im_end_token", None)) if images is not None else []
+        new_images = [im[j] for im in (images or []) for j in range(im.shape[0])]
+        keep = _reusable_prefix(self.tokens, self.spans, self.images, ids, new_spans, new_images)
+        need = len(ids) + int(room)
+        grown = -(-need // 256) * 256  # a call that needs more rows than the session has gets them in whole 256-row steps
+        if self.cache is None or (need > self.cache.Smax and keep == 0):  # (nothing to carry over: no copy)
+            self.cache = eng.new_cache(1, self.capacity if need <= self.capacity else grown, fp8=self.fp8_kv)
+        elif need > self.cache.Smax:
+            self.cache = eng.grow_cache(self.cache, grown)
+        self.capacity = self.cache.Smax
+        self.cache.truncate(keep)
+        kept = sum(1 for _, e in new_spans if e <= keep)  # images whose spans lie in the kept prefix: not encoded again
+        if keep == 0:
+            logits, _ = eng.prefill(input_ids, None, images, 0, kv_fp8=self.fp8_kv, cache=self.cache)
+            encoded = len(new_images)
+        else:
+            tail = new_images[kept:]
+            encoded = len(tail)
+            logits = eng.extend(self.cache, input_ids[:, keep:], [torch.stack(tail)] if tail else None, pos=keep)
+        # (copies: a caller that changes its image tensor in place must not change what the session believes it encoded)
+        self.tokens, self.spans, self.images = ids, new_spans, self.images[:kept] + [x.clone() for x in new_images[kept:len(new_spans)]]
+        self.last = dict(reused_tokens=keep, run_tokens=len(ids) - keep, images_encoded=encoded)
+        return logits, self.cache
+
+    def _fed(self, out):
+        """After a sampling loop: the cache holds the prompt and every generated token that was fed to the decoder, tokens =
+        out[0, :cache.lens] (never more than out holds: a draft accepted beyond a stop is rolled back)."""
+        n = min(int(self.cache.lens[0]), int(out.shape[1]))
+        self.cache.truncate(n)
+        self.tokens = [int(t) for t in out[0, :n].tolist()]
+
+
 def _resolve_lengths(prompt_len, max_new_tokens, max_length):
     if max_new_tokens is not None:
         return prompt_len + int(max_new_tokens)
@@ -107,7 +207,7 @@ def _resolve_options(generation_config, kw):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
@@ -121,7 +221,11 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     them, instead of one copy per beam (engine.BeamKVCache): a beam owns only the rows of its generated tokens, re-ordering the beams
     rewrites an int32 ancestry table (mh_beam_ancestry) and moves no K/V, and the attention loads every prompt key once for all the beams
     (mh_attn_decode_beams).  The same search in the same arithmetic up to the order of the attention's partial sums; composes with fp8_kv,
-    fp8_weights and fp4_weights.  The default (False) is the copying path."""
+    fp8_weights and fp4_weights.  The default (False) is the copying path.
+    session=s (a Session, model.new_session()): the call continues from the KV cache the session kept - the longest prefix of the prompt that
+    the cache already holds (same tokens, same image pixels) is not run again, only the tail is (engine.extend: no tower for images in
+    the prefix) - and leaves what it fed in the session for the next call.  One un-padded prompt per call, use_cache=True, the session's
+    cache format; every mode.  s.last = dict(reused_tokens, run_tokens, images_encoded) of the call.  None: every path as without it."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
@@ -136,6 +240,15 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         raise ValueError("share_prompt_kv=True shares the prompt's KV cache among the beams of beam search: it needs num_beams > 1")
     if share_prompt_kv and num_beams > 16:
         raise ValueError("share_prompt_kv=True takes num_beams <= 16 (the beams of a prompt are one query tile of the attention kernel)")
+    if session is not None:  # a session continues ONE un-padded sequence on its own KV cache: refused before any device work otherwise
+        if input_ids.shape[0] != 1:
+            raise ValueError(f"session: a session holds one sequence, input_ids has batch_size = {input_ids.shape[0]}")
+        if attention_mask is not None and not bool(torch.as_tensor(attention_mask).to(torch.bool).all()):
+            raise ValueError("session: a session takes an un-padded prompt (attention_mask with zeros)")
+        if not use_cache:
+            raise ValueError("session: continuing from a kept KV cache needs use_cache=True")
+        if bool(fp8_kv) != bool(session.fp8_kv):
+            raise ValueError(f"session: fp8_kv={bool(fp8_kv)} but the session's cache was made with fp8_kv={bool(session.fp8_kv)}")
     lookup, max_ngram = o["prompt_lookup_num_tokens"], o["max_matching_ngram_size"]
     if lookup is not None:  # prompt-lookup speculative decoding: refused before any device work where it does not apply
         if num_beams > 1:
@@ -165,22 +278,27 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise ValueError("`streamer` cannot be used with beam search. Make sure that `num_beams` is set to 1.")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
+        skw = {} if session is None else dict(session=session)
         return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights,
-                            share_prompt_kv=bool(share_prompt_kv))
+                            share_prompt_kv=bool(share_prompt_kv), **skw)
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
     if streamer is not None:
         streamer.put(input_ids.cpu())
     stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
     if getattr(model, "engine", None) is not None:
         model.engine.last_generate_stats = stats
+    skw = {} if session is None else dict(session=session)  # (without a session the modes get the arguments they always got)
     if lookup is not None:
         out = _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                             fp4_weights, lookup, max_ngram, stats)
+                             fp4_weights, lookup, max_ngram, stats, **skw)
     elif not use_cache:
         out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer)
     else:
-        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights)
+        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights,
+                             **skw)
         stats["plain_steps"] = max(0, out.shape[1] - input_ids.shape[1] - 1)  # every new token but the first (the prefill's) is one decode step
+    if session is not None:
+        stats.update(session.last)
     if streamer is not None:
         streamer.end()
     return out
@@ -213,12 +331,16 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
             return ids
 
 
-def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False):
+def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False,
+                   session=None):
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
-    logits, cache = eng.prefill(input_ids, attention_mask, images, max_new, kv_fp8=fp8_kv)
+    if session is not None:
+        logits, cache = session._prefill(input_ids, images, max_new)
+    else:
+        logits, cache = eng.prefill(input_ids, attention_mask, images, max_new, kv_fp8=fp8_kv)
     dev = logits.device
     graph = None
     if use_graph and logits.is_cuda and max_new > 2:
@@ -253,6 +375,8 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
             logits = eng.decode_step(nxt, cache, fp8=fp8_weights, fp4=fp4_weights)
     if padded:  # right-padded prompts (an extension; HF wants left padding): each row's continuation starts at its own length
         cur = _compact(ids, lens, torch.stack(new, dim=1), pad)
+    if session is not None:
+        session._fed(cur)  # (the last emitted token was never fed to the decoder: it is not in the cache)
     return cur.to(input_ids.device)
 
 
@@ -295,7 +419,7 @@ def _accept(draft, selected, room, stops):
 
 
 def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                   fp4_weights, k, max_ngram, stats):
+                   fp4_weights, k, max_ngram, stats, session=None):
     """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
     (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
     once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
@@ -305,7 +429,10 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
     V = model.config.vocab_size
     max_new = max_len - P
     T = k + 1
-    logits, cache = eng.prefill(input_ids, attention_mask, images, max_new + k, kv_fp8=fp8_kv)  # k rows of room for a rejected draft's tail
+    if session is not None:
+        logits, cache = session._prefill(input_ids, images, max_new + k)
+    else:
+        logits, cache = eng.prefill(input_ids, attention_mask, images, max_new + k, kv_fp8=fp8_kv)  # k rows of room for a rejected draft's tail
     dev = logits.device
     graph = vgraph = None
     if use_graph and logits.is_cuda and max_new > 2:
@@ -370,6 +497,8 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
     cur = seq[:, :n]
     if padded:
         cur = _compact(seq[:, :P], lens, seq[:, P:n], pad)
+    if session is not None:
+        session._fed(cur)  # (a rejected draft's tail is behind cache.lens: not counted)
     return cur.to(input_ids.device)
 
 
@@ -391,7 +520,7 @@ def _gather_beams(t, idx):
 
 
 def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False,
-                 share_prompt_kv=False):
+                 share_prompt_kv=False, session=None):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
@@ -402,12 +531,17 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
     V = model.config.vocab_size
     max_new = max_len - P
     # (the shared prompt cache appends to the beams' own rows: its prefill gets no spare rows, so the prefix holds the prompt and nothing else)
-    logits0, cache0 = eng.prefill(input_ids, None, images, 0 if share_prompt_kv else max_new, kv_fp8=fp8_kv)
+    if session is not None:  # the session's cache is the prompt cache: read by both paths, written by neither - it keeps the prompt
+        logits0, cache0 = session._prefill(input_ids, images, 0)
+    else:
+        logits0, cache0 = eng.prefill(input_ids, None, images, 0 if share_prompt_kv else max_new, kv_fp8=fp8_kv)
     dev = logits0.device
     ids = input_ids.to(dev)
     expand = torch.arange(B, device=dev).repeat_interleave(nb)
     if share_prompt_kv:
         cache = eng.share_cache(cache0, nb, max_new)  # cache0 lives on inside it: it is the prefix
+    elif session is not None:
+        cache = eng.expand_prefix(cache0, nb, P, P + max_new)  # (P + max_new rows per beam, not the session's capacity)
     else:
         cache = eng.expand_cache(cache0, expand)
         del cache0

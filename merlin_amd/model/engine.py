@@ -1261,6 +1261,15 @@ class HipEngine:
             if self.rpos is not None:
                 self.rpos.add_(n)
 
+        def truncate(self, n):
+            """lens = n for every sequence: roll the cache back to its first n rows (a session that keeps a prefix of what it holds).  The
+            rows behind them are stale and the next prefill / extend / decode step overwrites them, as after a rejected draft."""
+            if not 0 <= int(n) <= self.Smax:
+                raise ValueError(f"truncate({n}): the cache has rows [0, {self.Smax})")
+            if self.rpos is not None:
+                raise ValueError("truncate takes a cache whose rotary positions are its rows (no left padding or holes in the prompt)")
+            self.lens.fill_(int(n))
+
     class BeamKVCache:
         """Beam search on a shared prompt cache (generate(num_beams=n, share_prompt_kv=True); include/merlin_hip.h "beam search on a shared
         prompt cache").  prefix: the prefilled KVCache of the Bp prompts itself - its tensors are used where they lie, never copied;
@@ -1337,18 +1346,25 @@ class HipEngine:
         self._rope_table(cache.Smax + max_new, cache.lens.device)  # the prefill may have been given no room to append (its rows stay the prompt's)
         return HipEngine.BeamKVCache(cache, num_beams, max_new)
 
-    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False):
+    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False, cache=None):
         """Full forward over the prompt that also fills a KV cache; returns (logits fp32 [B, V] at each sequence's last
         valid position, cache).  Right-padded prompts (attention_mask) decode from their own length.
         kv_fp8=True: the cache is stored as e4m3 bytes + power-of-two scales (KVCache fp8=True); the prompt's own attention still runs on
-        the unquantised keys and values, so these logits do not change."""
+        the unquantised keys and values, so these logits do not change.
+        cache: an existing KVCache to fill from row 0 instead of a new one (a session's: generation.Session); it keeps its own format and
+        must have B rows and room for the prompt and max_new_tokens."""
         self.ensure_arena()
         cfg = self.model.config
         B, S = (input_ids.shape if input_ids is not None else inputs_embeds.shape[:2])
         A = self.arena
-        cache = HipEngine.KVCache(len(self.llama), B, S + max_new_tokens, cfg.hidden_size, A.flat.dtype, A.flat.device, fp8=kv_fp8,
-                                  H=cfg.num_attention_heads)
-        self._rope_table(S + max_new_tokens, A.flat.device)
+        if cache is None:
+            cache = HipEngine.KVCache(len(self.llama), B, S + max_new_tokens, cfg.hidden_size, A.flat.dtype, A.flat.device, fp8=kv_fp8,
+                                      H=cfg.num_attention_heads)
+        elif cache.B != B or S + max_new_tokens > cache.Smax:
+            raise ValueError(f"prefill into a cache of {cache.B} x {cache.Smax} rows: the prompt needs {B} x {S + max_new_tokens}")
+        else:
+            cache.rpos = None
+        self._rope_table(max(S + max_new_tokens, cache.Smax), A.flat.device)
         _, logits, ctx = self.forward(input_ids, attention_mask, None, images, inputs_embeds=inputs_embeds, kv_cache=cache,
                                       last_only=True)
         lens = ctx["lens"]
@@ -1360,6 +1376,110 @@ class HipEngine:
         else:
             cache.lens.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=A.flat.device))
         return logits, cache
+
+    def extend(self, cache, input_ids, images=None, pos=None):
+        """n = input_ids.shape[1] new positions of ONE sequence on a plain KVCache that already holds P = cache.lens[0] tokens; returns
+        logits fp32 [1, V] at the last new position and advances the cache by n.  The prefill's path on the tail alone: embedding and
+        image splice of the tail (tower and projector only for `images`, the images whose spans lie in the tail), per layer the prefill's
+        GEMMs with the RoPE epilogue reading the table from row P on (rotary positions P .. P + n - 1), the rotated keys and the values
+        appended to cache rows [P, P + n) (fp8 cache: quantised by mh_kv8_fill on views offset by P), then mh_attn_extend over the cache
+        AFTER the append - the new keys are read as stored, like decode_step and verify_step read them.  Always the 16-bit weights.
+        pos: P when the caller knows it on the host (a session does); None reads cache.lens back."""
+        m = self.model
+        cfg = m.config
+        if not isinstance(cache, HipEngine.KVCache) or cache.B != 1 or cache.rpos is not None:
+            raise ValueError("extend takes a plain KVCache of one sequence whose rotary positions are its rows (B = 1, no left padding or holes)")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1 or input_ids.shape[1] < 1:
+            raise ValueError(f"extend takes input_ids [1, n >= 1], got {tuple(input_ids.shape)}")
+        n = int(input_ids.shape[1])
+        P = int(cache.lens[0]) if pos is None else int(pos)
+        if P < 0 or P + n > cache.Smax:
+            raise ValueError(f"extend: {P} cached + {n} new tokens exceed the cache's {cache.Smax} rows (grow_cache makes a larger one)")
+        A = self.ensure_arena()
+        dev = A.flat.device
+        d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
+        eps = cfg.rms_norm_eps
+        rope = self._rope_table(cache.Smax, dev)[P:]  # row t of the slice is position P + t: the GEMM epilogue's table with S = n
+        ids = input_ids.to(dev).contiguous()
+        tower = getattr(m.get_model(), "vision_tower", None)
+        use_images = tower is not None and images is not None and sum(int(im.shape[0]) for im in images) > 0
+        src = self.validate_and_index(ids, None, None, None, images, use_images)
+        r32 = self.fp32_residual
+        feats = None
+        if use_images:
+            xt, N, Sv = self.tower(images, None)
+            feats, rpi, row0, Pimg = self.projector(xt, N, Sv, None, out_f32=r32)
+            assert (rpi, row0, Pimg) == self._splice_geometry()
+        self._check_errors()
+        emb = A.view("model.embed_tokens.weight", shape=(V, d))
+        splice = O.embed_splice_fwd_f32 if r32 else O.embed_splice_fwd
+        x = splice(ids.view(-1), src.view(-1) if src is not None else None, emb, feats)
+        del feats
+        lens1 = cache.lens + 1  # what the first new query sees: the cached rows and its own key
+        for li, W in enumerate(self.llama):
+            h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
+            qkv = O.gemm_nt_rope(h1, W.wqkv, rope, n, H, D)
+            q, k, v = self._qkv(qkv)
+            if cache.fp8:
+                k8, v8, ks, vs = cache.layer(li)
+                O.kv8_fill(k, k8, ks, 1, n, H, D, row0=P)
+                O.kv8_fill(v, v8, vs, 1, n, H, D, row0=P)
+                o = O.attn_extend_kv8(q, k8, v8, ks, vs, lens1, n, H, D)
+            else:
+                cache.k[li][:, P:P + n].copy_(k.view(1, n, d))
+                cache.v[li][:, P:P + n].copy_(v.view(1, n, d))
+                o = O.attn_extend(q, cache.k[li], cache.v[li], lens1, n, H, D)
+            x = self._stream_add(x, o, W.wo)
+            h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
+            _, act = O.gemm_swiglu_fwd(h2, W.wgu)
+            x = self._stream_add(x, act, W.wd)
+        hn, _ = self._stream_norm(x, A.view("model.norm.weight"), eps, want_x16=False)
+        logits = O.gemv(hn[n - 1:n], self._lm_head_w(), out_f32=True, n=V)
+        cache.lens.add_(n)
+        return logits
+
+    def grow_cache(self, cache, Smax):
+        """A new KVCache of Smax >= cache.Smax rows per sequence holding the rows of `cache` (the scales [B, H, Smax] of the fp8 form
+        included), same format, lengths and positions.  Off the hot path: plain copies, once per growth of a session."""
+        if Smax < cache.Smax:
+            raise ValueError(f"grow_cache({Smax}): the cache already has {cache.Smax} rows")
+        A = self.ensure_arena()
+        old = cache.Smax
+        out = HipEngine.KVCache(len(cache.k), cache.B, int(Smax), cache.k[0].shape[-1], A.flat.dtype, A.flat.device, fp8=cache.fp8, H=cache.H)
+        for li in range(len(cache.k)):
+            out.k[li][:, :old].copy_(cache.k[li])
+            out.v[li][:, :old].copy_(cache.v[li])
+            if cache.fp8:
+                out.ks[li][:, :, :old].copy_(cache.ks[li])
+                out.vs[li][:, :, :old].copy_(cache.vs[li])
+        out.lens.copy_(cache.lens)
+        out.rpos = cache.rpos.clone() if cache.rpos is not None else None
+        self._rope_table(int(Smax), A.flat.device)
+        return out
+
+    def new_cache(self, B, Smax, fp8=False):
+        """An empty KVCache of B sequences and Smax rows in the model's geometry (a session's cache: generation.Session)."""
+        cfg = self.model.config
+        A = self.ensure_arena()
+        self._rope_table(int(Smax), A.flat.device)
+        return HipEngine.KVCache(len(self.llama), int(B), int(Smax), cfg.hidden_size, A.flat.dtype, A.flat.device, fp8=bool(fp8),
+                                 H=cfg.num_attention_heads)
+
+    def expand_prefix(self, cache, nb, P, Smax):
+        """New cache of nb rows and Smax rows per sequence whose every row holds the first P rows of the one-sequence `cache` (beam search
+        from a session's cache, which may be far larger than the prompt: expand_cache would copy all of it per beam).  Once per call,
+        plain copies; `cache` is not written."""
+        if cache.B != 1 or P > min(Smax, cache.Smax):
+            raise ValueError(f"expand_prefix takes a one-sequence cache holding {P} <= {min(Smax, cache.Smax)} rows")
+        out = self.new_cache(nb, Smax, fp8=cache.fp8)
+        for li in range(len(cache.k)):
+            out.k[li][:, :P].copy_(cache.k[li][:, :P].expand(nb, -1, -1))
+            out.v[li][:, :P].copy_(cache.v[li][:, :P].expand(nb, -1, -1))
+            if cache.fp8:
+                out.ks[li][:, :, :P].copy_(cache.ks[li][:, :, :P].expand(nb, -1, -1))
+                out.vs[li][:, :, :P].copy_(cache.vs[li][:, :, :P].expand(nb, -1, -1))
+        out.lens.copy_(cache.lens.expand(nb))
+        return out
 
     def expand_cache(self, cache, rows):
         """New cache whose row i is a copy of `cache` row rows[i] (int64 on the device): a prefilled batch expanded to

@@ -269,10 +269,21 @@ class MMGPTLlamaForCausalLM(nn.Module):
         fp4_weights (MXFP4 copies instead: e2m1 values + one power-of-two scale per 32 k, about a quarter of the 16-bit bytes; needs use_cache),
         fp8_kv (KV cache stored as e4m3 bytes + power-of-two scales: about half the cache bytes; needs use_cache),
         share_prompt_kv (beam search only: the prompt's K/V once per prompt instead of once per beam, beams re-ordered through a table),
-        seed (counter-based sampling stream; default drawn from torch's global generator)."""
+        seed (counter-based sampling stream; default drawn from torch's global generator),
+        session (a Session from new_session(): the call continues from the KV cache the session kept - the prefix of the prompt that the
+        cache already holds, tokens and image pixels alike, is not run again, and the tower encodes only the images behind it; one
+        un-padded prompt per call; for evaluation loops over one image and for multi-turn chat)."""
         from ..generation import generate as _generate
 
         return _generate(self, input_ids, images=images, **kwargs)
+
+    def new_session(self, capacity=None, fp8_kv=False):
+        """A Session for generate(..., session=s): one sequence's KV cache kept between calls (merlin_amd/generation.py).  capacity: cache
+        rows (default config.max_position_embeddings; a call that needs more grows it); fp8_kv: the cache format, which the calls must
+        name too."""
+        from ..generation import Session
+
+        return Session(self, capacity=capacity, fp8_kv=fp8_kv)
 
     # ---- construction helpers ----------------------------------------------------------------------
     @classmethod

@@ -360,11 +360,17 @@ def attn_decode(q, kcache, vcache, lens, H, D, out=None, split_kv=True):
     return out
 
 
-def kv8_fill(x, c8, scales, B, S, H, D):
+def kv8_fill(x, c8, scales, B, S, H, D, row0=0):
     """Prefill of the fp8 KV cache: x [B*S, H*D] (a view with row stride x.stride(0), e.g. the k section of the fused q|k|v buffer) ->
-    e4m3 rows [b, s < S] of c8 (uint8 [B, Smax, H*D]) and their power-of-two scales [b, h, s] (fp32 [B, H, Smax])."""
+    e4m3 rows [b, s < S] of c8 (uint8 [B, Smax, H*D]) and their power-of-two scales [b, h, s] (fp32 [B, H, Smax]).
+    row0: the rows go to [b, row0 + s] instead (extending a kept cache: the same launch on views of c8 and scales offset by row0 rows,
+    with the cache's own Smax as the stride)."""
     assert x.stride(1) == 1 and x.shape == (B * S, H * D) and c8.dtype == torch.uint8 and c8.is_contiguous() and scales.is_contiguous()
     assert scales.shape == (c8.shape[0], H, c8.shape[1]) and scales.dtype == torch.float32
+    assert 0 <= row0 and row0 + S <= c8.shape[1]
+    if row0:
+        L.call("mh_kv8_fill", x, x.stride(0), c8[:, row0:], scales[:, :, row0:], B, S, H, D, c8.shape[1], dt_of(x), _stream())
+        return
     L.call("mh_kv8_fill", x, x.stride(0), c8, scales, B, S, H, D, c8.shape[1], dt_of(x), _stream())
 
 
@@ -441,6 +447,32 @@ def attn_decode_multi_kv8(q, k8, v8, kscale, vscale, lens, T, H, D, out=None, sp
     splits = attn_decode_multi_splits(B, T, H, Smax)
     ws = torch.empty(B * T * H * splits * (D + 2), dtype=torch.float32, device=q.device) if (splits > 1 and split_kv) else None
     L.call("mh_attn_decode_multi_kv8", q, q.stride(0), k8, v8, kscale, vscale, out, lens, B, T, H, D, Smax, ws, dt_of(q), _stream())
+    return out
+
+
+def attn_extend(q, kcache, vcache, lens, n, H, D, out=None):
+    """n new queries per sequence, any n >= 1: q [B*n, H*D] view (row stride ldq, row b*n + t) against the cache [B, Smax, H*D] that
+    already holds their keys; query (b, t) sees keys [0, lens[b] + t).  Flash-style (mh_attn_extend): no workspace, no limit on Smax."""
+    B = lens.shape[0]
+    assert q.shape == (B * n, H * D) and q.stride(1) == 1 and lens.dtype == torch.int32 and kcache.is_contiguous() and vcache.is_contiguous()
+    assert kcache.shape == vcache.shape and kcache.shape[0] == B and kcache.shape[2] == H * D
+    out = torch.empty(B * n, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    assert out.shape == (B * n, H * D) and out.is_contiguous()
+    L.call("mh_attn_extend", q, q.stride(0), kcache, vcache, out, lens, B, n, H, D, kcache.shape[1], dt_of(q), _stream())
+    return out
+
+
+def attn_extend_kv8(q, k8, v8, kscale, vscale, lens, n, H, D, out=None):
+    """attn_extend against the fp8 KV cache (k8, v8 uint8 [B, Smax, H*D]; kscale, vscale fp32 [B, H, Smax])."""
+    B = lens.shape[0]
+    Smax = k8.shape[1]
+    assert q.shape == (B * n, H * D) and q.stride(1) == 1 and lens.dtype == torch.int32
+    assert k8.dtype == v8.dtype == torch.uint8 and k8.shape == v8.shape == (B, Smax, H * D) and k8.is_contiguous() and v8.is_contiguous()
+    assert kscale.dtype == vscale.dtype == torch.float32 and kscale.shape == vscale.shape == (B, H, Smax)
+    assert kscale.is_contiguous() and vscale.is_contiguous()
+    out = torch.empty(B * n, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    assert out.shape == (B * n, H * D) and out.is_contiguous()
+    L.call("mh_attn_extend_kv8", q, q.stride(0), k8, v8, kscale, vscale, out, lens, B, n, H, D, Smax, dt_of(q), _stream())
     return out
 
 

@@ -3,7 +3,7 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
@@ -19,7 +19,13 @@ beam step = re-order + decode_step, on the expanded cache (engine.expand_cache +
 on the shared prompt cache (engine.share_cache + BeamKVCache.reorder: share_prompt_kv=True), same box, same process, same beam_idx per
 step.  Per arm: median ms of the step and of its re-order and decode parts, one attention launch (from a graph over the 32 layers, as
 above), and the resident cache bytes.  --new G (default 24): room for G generated tokens per beam, as max_new_tokens = G gives it; above
-24 the timed steps are the LAST 16 of such a run (G - 20 generated keys are taken as written, whatever they hold)."""
+24 the timed steps are the LAST 16 of such a run (G - 20 generated keys are taken as written, whatever they hold).
+
+--extend: the session arm instead (generate(session=...): continuing a kept KV cache), B = 1, one process per (context, cache format): a
+prompt of one image and text, context + n tokens.  For each n (--n a,b,c; default 32,64,512 at context 613, else 64), in this process:
+the prefill of all context + n tokens with the tower for the image (what a call without a session runs; timed as it is, with its cache
+allocation, and into an existing cache), engine.extend of the last n tokens on a cache that holds the first `context` (image included), and
+one mh_attn_extend launch alone (from a graph over the 32 layers' caches).  Medians of 7 runs after 2 warm-ups, each between two events."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -51,6 +57,14 @@ if VERIFY:
 BEAMS = "--beams" in sys.argv
 if BEAMS:
     sys.argv.remove("--beams")
+EXTEND = "--extend" in sys.argv
+if EXTEND:
+    sys.argv.remove("--extend")
+EXTEND_NS = None
+if "--n" in sys.argv:  # --extend: the tail lengths
+    _i = sys.argv.index("--n")
+    EXTEND_NS = [int(a) for a in sys.argv[_i + 1].split(",")]
+    del sys.argv[_i:_i + 2]
 BEAMS_NEW = 24
 if "--new" in sys.argv:  # --beams: room for this many generated tokens per beam (max_new_tokens); above 24 the steps are timed at its end
     _i = sys.argv.index("--new")
@@ -191,7 +205,64 @@ def beams_arm(cache0, cache_s, nb=5, G=BEAMS_NEW, warm=3, steps=13):
             del c
 
 
+def _median_ms(fn, warm=2, reps=7):
+    out = []
+    for i in range(warm + reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record(); torch.cuda.synchronize()
+        if i >= warm:
+            out.append(a.elapsed_time(b))
+    return _median(out)
+
+
+def extend_arm():
+    """Prefill of context + n tokens against extend of n tokens on a context-token cache, and the attention launch alone (module docstring)."""
+    eng = model.engine
+    P = S
+    span = synth._image_span(576, 32000)
+    if B != 1 or P < 1 + len(span):
+        raise SystemExit("--extend takes B = 1 and a context that holds BOS and one image span (579 tokens)")
+    img = torch.randn(1, 3, 336, 336, generator=g).to(dev)
+    for n in EXTEND_NS or ((32, 64, 512) if P == 613 else (64,)):
+        row = [1] + span + torch.randint(3, 32000, (P + n - 1 - len(span),), generator=g).tolist()
+        ids_t = torch.tensor([row]).to(dev)
+        ms_prefill = _median_ms(lambda: eng.prefill(ids_t, None, [img], 8, kv_fp8=KV8))
+        pre = eng.new_cache(1, P + n + 8, fp8=KV8)
+        ms_prefill_into = _median_ms(lambda: eng.prefill(ids_t, None, [img], 8, kv_fp8=KV8, cache=pre))
+        del pre
+        _, cache = eng.prefill(ids_t[:, :P], None, [img], n + 8, kv_fp8=KV8)
+
+        def run_extend():
+            cache.truncate(P)
+            eng.extend(cache, ids_t[:, P:], None, pos=P)
+
+        ms_extend = _median_ms(run_extend)
+        q = torch.randn(n, 4096, dtype=torch.bfloat16, device=dev)
+        lens1 = torch.full((1,), P + 1, dtype=torch.int32, device=dev)
+        if KV8:
+            attn = lambda li: _O.attn_extend_kv8(q, *cache.layer(li), lens1, n, 32, 128)  # noqa: E731
+        else:
+            attn = lambda li: _O.attn_extend(q, cache.k[li], cache.v[li], lens1, n, 32, 128)  # noqa: E731
+        attn(0)
+        torch.cuda.synchronize()
+        ga = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(ga):
+            for li in range(32):
+                attn(li)
+        us = _replay_ms(ga, n=8, warm=2) / 32 * 1e3
+        del ga, cache
+        print(json.dumps({"extend": "16-bit weights", "kv": KV, "context": P, "n": n, "ms_prefill_context_plus_n": round(ms_prefill, 3),
+                          "ms_prefill_into_existing_cache": round(ms_prefill_into, 3), "ms_extend_n": round(ms_extend, 3),
+                          "prefill_over_extend": round(ms_prefill / ms_extend, 2), "us_attn_extend_launch": round(us, 2)}), flush=True)
+
+
 with torch.no_grad():
+    if EXTEND:
+        extend_arm()
+        sys.exit(0)
     t0 = time.time()
     logits, cache = model.engine.prefill(ids, None, None, BEAMS_NEW if BEAMS else NEW + 8, kv_fp8=KV8)
     torch.cuda.synchronize()
