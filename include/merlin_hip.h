@@ -468,6 +468,28 @@ int mh_ngram_draft(const int64_t* ids, int64_t ld, int rows, int len, int max_ng
  * the same (seed, step, row) always draws the same token); out_u (nullable) receives it.  out int64 [rows]. */
 int mh_select_tokens(const float* logits, int64_t ldl, int rows, int V, int do_sample, float temperature, int top_k, float top_p,
                      uint64_t seed, int64_t step, int64_t* out, float* out_u, void* stream);
+/* mh_select_tokens with two more warpers behind top-p (transformers' order): MinPLogitsWarper (min_p > 0: keep p_i >= min_p * p_max, i.e.
+ * z_i >= z_max + ln(min_p); 0 = off; 0 <= min_p <= 1) and EpsilonLogitsWarper (0 < epsilon_cutoff < 1: drop p_i < epsilon_cutoff, p the
+ * softmax over what the earlier warpers left, the maximum always kept; 0 = off).  At min_p = 0 and epsilon_cutoff = 0 it is
+ * mh_select_tokens: same kernel, same thresholds, same tokens.  Both accept -inf logits (banned tokens, mh_ban_tokens): they carry no mass
+ * and are never selected while the row holds a finite value; greedy on a row of -inf only returns 0. */
+int mh_select_tokens_warp(const float* logits, int64_t ldl, int rows, int V, int do_sample, float temperature, int top_k, float top_p,
+                          float min_p, float epsilon_cutoff, uint64_t seed, int64_t step, int64_t* out, float* out_u, void* stream);
+/* Token bans of generate() (transformers NoRepeatNGram / NoBadWords / SuppressTokens / SuppressTokensAtBegin / MinNewTokensLength
+ * logits processors): -inf into logits fp32 [rows, ldl] (V valid columns) in place, one launch, nothing allocated or read back.
+ * History: ids int64, row r at ids + r * ld_ids (ld_ids = 0: every row reads one sequence), its first len_r = len0 + r * len_step
+ * entries valid (a batch step: len_step = 0; the rows of one verify step over a shared sequence: ld_ids = 0, len_step = 1).
+ * Clauses, each off at count / size 0:
+ *   ngram = n: for every i in [0, len_r - n] with h[i : i + n - 1] == h[len_r - n + 1 : len_r], token h[i + n - 1] (n = 1: every token of h)
+ *   words int64 + word_off int32 [n_words + 1]: word w = words[word_off[w] : word_off[w + 1]) (k >= 1 tokens) bans its last token when
+ *     the history ends with its first k - 1 (k = 1: always; k > 1 and k > len_r: never - transformers skips a word longer than the
+ *     context, also the one of len_r + 1 tokens whose prefix is the whole history)
+ *   always [n_always]: banned;  begin [n_begin]: banned when len_r == begin_index;  eos [n_eos]: banned while len_r < min_total
+ * A target outside [0, V) is skipped (as history it still compares); columns [V, ldl) and every other element are not written.
+ * ids may be NULL when ngram = 0 and n_words = 0. */
+int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int len0, int len_step, int ngram,
+                  const int64_t* words, const int32_t* word_off, int n_words, const int64_t* always, int n_always, const int64_t* begin,
+                  int n_begin, int begin_index, const int64_t* eos, int n_eos, int min_total, void* stream);
 /* out[r, :V] = log_softmax(logits[r, :V]) + row_bias[r] (fp32; row_bias nullable): beam search's accumulated scores
  * log_probs + running_beam_scores (transformers/generation/utils.py `_beam_search`) */
 int mh_log_softmax_rows(const float* logits, int64_t ldl, int rows, int V, float* out, int64_t ldo, const float* row_bias, void* stream);

@@ -2,8 +2,11 @@
 // num_beams=5): the logits processors + samplers HF's GenerationMixin applies to the last-position logits, as HBM/L2-bound
 // row kernels (one 256-thread block per sequence; a row of 32003 fp32 logits is 128 KB and is re-read from L2).
 //
+//   mh_ban_tokens      -inf into the logits the token-level constraints forbid given the sequence so far (no_repeat_ngram_size,
+//                      bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens), in place, from ids resident on the device
 //   mh_select_tokens   argmax (do_sample=0) or temperature -> top-k -> top-p -> multinomial (inverse CDF in index order; the
 //                      uniform comes from a counter-based generator keyed on (seed, step, row): no host RNG traffic, replayable)
+//   mh_select_tokens_warp  the same kernel with two more warpers behind top-p: min_p, then epsilon_cutoff
 //   mh_log_softmax_rows  fp32 log-probabilities for beam search
 //   mh_gather_rows2d   dst[i, :cols] = src[idx[i], :cols], zeros where idx[i] < 0  (KV-cache reorder by beam index, batch expansion,
 //                      unpad / pad of the key-padding attention branch)
@@ -11,8 +14,10 @@
 
 namespace {
 
-// order-preserving map float -> uint32 (larger float <-> larger key); -0.0 sorts below +0.0, NaN keys are never produced
-// because the callers skip non-finite comparisons by construction (logits are finite)
+// order-preserving map float -> uint32 (larger float <-> larger key); -0.0 sorts below +0.0.  -inf (a banned token) maps to
+// 0x007fffff, one below the key of -FLT_MAX (KEY_FINITE): it orders like any other value.  Logits are finite or -inf, so NaN keys are
+// never produced.
+constexpr uint32_t KEY_FINITE = 0x00800000u;  // fkey(-FLT_MAX): the smallest key of a finite value
 __device__ __forceinline__ uint32_t fkey(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -58,10 +63,15 @@ struct BlockRed {
 //   do_sample == 0: out = lowest index of the maximum.
 //   else keep = { z_i >= t_k } (t_k = k-th largest value; ties kept, like HF's TopKLogitsWarper `scores < kth`), then
 //        keep &= { mass of strictly larger kept tokens < top_p } (TopPLogitsWarper: tokens whose ascending cumulative
-//        probability is <= 1 - top_p are removed, at least one is kept), then multinomial over softmax(z | keep).
+//        probability is <= 1 - top_p are removed, at least one is kept), then keep &= { z_i >= max z + ln(min_p) } (MinPLogitsWarper
+//        p_i >= min_p * p_max; min_p <= 0: off), then keep &= { p_i >= eps } with p = softmax(z | keep) (EpsilonLogitsWarper; eps <= 0:
+//        off; the maximum always stays), then multinomial over softmax(z | keep).
+// Logits are finite or -inf (mh_ban_tokens), with at least one finite value per row when sampling.  A -inf has zero mass in every
+// pass (expf(-inf - gm) = 0 for a finite gm) and is never picked: a top-k that asks for more tokens than are finite gets the key of
+// -inf as its threshold, which the KEY_FINITE floor below raises again.  do_sample == 0 on a row of -inf only: 0, like argmax.
 __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__ logits, int64_t ldl, int V, int do_sample,
-                                                       float inv_t, int top_k, float top_p, uint64_t seed, int64_t step,
-                                                       int64_t* __restrict__ out, float* __restrict__ out_u) {
+                                                       float inv_t, int top_k, float top_p, float min_p, float eps, uint64_t seed,
+                                                       int64_t step, int64_t* __restrict__ out, float* __restrict__ out_u) {
   __shared__ float fs[4];
   __shared__ int is[4];
   __shared__ float chunk_sum[256];
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
   const int C = (V + 255) / 256, i0 = tid * C, i1 = min(V, i0 + C);
 
   float m = -INFINITY;
-  int am = 0x7fffffff;
+  int am = i0 < V ? i0 : 0x7fffffff;  // (a chunk of -inf only: its first index, which wins only when the whole row is -inf)
   for (int i = i0; i < i1; ++i) {
     const float z = x[i] * inv_t;
     if (z > m) { m = z; am = i; }
@@ -128,6 +138,22 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
     }
     total = red.sum(total);
   }
+  // ---- min_p: z >= gm + ln(min_p) (independent of the normaliser; min_p <= 1 keeps the maximum)
+  if (min_p > 0.f) {
+    const uint32_t mk = min(fkey(gm + logf(min_p)), fkey(gm));
+    if (mk > kkey) {
+      kkey = mk;
+      total = 0.f;
+      for (int i = i0; i < i1; ++i) {
+        const float z = x[i] * inv_t;
+        if (fkey(z) >= kkey) total += __expf(z - gm);
+      }
+      total = red.sum(total);
+    }
+  }
+  // ---- epsilon: p_i = exp(z_i - gm) / total >= eps  <=>  z_i >= gm + ln(eps * total); the maximum is kept whatever eps
+  if (eps > 0.f) kkey = max(kkey, min(fkey(gm + logf(eps * total)), fkey(gm)));
+  kkey = max(kkey, KEY_FINITE);  // a banned token is never kept (a no-op on finite logits: no key lies below it)
   // ---- multinomial: inverse CDF in index order
   float cs = 0.f;
   for (int i = i0; i < i1; ++i) {
@@ -163,6 +189,48 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
     out[row] = pick >= 0 ? pick : lastk;
     if (out_u) out_u[row] = u;
   }
+}
+
+// One block per row, in place.  Row r conditions on h = ids[r * ld_ids : ][0 : len), len = len0 + r * len_step.  Every clause only
+// writes -inf, so duplicate and racing writes are harmless and the result does not depend on their order.
+//   ngram n > 0:  every window i in [0, len - n] with h[i : i + n - 1] == h[len - n + 1 : len] bans h[i + n - 1]   (n = 1: all of h)
+//   words:        word w (tokens words[off[w] : off[w + 1]), k of them) bans its last token when k = 1, or when k <= len and h ends with its
+//                 first k - 1 (transformers' SequenceBiasLogitsProcessor skips a word longer than the context, k = len + 1 included)
+//   always:       banned;   begin: banned when len == begin_index;   eos: banned while len < min_total
+// A target outside [0, V) is skipped (it still compares as history).
+__global__ __launch_bounds__(256) void ban_tokens_k(float* __restrict__ logits, int64_t ldl, int V, const int64_t* __restrict__ ids,
+                                                    int64_t ld_ids, int len0, int len_step, int ngram, const int64_t* __restrict__ words,
+                                                    const int32_t* __restrict__ word_off, int n_words, const int64_t* __restrict__ always,
+                                                    int n_always, const int64_t* __restrict__ begin, int n_begin, int begin_index,
+                                                    const int64_t* __restrict__ eos, int n_eos, int min_total) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  float* x = logits + (int64_t)row * ldl;
+  const int64_t* h = ids + (int64_t)row * ld_ids;
+  const int len = len0 + row * len_step;
+  auto ban = [&](int64_t t) {
+    if (t >= 0 && t < (int64_t)V) x[t] = -INFINITY;
+  };
+  if (ngram > 0) {
+    const int64_t* tail = h + (len - ngram + 1);  // the last ngram - 1 tokens (read only inside the loop: len >= ngram there)
+    for (int i = tid; i <= len - ngram; i += 256) {
+      bool eq = true;
+      for (int j = 0; j < ngram - 1 && eq; ++j) eq = h[i + j] == tail[j];
+      if (eq) ban(h[i + ngram - 1]);
+    }
+  }
+  for (int w = tid; w < n_words; w += 256) {
+    const int o = word_off[w], k = word_off[w + 1] - o;
+    if (k < 1 || (k > 1 && k > len)) continue;
+    const int64_t* tail = h + (len - (k - 1));
+    bool eq = true;
+    for (int j = 0; j < k - 1 && eq; ++j) eq = tail[j] == words[o + j];
+    if (eq) ban(words[o + k - 1]);
+  }
+  for (int i = tid; i < n_always; i += 256) ban(always[i]);
+  if (len == begin_index)
+    for (int i = tid; i < n_begin; i += 256) ban(begin[i]);
+  if (len < min_total)
+    for (int i = tid; i < n_eos; i += 256) ban(eos[i]);
 }
 
 __global__ __launch_bounds__(256) void log_softmax_rows_k(const float* __restrict__ logits, int64_t ldl, int V, float* __restrict__ out,
@@ -203,7 +271,32 @@ extern "C" int mh_select_tokens(const float* logits, int64_t ldl, int rows, int 
   if (!logits || !out || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
   if (do_sample && (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0)) return MH_ERR_ARG;
   hipLaunchKernelGGL(select_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, do_sample,
-                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, seed, step, out, out_u);
+                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, 0.f, 0.f, seed, step, out, out_u);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_select_tokens_warp(const float* logits, int64_t ldl, int rows, int V, int do_sample, float temperature, int top_k,
+                                     float top_p, float min_p, float epsilon_cutoff, uint64_t seed, int64_t step, int64_t* out,
+                                     float* out_u, void* stream) {
+  if (!logits || !out || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
+  if (do_sample && (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0)) return MH_ERR_ARG;
+  if (do_sample && (!(min_p >= 0.f) || min_p > 1.0f || !(epsilon_cutoff >= 0.f) || !(epsilon_cutoff < 1.0f))) return MH_ERR_ARG;
+  hipLaunchKernelGGL(select_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, do_sample,
+                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, min_p, epsilon_cutoff, seed, step, out, out_u);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int len0, int len_step,
+                             int ngram, const int64_t* words, const int32_t* word_off, int n_words, const int64_t* always, int n_always,
+                             const int64_t* begin, int n_begin, int begin_index, const int64_t* eos, int n_eos, int min_total,
+                             void* stream) {
+  if (!logits || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
+  if (len0 < 0 || len_step < 0 || ld_ids < 0 || ngram < 0 || n_words < 0 || n_always < 0 || n_begin < 0 || n_eos < 0) return MH_ERR_ARG;
+  if ((int64_t)len0 + (int64_t)(rows - 1) * len_step > 0x7fffffff) return MH_ERR_ARG;
+  if ((ngram > 0 || n_words > 0) && !ids) return MH_ERR_ARG;
+  if ((n_words > 0 && (!words || !word_off)) || (n_always > 0 && !always) || (n_begin > 0 && !begin) || (n_eos > 0 && !eos)) return MH_ERR_ARG;
+  hipLaunchKernelGGL(ban_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, ids, ld_ids, len0, len_step, ngram, words,
+                     word_off, n_words, always, n_always, begin, n_begin, begin_index, eos, n_eos, min_total);
   MH_LAUNCH_CHECK();
 }
 

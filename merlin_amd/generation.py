@@ -16,6 +16,14 @@ reference's multimodal beam path needs transformers 4.31's tuple KV cache and ca
 the warper chain = transformers' Temperature/TopK/TopP warpers.  Device work is in kernels (decode step, mh_select_tokens, mh_log_softmax_rows, mh_gather_rows2d);
 what stays here is the control flow HF also keeps on the host (beam bookkeeping on [B, 2*num_beams] tensors, the stopping
 criteria protocol: user criteria are called with (input_ids, scores) every step exactly like StoppingCriteriaList does).
+
+Token-level constraints (transformers' NoRepeatNGram / NoBadWords / SuppressTokens / SuppressTokensAtBegin / MinNewTokensLength logits
+processors: no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens) all write -inf into chosen logits
+given the sequence so far.  They run on the device: the options are resolved once per call into a plan (_ban_plan; its tables are built
+once, _ban_tables), the sequence is kept in one preallocated ids buffer, and every step is ONE mh_ban_tokens launch on the step's logits
+right before the selection (beam search: on log_probs + running scores before the top-k) - no ids come back to the host.  _banned is the
+restatement of the five clauses on a Python list.  Two more warpers, min_p and epsilon_cutoff, are thresholds of the selection kernel
+(mh_select_tokens_warp), behind top-p in transformers' order.  A call with none of these options launches what it launched before them.
 """
 from __future__ import annotations
 
@@ -168,16 +176,17 @@ def _resolve_lengths(prompt_len, max_new_tokens, max_length):
 # decoding options this module implements, with transformers' GenerationConfig defaults
 _DEFAULTS = dict(max_new_tokens=None, max_length=None, eos_token_id=None, pad_token_id=None, do_sample=False, temperature=1.0, top_k=50,
                  top_p=1.0, num_beams=1, length_penalty=1.0, early_stopping=False, use_cache=True, prompt_lookup_num_tokens=None,
-                 max_matching_ngram_size=2)
+                 max_matching_ngram_size=2, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None,
+                 begin_suppress_tokens=None, min_p=None, epsilon_cutoff=0.0)
 # options that are accepted only at the value that leaves the implemented modes unchanged (anything else is a decoding mode the
 # reference's scripts never reach: refuse it instead of silently returning something different)
-_NEUTRAL = dict(repetition_penalty=(1.0, None), no_repeat_ngram_size=(0, None), num_return_sequences=(1, None), num_beam_groups=(1, None),
-                penalty_alpha=(None, 0.0), typical_p=(1.0, None), min_new_tokens=(None, 0), min_length=(0, None), bad_words_ids=(None,),
+_NEUTRAL = dict(repetition_penalty=(1.0, None), num_return_sequences=(1, None), num_beam_groups=(1, None),
+                penalty_alpha=(None, 0.0), typical_p=(1.0, None), min_length=(0, None),
                 return_dict_in_generate=(False, None), output_scores=(False, None), output_logits=(False, None),
                 output_attentions=(False, None), output_hidden_states=(False, None), logits_processor=(None,), prefix_allowed_tokens_fn=(None,),
-                encoder_no_repeat_ngram_size=(0, None), diversity_penalty=(0.0, None), epsilon_cutoff=(0.0, None), eta_cutoff=(0.0, None),
-                min_p=(None,), renormalize_logits=(False, None), forced_bos_token_id=(None,), forced_eos_token_id=(None,),
-                suppress_tokens=(None,), begin_suppress_tokens=(None,), assistant_model=(None,), synced_gpus=(False, None),
+                encoder_no_repeat_ngram_size=(0, None), diversity_penalty=(0.0, None), eta_cutoff=(0.0, None),
+                renormalize_logits=(False, None), forced_bos_token_id=(None,), forced_eos_token_id=(None,), sequence_bias=(None,),
+                assistant_model=(None,), synced_gpus=(False, None),
                 bos_token_id=None, use_beam_search=None, negative_prompt_ids=(None,), num_assistant_tokens=None, trust_remote_code=None)
 
 
@@ -202,7 +211,114 @@ def _resolve_options(generation_config, kw):
                 raise NotImplementedError(f"generate({k}={v!r}) is not part of the decoding modes the reference's eval scripts use")
         else:
             raise TypeError(f"generate() got an unexpected keyword argument '{k}'")
+    _validate_constraints(opt)
     return opt
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _id_list(name, v):
+    """suppress_tokens / begin_suppress_tokens: None or ids >= 0 (a list, a tuple or a tensor) -> list of ints ([]: off)."""
+    v = _as_list(v)
+    if any(not _is_int(t) or t < 0 for t in v):
+        raise ValueError(f"`{name}` has to be a list of integers >= 0, but is {v}")
+    return v
+
+
+def _validate_constraints(opt):
+    """The token-ban and min_p / epsilon options: refused here, before any device work (transformers' messages where its processors have
+    one), and brought to one form - ints, lists of ints, floats; 0 / [] / None: off."""
+    n = opt["no_repeat_ngram_size"]
+    if not _is_int(n) or n < 0:
+        raise ValueError(f"`no_repeat_ngram_size` has to be an integer >= 0, but is {n}")
+    m = opt["min_new_tokens"]
+    if not _is_int(m) or m < 0:
+        raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {m}")
+    words = opt["bad_words_ids"]
+    if words is not None and words != []:
+        if not isinstance(words, list):
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {words}.")
+        if any(not isinstance(w, list) for w in words):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {words}.")
+        if any(len(w) == 0 for w in words):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a non-empty list of positive integers, but is {words}.")
+        if any(not _is_int(t) or t < 0 for w in words for t in w):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {words}.")
+    opt["bad_words_ids"] = [list(w) for w in words] if words else None
+    opt["suppress_tokens"] = _id_list("suppress_tokens", opt["suppress_tokens"]) or None
+    opt["begin_suppress_tokens"] = _id_list("begin_suppress_tokens", opt["begin_suppress_tokens"]) or None
+    mp = opt["min_p"]
+    if mp is not None:
+        if isinstance(mp, bool) or not isinstance(mp, (int, float)) or not 0 <= mp <= 1.0:
+            raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {mp}")
+        opt["min_p"] = float(mp)
+    e = opt["epsilon_cutoff"]
+    if isinstance(e, bool) or not isinstance(e, (int, float)) or not 0 <= e < 1:
+        raise ValueError(f"`epsilon_cutoff` has to be a float > 0 and < 1, but is {e}")
+    opt["epsilon_cutoff"] = float(e)
+
+
+def _pack_words(words):
+    """[[ids of word 0], [ids of word 1], ...] -> (flat token list, offsets [n_words + 1]): word w is flat[off[w] : off[w + 1]]."""
+    flat, off = [], [0]
+    for w in words:
+        flat.extend(int(t) for t in w)
+        off.append(len(flat))
+    return flat, off
+
+
+def _unpack_words(flat, off):
+    return [list(flat[off[w]:off[w + 1]]) for w in range(len(off) - 1)]
+
+
+def _ban_plan(opt, eos_ids):
+    """The token bans of one call, on the host: dict(ngram, words, always, begin, min_new) - words without the ones equal to [eos] (as
+    NoBadWordsLogitsProcessor drops them), min_new 0 when there is no eos id to ban - or None when the call bans nothing."""
+    words = [list(w) for w in (opt["bad_words_ids"] or []) if not any(list(w) == [e] for e in eos_ids)]
+    plan = dict(ngram=int(opt["no_repeat_ngram_size"]), words=words, always=list(opt["suppress_tokens"] or []),
+                begin=list(opt["begin_suppress_tokens"] or []), min_new=int(opt["min_new_tokens"]) if eos_ids else 0)
+    return plan if any(plan.values()) else None
+
+
+def _banned(ids_row, P, plan, eos_ids):
+    """The token ids whose logits get -inf when the sequence so far is ids_row (a list of ints: the call's whole prompt, pads included,
+    then the new tokens) and the prompt had P tokens: the five clauses of mh_ban_tokens, restated (the kernel is tested against this and
+    against transformers' processors)."""
+    h = [int(t) for t in ids_row]
+    L = len(h)
+    out = set()
+    if plan is None:
+        return out
+    n = plan["ngram"]
+    if n > 0:
+        tail = h[L - n + 1:L] if n > 1 else []
+        for i in range(0, L - n + 1):
+            if h[i:i + n - 1] == tail:
+                out.add(h[i + n - 1])
+    for w in plan["words"]:
+        k = len(w)
+        if k == 1 or (k <= L and h[L - (k - 1):] == list(w[:-1])):  # (transformers skips a word longer than the context: k = L + 1 too)
+            out.add(int(w[-1]))
+    out.update(int(t) for t in plan["always"])
+    if L == P:
+        out.update(int(t) for t in plan["begin"])
+    if L - P < plan["min_new"]:
+        out.update(int(e) for e in eos_ids)
+    return out
+
+
+def _ban_tables(plan, eos_ids, P, dev):
+    """The plan's device tables, built once per call: the keyword arguments of ops.ban_tokens that do not change from step to step."""
+    t64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev) if v else None  # noqa: E731
+    kw = dict(ngram=plan["ngram"], always=t64(plan["always"]), begin=t64(plan["begin"]), begin_index=P)
+    if plan["words"]:
+        flat, off = _pack_words(plan["words"])
+        kw.update(words=t64(flat), word_off=torch.tensor(off, dtype=torch.int32, device=dev))
+    if plan["min_new"] > 0:
+        kw.update(eos=t64(list(eos_ids)), min_total=P + plan["min_new"])
+    return kw
 
 
 @torch.no_grad()
@@ -225,7 +341,14 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     session=s (a Session, model.new_session()): the call continues from the KV cache the session kept - the longest prefix of the prompt that
     the cache already holds (same tokens, same image pixels) is not run again, only the tail is (engine.extend: no tower for images in
     the prefix) - and leaves what it fed in the session for the next call.  One un-padded prompt per call, use_cache=True, the session's
-    cache format; every mode.  s.last = dict(reused_tokens, run_tokens, images_encoded) of the call.  None: every path as without it."""
+    cache format; every mode.  s.last = dict(reused_tokens, run_tokens, images_encoded) of the call.  None: every path as without it.
+    Token bans - no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens, with transformers' semantics
+    and order (on the raw scores, before the warpers; in beam search on the log-probabilities, a banned candidate's mass is not
+    renormalised) - are one mh_ban_tokens launch per step on the device (module docstring).  The history they see is the ids tensor the
+    stopping criteria are handed at that step: the call's whole prompt, its pads wherever they sit, then the new tokens - also with a
+    session, however much of the prompt came from its cache.  min_p and epsilon_cutoff (do_sample=True only) follow top-p.  All of these
+    work on the logits alone, so they compose with every mode and with use_graph, use_cache=False, prompt_lookup_num_tokens, fp8_kv,
+    fp8_weights, fp4_weights, share_prompt_kv and sessions without further work."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
@@ -271,6 +394,8 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     if seed is None:  # torch.manual_seed governs the stream, like HF's torch.multinomial
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if do_sample else 0
     stop = _Stopper(max_len, eos_ids, stopping_criteria)
+    plan = _ban_plan(o, eos_ids)
+    bkw = {} if plan is None else dict(bans=(plan, eos_ids))  # (without bans the modes get the arguments they always got)
     if num_beams > 1:
         if do_sample:
             raise NotImplementedError("beam-sample is not one of the reference's decoding modes (eval scripts: num_beams=5, do_sample unset)")
@@ -280,8 +405,10 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
         skw = {} if session is None else dict(session=session)
         return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights,
-                            share_prompt_kv=bool(share_prompt_kv), **skw)
+                            share_prompt_kv=bool(share_prompt_kv), **skw, **bkw)
     sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
+    if do_sample and (o["min_p"] is not None or o["epsilon_cutoff"] > 0.0):
+        sel.update(min_p=o["min_p"], epsilon_cutoff=o["epsilon_cutoff"])
     if streamer is not None:
         streamer.put(input_ids.cpu())
     stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
@@ -290,12 +417,12 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     skw = {} if session is None else dict(session=session)  # (without a session the modes get the arguments they always got)
     if lookup is not None:
         out = _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                             fp4_weights, lookup, max_ngram, stats, **skw)
+                             fp4_weights, lookup, max_ngram, stats, **skw, **bkw)
     elif not use_cache:
-        out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer)
+        out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer, **bkw)
     else:
         out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights,
-                             **skw)
+                             **skw, **bkw)
         stats["plain_steps"] = max(0, out.shape[1] - input_ids.shape[1] - 1)  # every new token but the first (the prefill's) is one decode step
     if session is not None:
         stats.update(session.last)
@@ -305,24 +432,35 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
 
 
 def _select(logits, V, sel, step):
+    extra = {key: sel[key] for key in ("min_p", "epsilon_cutoff") if key in sel}
     return O.select_tokens(logits, V, do_sample=sel["do_sample"], temperature=sel["temperature"], top_k=sel["top_k"], top_p=sel["top_p"],
-                           seed=sel["seed"], step=step)
+                           seed=sel["seed"], step=step, **extra)
 
 
-def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer=None):
+def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer=None, bans=None):
     """use_cache=False: full-sequence forward per token (the cross-check of the cached path)."""
     V = model.config.vocab_size
     unfinished = torch.ones(ids.shape[0], dtype=torch.bool, device=ids.device)
     step = 0
+    P = ids.shape[1]
+    tables = hist = None
     while True:
         out = model.forward(input_ids=ids, attention_mask=attention_mask, images=images)
         logits = out.logits[:, -1, :].float().contiguous()
+        if bans is not None:
+            if tables is None:  # the history lives on the logits' device in one [B, max_len] buffer
+                tables = _ban_tables(bans[0], bans[1], P, logits.device)
+                hist = torch.full((ids.shape[0], max_len), pad, dtype=torch.int64, device=logits.device)
+                hist[:, :P] = ids
+            O.ban_tokens(logits, V, hist, len0=P + step, **tables)
         nxt = _select(logits, V, sel, step).to(ids.device)
         if eos_ids:
             nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
         if streamer is not None:
             streamer.put(nxt.cpu())
         ids = torch.cat([ids, nxt[:, None]], dim=1)
+        if hist is not None and P + step < max_len:
+            hist[:, P + step] = nxt
         if attention_mask is not None:
             attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, :1])], dim=1)
         unfinished = unfinished & ~stop(ids, None)
@@ -332,7 +470,7 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
 
 
 def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False,
-                   session=None):
+                   session=None, bans=None):
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
@@ -356,14 +494,25 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
     lens = am.sum(dim=1) if padded else None
     unfinished = torch.ones(B, dtype=torch.bool, device=dev)
     new = []
+    hist = None
+    if bans is not None:  # the sequence as the criteria see it, kept on the device in one buffer: what mh_ban_tokens reads
+        tables = _ban_tables(bans[0], bans[1], P, dev)
+        hist = torch.full((B, max_len), pad, dtype=torch.int64, device=dev)
+        hist[:, :P] = ids
     for step in range(max_new):
+        if hist is not None:
+            O.ban_tokens(logits, V, hist, len0=P + step, **tables)
         nxt = _select(logits, V, sel, step)
         if eos_ids:
             nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
         new.append(nxt)
         if streamer is not None:
             streamer.put(nxt.cpu())
-        cur = torch.cat([ids, torch.stack(new, dim=1)], dim=1)  # (right-padded prompts: criteria see the pads in the middle)
+        if hist is not None:
+            hist[:, P + step] = nxt
+            cur = hist[:, :P + step + 1]
+        else:
+            cur = torch.cat([ids, torch.stack(new, dim=1)], dim=1)  # (right-padded prompts: criteria see the pads in the middle)
         unfinished = unfinished & ~stop(cur, None)
         if not bool(unfinished.any()) or step + 1 == max_new:
             break
@@ -419,7 +568,7 @@ def _accept(draft, selected, room, stops):
 
 
 def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                   fp4_weights, k, max_ngram, stats, session=None):
+                   fp4_weights, k, max_ngram, stats, session=None, bans=None):
     """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
     (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
     once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
@@ -441,10 +590,12 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
     am = attention_mask.to(dev).to(torch.bool) if attention_mask is not None else None
     padded = am is not None and not bool(am.all()) and cache.rpos is None  # right-padded prompt: as _sample_cached
     lens = am.sum(dim=1) if padded else None
-    seq = torch.full((1, max_len), pad, dtype=torch.int64, device=dev)  # the sequence as the criteria and the drafter see it
+    # the sequence as the criteria and the drafter see it (with bans: k cells more, a draft is written behind it before it is verified)
+    seq = torch.full((1, max_len + (k if bans is not None else 0)), pad, dtype=torch.int64, device=dev)
     seq[:, :P] = input_ids.to(dev)
+    tables = _ban_tables(bans[0], bans[1], P, dev) if bans is not None else None
     n = P  # valid length of seq
-    sel_kw = {key: sel[key] for key in ("do_sample", "temperature", "top_k", "top_p", "seed")}
+    sel_kw = {key: sel[key] for key in ("do_sample", "temperature", "top_k", "top_p", "seed", "min_p", "epsilon_cutoff") if key in sel}
 
     def emit(cand, draft):
         """Append the accepted part of `cand` (selected tokens, on the host) to seq; -> (tokens emitted, accepted, stopped)."""
@@ -461,6 +612,8 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
             streamer.put(torch.tensor([out], dtype=torch.int64))
         return out, a, stopped
 
+    if tables is not None:
+        O.ban_tokens(logits, V, seq, len0=P, **tables)
     first = _select(logits, V, sel, 0)
     out, _, stopped = emit(first.tolist(), [])
     while not stopped and n < max_len:
@@ -476,6 +629,8 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
             else:
                 logits = eng.decode_step(last, cache, fp8=fp8_weights, fp4=fp4_weights)
             stats["plain_steps"] += 1
+            if tables is not None:
+                O.ban_tokens(logits, V, seq, len0=n, **tables)
             out, _, stopped = emit(_select(logits, V, sel, emitted).tolist(), [])
             continue
         toks = v_tok if vgraph is not None else torch.empty(1, T, dtype=torch.int64, device=dev)
@@ -487,6 +642,9 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
             logits = v_logits
         else:
             logits = eng.verify_step(toks, cache, fp8=fp8_weights, fp4=fp4_weights)
+        if tables is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
+            seq[0, n:n + c] = draft_dev[0, :c]
+            O.ban_tokens(logits[0], V, seq, len0=n, len_step=1, ld_ids=0, **tables)
         picked = O.select_tokens_multi(logits, V, step0=emitted, **sel_kw)[:, 0]  # [T]
         both = torch.cat([picked, draft_dev[0]]).tolist()  # one transfer
         out, a, stopped = emit(both[:c + 1], both[T:T + c])
@@ -520,7 +678,7 @@ def _gather_beams(t, idx):
 
 
 def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False,
-                 share_prompt_kv=False, session=None):
+                 share_prompt_kv=False, session=None, bans=None):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
@@ -563,8 +721,11 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
     unsat = torch.ones(B, 1, dtype=torch.bool, device=dev)          # "early-stop heuristic unsatisfied"
     batch_off = (torch.arange(B, device=dev) * nb)[:, None]
     cur = P
+    tables = _ban_tables(bans[0], bans[1], P, dev) if bans is not None else None
     while True:
         acc = O.log_softmax_rows(logits, V, row_bias=running_scores.reshape(-1).contiguous())  # log_probs + running_beam_scores
+        if tables is not None:  # HF: the processors run on log_softmax(logits) of flat_running_sequences; a ban only writes -inf, so after the add
+            O.ban_tokens(acc, V, running.view(B * nb, max_len), len0=cur, **tables)
         top_lp, top_i = torch.topk(acc.view(B, nb * V), k=keep)
         parent = top_i // V
         tok = top_i % V

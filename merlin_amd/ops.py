@@ -541,17 +541,49 @@ def ngram_draft(ids, length, max_ngram, k, max_length):
     return out, cnt
 
 
-def select_tokens_multi(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step0=0):
+def select_tokens_multi(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step0=0, min_p=None, epsilon_cutoff=0.0):
     """logits fp32 [B, T, >=V] -> int64 [T, B]: position t of sequence b is drawn as the plain path draws its token number step0 + t, i.e. with
-    mh_select_tokens' key (seed, step0 + t, row b) - one launch per t on the strided view logits[:, t]."""
+    mh_select_tokens' key (seed, step0 + t, row b) - one launch per t on the strided view logits[:, t].  min_p / epsilon_cutoff: as select_tokens."""
     B, T = logits.shape[:2]
     V = logits.shape[2] if V is None else V
     assert logits.dtype == torch.float32 and logits.stride(2) == 1
     out = torch.empty(T, B, dtype=torch.int64, device=logits.device)
+    warp = min_p is not None or epsilon_cutoff
     for t in range(T):
-        L.call("mh_select_tokens", logits[:, t], logits.stride(0), B, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step0 + t,
-               out[t], None, _stream())
+        if warp:
+            L.call("mh_select_tokens_warp", logits[:, t], logits.stride(0), B, V, int(do_sample), temperature, top_k, top_p, float(min_p or 0.0),
+                   float(epsilon_cutoff or 0.0), seed & 0xFFFFFFFFFFFFFFFF, step0 + t, out[t], None, _stream())
+        else:
+            L.call("mh_select_tokens", logits[:, t], logits.stride(0), B, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step0 + t,
+                   out[t], None, _stream())
     return out
+
+
+def ban_tokens(logits, V=None, ids=None, len0=0, len_step=0, ld_ids=None, ngram=0, words=None, word_off=None, always=None, begin=None, begin_index=-1,
+               eos=None, min_total=0):
+    """-inf into the banned columns of logits fp32 [R, >=V], in place (mh_ban_tokens; generation._banned is its restatement).  ids int64
+    [rows, >= len] is the history, row r's first len0 + r * len_step entries valid; ld_ids=0: every row reads ids[0] (the rows of a verify
+    step).  ngram: no_repeat_ngram_size; words / word_off: flat int64 tokens + int32 offsets [n_words + 1] (generation._pack_words);
+    always / begin / eos: int64 id lists, begin banned when the length is begin_index, eos while it is below min_total.  -> logits."""
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    ld = 0
+    if ids is not None:
+        assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and ids.device == logits.device
+        ld = ids.stride(0) if ld_ids is None else int(ld_ids)
+        assert ld == 0 or (ld == ids.stride(0) and ids.shape[0] >= R)
+        assert 0 <= len0 and 0 <= len_step and len0 + (R - 1) * len_step <= ids.shape[1], (len0, len_step, R, tuple(ids.shape))
+    n_words = 0
+    if words is not None:
+        assert words.dtype == torch.int64 and word_off.dtype == torch.int32 and words.is_contiguous() and word_off.is_contiguous()
+        n_words = word_off.numel() - 1
+    for t in (always, begin, eos):
+        assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.device == logits.device)
+    cnt = lambda t: 0 if t is None else t.numel()  # noqa: E731
+    L.call("mh_ban_tokens", logits, logits.stride(0), R, V, ids, ld, int(len0), int(len_step), int(ngram), words, word_off, n_words, always, cnt(always),
+           begin, cnt(begin), int(begin_index), eos, cnt(eos), int(min_total), _stream())
+    return logits
 
 
 def attn_decode_fused_merge(on: bool):
@@ -1174,15 +1206,20 @@ def copy2d(src, dst, accumulate=False):
     return dst
 
 
-def select_tokens(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, return_u=False):
+def select_tokens(logits, V=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, return_u=False, min_p=None, epsilon_cutoff=0.0):
     """logits fp32 [R, >=V] -> next token ids int64 [R]: greedy argmax, or temperature / top-k / top-p multinomial with a
-    counter-based uniform per (seed, step, row) (include/merlin_hip.h: mh_select_tokens)."""
+    counter-based uniform per (seed, step, row) (include/merlin_hip.h: mh_select_tokens).  min_p (not None) / epsilon_cutoff (not 0): the two
+    warpers behind top-p (mh_select_tokens_warp); at their defaults the launch is mh_select_tokens."""
     R = logits.shape[0]
     V = logits.shape[1] if V is None else V
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
     out = torch.empty(R, dtype=torch.int64, device=logits.device)
     u = torch.empty(R, dtype=torch.float32, device=logits.device) if return_u else None
-    L.call("mh_select_tokens", logits, logits.stride(0), R, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step, out, u, _stream())
+    if min_p is not None or epsilon_cutoff:
+        L.call("mh_select_tokens_warp", logits, logits.stride(0), R, V, int(do_sample), temperature, top_k, top_p, float(min_p or 0.0),
+               float(epsilon_cutoff or 0.0), seed & 0xFFFFFFFFFFFFFFFF, step, out, u, _stream())
+    else:
+        L.call("mh_select_tokens", logits, logits.stride(0), R, V, int(do_sample), temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF, step, out, u, _stream())
     return (out, u) if return_u else out
 
 

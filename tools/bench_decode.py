@@ -3,7 +3,7 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend | --bans]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
@@ -25,7 +25,13 @@ above), and the resident cache bytes.  --new G (default 24): room for G generate
 prompt of one image and text, context + n tokens.  For each n (--n a,b,c; default 32,64,512 at context 613, else 64), in this process:
 the prefill of all context + n tokens with the tower for the image (what a call without a session runs; timed as it is, with its cache
 allocation, and into an existing cache), engine.extend of the last n tokens on a cache that holds the first `context` (image included), and
-one mh_attn_extend launch alone (from a graph over the 32 layers' caches).  Medians of 7 runs after 2 warm-ups, each between two events."""
+one mh_attn_extend launch alone (from a graph over the 32 layers' caches).  Medians of 7 runs after 2 warm-ups, each between two events.
+
+--bans: the token-ban arm instead (generate(no_repeat_ngram_size=3, bad_words_ids=<64 words>, min_new_tokens=...)), B = 1: the graph decode
+step + the selection as generate() runs them per token (graph replay, mh_select_tokens greedy, the token copied back), without and with the
+one mh_ban_tokens launch in front of the selection, over a history of `context` tokens.  The two arms alternate step by step in the same
+process on the same cache (cache.lens put back before each), every step between its own events, after warm-up; medians.  Then the
+mh_ban_tokens and mh_select_tokens launches alone, each replayed from a graph of 32 launches."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -60,6 +66,9 @@ if BEAMS:
 EXTEND = "--extend" in sys.argv
 if EXTEND:
     sys.argv.remove("--extend")
+BANS = "--bans" in sys.argv
+if BANS:
+    sys.argv.remove("--bans")
 EXTEND_NS = None
 if "--n" in sys.argv:  # --extend: the tail lengths
     _i = sys.argv.index("--n")
@@ -259,6 +268,58 @@ def extend_arm():
                           "prefill_over_extend": round(ms_prefill / ms_extend, 2), "us_attn_extend_launch": round(us, 2)}), flush=True)
 
 
+def bans_arm(logits, cache, warm=6, steps=40):
+    """Decode step + selection without and with mh_ban_tokens, alternating (module docstring)."""
+    from merlin_amd import generation as G
+
+    eng = model.engine
+    V, P = 32000, S
+    rng = torch.Generator().manual_seed(2)
+    words = [torch.randint(3, V, (int(k),), generator=rng).tolist() for k in torch.randint(1, 5, (64,), generator=rng)]
+    opt = G._resolve_options(None, dict(no_repeat_ngram_size=3, bad_words_ids=words, min_new_tokens=P + 64))
+    plan = G._ban_plan(opt, [2])
+    tables = G._ban_tables(plan, [2], P, dev)
+    hist = torch.zeros(1, P + NEW + 8, dtype=torch.int64, device=dev)
+    hist[:, :P] = ids
+    graph, g_tok, g_logits = eng.capture_decode_graph(cache)
+    keep = cache.lens.clone()
+    g_tok.copy_(logits.argmax(-1))
+
+    def step(ban):
+        graph.replay()
+        if ban:
+            _O.ban_tokens(g_logits, V, hist, len0=P, **tables)
+        g_tok.copy_(_O.select_tokens(g_logits, V))
+
+    ev = {ban: [] for ban in (False, True)}
+    for t in range(warm + steps):
+        for ban in ((False, True) if t % 2 == 0 else (True, False)):  # the arms alternate, and so does which one goes first
+            cache.lens.copy_(keep)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            step(ban)
+            b.record()
+            if t >= warm:
+                ev[ban].append((a, b))
+    torch.cuda.synchronize()
+    ms = {ban: _median([a.elapsed_time(b) for a, b in ev[ban]]) for ban in ev}
+    cache.lens.copy_(keep)
+    x = torch.randn(1, g_logits.shape[1], device=dev)
+    out = {}
+    for name, fn in (("mh_ban_tokens", lambda: _O.ban_tokens(x, V, hist, len0=P, **tables)), ("mh_select_tokens", lambda: _O.select_tokens(x, V))):
+        fn()
+        torch.cuda.synchronize()
+        ga = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(ga):
+            for _ in range(32):
+                fn()
+        out[name] = _replay_ms(ga, n=8, warm=2) / 32 * 1e3
+        del ga
+    print(json.dumps({"bans": "no_repeat_ngram_size=3 + 64 bad words + min_new_tokens", "kv": KV, "context": P, "ms_step_plus_select": round(ms[False], 4),
+                      "ms_step_plus_ban_plus_select": round(ms[True], 4), "added_us_per_step": round((ms[True] - ms[False]) * 1e3, 2),
+                      "us_mh_ban_tokens_launch": round(out["mh_ban_tokens"], 2), "us_mh_select_tokens_launch": round(out["mh_select_tokens"], 2)}), flush=True)
+
+
 with torch.no_grad():
     if EXTEND:
         extend_arm()
@@ -272,6 +333,11 @@ with torch.no_grad():
         sys.exit(0)
     if BEAMS:
         beams_arm(cache, model.engine.prefill(ids, None, None, 0, kv_fp8=KV8)[1])
+        sys.exit(0)
+    if BANS:
+        if B != 1:
+            raise SystemExit("--bans takes B = 1")
+        bans_arm(logits, cache)
         sys.exit(0)
     tok = logits.argmax(-1)
     for _ in range(3):
