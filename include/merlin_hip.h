@@ -424,6 +424,22 @@ int mh_attn_extend(const void* q, int64_t ldq, const void* kcache, const void* v
                    int D, int Smax, int dt, void* stream);
 int mh_attn_extend_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                        const int32_t* lens, int B, int n, int H, int D, int Smax, int dt, void* stream);
+/* ---- the packed rows of several continuations of ONE prompt (model.score, engine.extend_branches).  The cache of one sequence
+ * ([1, Smax, H*D], fp8: + scales [1, H, Smax]) holds the prompt in rows [0, P); the R = sum(n_c - 1) fed rows of the C continuations lie
+ * behind it in packed order, row r in cache row P + r, written before the call.  seg_start int32 [R] (read on the device): the packed
+ * index of the first row of r's own continuation - non-decreasing, seg_start[r] <= r.
+ * mh_attn_extend_branches / _kv8: q rows r (row stride ldq, 16-byte aligned), out [R, H*D] (16-byte aligned); query r attends the keys
+ *   [0, P) and the cache rows [P + seg_start[r], P + r]: the whole prompt and the earlier rows of its own continuation, itself included.
+ *   P >= 0 (P = 0: block-diagonal causal attention over the packed segments), R >= 1, P + R <= Smax (MH_ERR_ARG otherwise), D in {64, 128}.
+ *   mh_attn_extend's kernel with a two-part horizon, same arithmetic: 64-query tiles, 32-key tiles aligned from row 0, online softmax;
+ *   the tile that holds row P is masked per element (prompt keys for every query, continuation keys by segment); a block goes from its
+ *   last prompt tile to the tile of P + seg_start of its first query, a wave skips the continuation tiles outside
+ *   [P + seg_start of its first query, P + its last query].  Rows of other continuations never enter a query's maximum, sum or output
+ *   (their probabilities are exact zeros).  No split-KV either: few rows on a long prompt keep one wave per head busy. */
+int mh_attn_extend_branches(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* seg_start, int P,
+                            int R, int H, int D, int Smax, int dt, void* stream);
+int mh_attn_extend_branches_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
+                                const int32_t* seg_start, int P, int R, int H, int D, int Smax, int dt, void* stream);
 /* ---- beam search on a shared prompt cache (generate(num_beams = nb, share_prompt_kv = True)).  The K/V of a prompt lie ONCE, where the
  * prefill wrote them (the prefix: pre_k / pre_v [Bp, Pmax, H*D], fp8: + pre_kscale / pre_vscale [Bp, H, Pmax]; pre_lens[p] valid rows);
  * beam row m = p*nb + i owns only rows of generated tokens (the suffix: suf_k / suf_v [Bp*nb, G, H*D], fp8: + scales [Bp*nb, H, G], the
@@ -493,6 +509,12 @@ int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const int64_t* id
 /* out[r, :V] = log_softmax(logits[r, :V]) + row_bias[r] (fp32; row_bias nullable): beam search's accumulated scores
  * log_probs + running_beam_scores (transformers/generation/utils.py `_beam_search`) */
 int mh_log_softmax_rows(const float* logits, int64_t ldl, int rows, int V, float* out, int64_t ldo, const float* row_bias, void* stream);
+/* logprob[r] = log_softmax(logits[r, :V])[targets[r]] (mh_log_softmax_rows' arithmetic: m = max, s = sum exp(x - m) in fixed order,
+ * x[t] - (m + log s)) and greedy[r] = (lowest index of the row maximum == targets[r]), fp32 / int32 [rows]; one block per row, nothing of
+ * size V is written (model.score: no [rows, V] log-softmax).  targets int64 [rows], read on the device; a row whose target lies outside
+ * [0, V) is not read: logprob = NaN, greedy = 0.  Columns [V, ldl) are never read.  ldl = 0: every row reads the one row of logits
+ * (several targets on the same distribution: the first token of every candidate on the prompt's last-position logits). */
+int mh_token_logprobs(const float* logits, int64_t ldl, int rows, int V, const int64_t* targets, float* logprob, int32_t* greedy, void* stream);
 /* dst[i, :cols_bytes] = src[idx[i], :cols_bytes], zeros where idx[i] < 0; row strides and cols in BYTES, multiples of 4 (16 for the fast path) (KV-cache reorder by
  * beam index = HF `_reorder_cache`; expansion of a prefilled batch to num_beams rows per prompt) */
 int mh_gather_rows2d(const void* src, int64_t lds_bytes, const int64_t* idx, void* dst, int64_t ldd_bytes, int rows, int64_t cols_bytes,

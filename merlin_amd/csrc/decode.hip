@@ -28,6 +28,8 @@
 //                       for all T queries (scores on the matrix pipe, causality inside the block), and the device-side drafter.
 //   mh_attn_extend (+ _kv8)   any number of new query rows of a sequence over a kept cache (generate(session=...), engine.extend): flash-style,
 //                       64-query tiles, 32-key tiles with an online softmax, scores and P.V on the matrix pipe; no limit on Smax.
+//   mh_attn_extend_branches (+ _kv8)   the packed rows of several continuations of one prompt (model.score, engine.extend_branches): the
+//                       kernel of mh_attn_extend with a two-part horizon - the prompt's keys and the query's own continuation's.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include "mh_common.h"
 
@@ -1981,11 +1983,18 @@ extern "C" int mh_attn_decode_multi_kv8(const void* q, int64_t ldq, const void* 
 // horizon (it still takes part in the staging).  Split-KV is not done: n <= 16 on a long cache runs B * H blocks with one busy wave each.
 constexpr int EXT_TQ = 64, EXT_TK = 32, EXT_VLD = 40;  // queries per block, keys per tile, 16-bit elements per vt row
 
-template <int DT, int D, bool KV8>
+//
+// BR (mh_attn_extend_branches / _kv8): the n query rows are the packed rows of several continuations of ONE sequence whose cache holds P
+// prompt rows; row t sits in cache row P + t, `lens` is seg_start (the packed index of the first row of t's own continuation, monotone)
+// and query t sees the keys [0, P) and [P + seg_start[t], P + t].  The horizon has two parts, nothing else differs: key tiles stay
+// aligned to multiples of EXT_TK from row 0, so the tile that holds row P carries prompt keys (seen by every query) and continuation keys
+// (seen by segment) and the per-element mask tells them apart; a block steps from its last prompt tile to the tile of P + seg_start of
+// its first query (its minimum, seg_start being monotone), a wave skips the continuation tiles below P + seg_start of its own first query.
+template <int DT, int D, bool KV8, bool BR = false>
 __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
                                                      const void* __restrict__ vc_, const float* __restrict__ ks, const float* __restrict__ vs,
                                                      uint16_t* __restrict__ out, const int32_t* __restrict__ lens, int n, int H, int Smax,
-                                                     int nqt, float scale_log2) {
+                                                     int nqt, float scale_log2, int P) {
   __shared__ __attribute__((aligned(16))) uint16_t vt[D * EXT_VLD];
   constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
   constexpr int KK = D / 32;       // MFMA k steps of a score tile
@@ -1994,12 +2003,15 @@ __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int jq = lane & 15, g = lane >> 4;
   const int qt = blockIdx.x % nqt, h = (blockIdx.x / nqt) % H, b = blockIdx.x / (nqt * H);
-  const int len0 = max(0, min(lens[b], Smax));
+  const int len0 = BR ? P + 1 : max(0, min(lens[b], Smax));  // (BR: query t's own key is row P + t)
   const int q0 = qt * EXT_TQ, w0 = q0 + wave * 16;
   const int kend = min(len0 + min(q0 + EXT_TQ, n) - 1, Smax);         // keys the block's last query sees
   const int wend = w0 < n ? min(len0 + min(w0 + 16, n) - 1, Smax) : 0;  // keys the wave's last query sees
   const int t = w0 + jq;                                               // this lane's query
   const int lim = t < n ? min(len0 + t, Smax) : 0;
+  // BR: first continuation row the block / the wave / this lane's query sees (queries at or beyond n: lim = 0 hides everything)
+  const int blo = BR ? P + lens[q0] : 0, wlo = BR ? P + lens[min(w0, n - 1)] : 0, lo = BR ? P + lens[min(t, n - 1)] : 0;
+  auto sees = [&](int j) { return j < lim && (!BR || j < P || j >= lo); };  // key row j is visible to this lane's query
   const int64_t HD = (int64_t)H * D;
   const uint8_t* kc = (const uint8_t*)kc_ + ((int64_t)b * Smax * HD + (int64_t)h * D) * ES;
   const uint8_t* vc = (const uint8_t*)vc_ + ((int64_t)b * Smax * HD + (int64_t)h * D) * ES;
@@ -2020,6 +2032,12 @@ __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict_
   for (int db = 0; db < NDB; ++db) acc[db] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m = -1e30f, l = 0.f;
   for (int j0 = 0; j0 < kend; j0 += EXT_TK) {
+    if constexpr (BR) {  // (block-uniform) tiles of other continuations' rows only: on to the tile that holds the block's first row
+      if (j0 >= P && j0 + EXT_TK <= blo) {
+        j0 = (blo & ~(EXT_TK - 1)) - EXT_TK;
+        continue;
+      }
+    }
     uint4 vr[2];
     float vsc[2] = {1.f, 1.f};
     if (vstage) {
@@ -2037,7 +2055,7 @@ __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict_
         }
       }
     }
-    const bool active = j0 < wend;  // (wave-uniform)
+    const bool active = j0 < wend && (!BR || j0 < P || j0 + EXT_TK > wlo);  // (wave-uniform)
     float alpha = 1.f;
     uint4 pb = make_uint4(0, 0, 0, 0);
     if (active) {
@@ -2084,7 +2102,7 @@ __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict_
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           s[sub][r] = KV8 ? s4[r] * ksc[sub][r] * scale_log2 : s4[r] * scale_log2;
-          if (j0 + sub * 16 + 4 * g + r < lim) tm = fmaxf(tm, s[sub][r]);
+          if (sees(j0 + sub * 16 + 4 * g + r)) tm = fmaxf(tm, s[sub][r]);
         }
       }
       tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
@@ -2097,7 +2115,7 @@ __global__ __launch_bounds__(256) void attn_extend_k(const uint16_t* __restrict_
       for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          p[sub][r] = (j0 + sub * 16 + 4 * g + r < lim) ? fast_exp2(s[sub][r] - mn) : 0.f;
+          p[sub][r] = sees(j0 + sub * 16 + 4 * g + r) ? fast_exp2(s[sub][r] - mn) : 0.f;
           psum += p[sub][r];
         }
       l = fmaf(l, alpha, psum);  // (this lane's four keys per sub-tile; the four lanes of a query are summed at the end)
@@ -2163,7 +2181,29 @@ static int attn_extend_impl(const void* q, int64_t ldq, const void* kc, const vo
   const dim3 grid((unsigned)(B * H * nqt)), block(256);
 #define GO(DT_, D_)                                                                                                                    \
   hipLaunchKernelGGL((attn_extend_k<DT_, D_, KV8>), grid, block, 0, as_stream(stream), (const uint16_t*)q, ldq, kc, vc, ks, vs, (uint16_t*)out, \
-                     lens, n, H, Smax, nqt, scale_log2)
+                     lens, n, H, Smax, nqt, scale_log2, 0)
+  if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
+  else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
+#undef GO
+  MH_LAUNCH_CHECK();
+}
+
+template <bool KV8>
+static int attn_branches_impl(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                              const int32_t* seg_start, int P, int R, int H, int D, int Smax, int dt, void* stream) {
+  if (!q || !kc || !vc || !out || !seg_start || H <= 0 || Smax <= 0 || (ldq & 7) || !aligned16(q) || !aligned16(out)) return MH_ERR_ARG;
+  if (P < 0 || R < 1 || (int64_t)P + R > Smax) return MH_ERR_ARG;  // every row the kernel reads, [0, P + R), lies in the cache
+  if (KV8 && (!ks || !vs || (((uintptr_t)kc | (uintptr_t)vc) & 7u))) return MH_ERR_ARG;
+  if (!KV8 && (!aligned16(kc) || !aligned16(vc))) return MH_ERR_ARG;
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  const int nqt = (R + EXT_TQ - 1) / EXT_TQ;
+  if ((int64_t)H * nqt > 0x7fffffff) return MH_ERR_SHAPE;
+  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  const dim3 grid((unsigned)(H * nqt)), block(256);
+#define GO(DT_, D_)                                                                                                                    \
+  hipLaunchKernelGGL((attn_extend_k<DT_, D_, KV8, true>), grid, block, 0, as_stream(stream), (const uint16_t*)q, ldq, kc, vc, ks, vs,   \
+                     (uint16_t*)out, seg_start, R, H, Smax, nqt, scale_log2, P)
   if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
   else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
 #undef GO
@@ -2178,6 +2218,16 @@ extern "C" int mh_attn_extend(const void* q, int64_t ldq, const void* kcache, co
 extern "C" int mh_attn_extend_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                                   const int32_t* lens, int B, int n, int H, int D, int Smax, int dt, void* stream) {
   return attn_extend_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, n, H, D, Smax, dt, stream);
+}
+
+extern "C" int mh_attn_extend_branches(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* seg_start,
+                                       int P, int R, int H, int D, int Smax, int dt, void* stream) {
+  return attn_branches_impl<false>(q, ldq, kcache, vcache, nullptr, nullptr, out, seg_start, P, R, H, D, Smax, dt, stream);
+}
+
+extern "C" int mh_attn_extend_branches_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale,
+                                           void* out, const int32_t* seg_start, int P, int R, int H, int D, int Smax, int dt, void* stream) {
+  return attn_branches_impl<true>(q, ldq, k8, v8, kscale, vscale, out, seg_start, P, R, H, D, Smax, dt, stream);
 }
 
 // ---- beam search on a shared prompt cache ------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 //                      uniform comes from a counter-based generator keyed on (seed, step, row): no host RNG traffic, replayable)
 //   mh_select_tokens_warp  the same kernel with two more warpers behind top-p: min_p, then epsilon_cutoff
 //   mh_log_softmax_rows  fp32 log-probabilities for beam search
+//   mh_token_logprobs  log p(target) and "target is the greedy token" per row, nothing of size V written (model.score)
 //   mh_gather_rows2d   dst[i, :cols] = src[idx[i], :cols], zeros where idx[i] < 0  (KV-cache reorder by beam index, batch expansion,
 //                      unpad / pad of the key-padding attention branch)
 #include "mh_common.h"
@@ -250,6 +251,46 @@ __global__ __launch_bounds__(256) void log_softmax_rows_k(const float* __restric
   for (int i = threadIdx.x; i < V; i += 256) out[(int64_t)row * ldo + i] = x[i] - lse;
 }
 
+// One block per row: logprob = x[t] - (m + log sum exp(x - m)) in log_softmax_rows_k's arithmetic and order, greedy = (lowest index of the
+// maximum == t), select_tokens_k's do_sample == 0 answer.  A target outside [0, V) is not read: NaN and 0.
+__global__ __launch_bounds__(256) void token_logprobs_k(const float* __restrict__ logits, int64_t ldl, int V, const int64_t* __restrict__ targets,
+                                                        float* __restrict__ logprob, int32_t* __restrict__ greedy) {
+  __shared__ float fs[4];
+  __shared__ int is[4];
+  BlockRed red{fs, is};
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int64_t t = targets[row];
+  if (t < 0 || t >= (int64_t)V) {  // (block-uniform)
+    if (tid == 0) {
+      logprob[row] = __int_as_float(0x7fc00000);
+      greedy[row] = 0;
+    }
+    return;
+  }
+  const float* x = logits + (int64_t)row * ldl;
+  float m = -INFINITY;
+  int am = 0x7fffffff;
+  for (int i = tid; i < V; i += 256) {
+    const float z = x[i];
+    if (z > m) { m = z; am = i; }  // (ascending i: the thread's first index of its maximum)
+  }
+  const float gm = red.max(m);
+  int cand = (m == gm) ? am : 0x7fffffff;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
+  __syncthreads();
+  if ((tid & 63) == 0) is[tid >> 6] = cand;
+  __syncthreads();
+  const int first = min(min(is[0], is[1]), min(is[2], is[3]));
+  float s = 0.f;
+  for (int i = tid; i < V; i += 256) s += expf(x[i] - gm);
+  s = red.sum(s);
+  if (tid == 0) {
+    logprob[row] = x[t] - (gm + logf(s));
+    greedy[row] = first == (int)t;
+  }
+}
+
 // VT-sized vectors (16 bytes when every stride / width / pointer allows it, else 4 bytes)
 template <typename VT>
 __global__ __launch_bounds__(256) void gather_rows2d_k(const VT* __restrict__ src, int64_t lds_v, const int64_t* __restrict__ idx,
@@ -304,6 +345,13 @@ extern "C" int mh_log_softmax_rows(const float* logits, int64_t ldl, int rows, i
                                    void* stream) {
   if (!logits || !out || rows <= 0 || V <= 0 || ldl < V || ldo < V) return MH_ERR_ARG;
   hipLaunchKernelGGL(log_softmax_rows_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, out, ldo, row_bias);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_token_logprobs(const float* logits, int64_t ldl, int rows, int V, const int64_t* targets, float* logprob, int32_t* greedy,
+                                 void* stream) {
+  if (!logits || !targets || !logprob || !greedy || rows <= 0 || V <= 0 || (ldl != 0 && ldl < V)) return MH_ERR_ARG;  // (ldl = 0: one row)
+  hipLaunchKernelGGL(token_logprobs_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, targets, logprob, greedy);
   MH_LAUNCH_CHECK();
 }
 

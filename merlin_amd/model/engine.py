@@ -1438,6 +1438,77 @@ class HipEngine:
         cache.lens.add_(n)
         return logits
 
+    HEAD_CHUNK = 256  # rows of fp32 logits held at a time by the scoring pass (256 x V floats: 33 MB at V = 32003)
+
+    def head_logits(self, hn):
+        """fp32 logits [rows, >= V] of normalised hidden rows through lm_head (the first V columns are valid): the decode step's GEMV up
+        to its 16 rows, the prefill's GEMM beyond."""
+        V = self.model.config.vocab_size
+        if hn.shape[0] <= 16:
+            return O.gemv(hn, self._lm_head_w(), out_f32=True, n=V)
+        return O.gemm_nt(hn, self._lm_head_w(), out_f32=True)
+
+    def extend_branches(self, cache, plan, pos=None, return_logits=False):
+        """The R = len(plan.fed) packed rows of several text continuations of ONE prompt (generation scoring: scoring.score) on a plain
+        KVCache that holds the P = cache.lens[0] prompt tokens: extend's layer loop with every continuation branching off the prompt.
+        plan (scoring._branch_plan): fed [R] token ids, seg_start int32 [R] (the packed index of the first row of the row's continuation)
+        and rel_pos int32 [R] (the row's offset inside it).  The embedding is a plain gather, the RoPE epilogue reads a table whose row
+        r is position P + rel_pos[r], the rotated keys and the values go to cache rows [P, P + R) in packed order, and
+        mh_attn_extend_branches lets row r see the prompt and rows seg_start[r] .. r only.  One pass over the 16-bit weights for all
+        continuations.  cache.lens is NOT advanced: the rows behind the prompt are stale afterwards, as after a rejected draft.
+        Returns the normalised final hidden rows [R, d] (head_logits turns a chunk of them into logits); return_logits=True: (hidden,
+        fp32 logits [R, V]), for tests.  pos: P when the caller knows it on the host."""
+        m = self.model
+        cfg = m.config
+        if not isinstance(cache, HipEngine.KVCache) or cache.B != 1 or cache.rpos is not None:
+            raise ValueError("extend_branches takes a plain KVCache of one sequence whose rotary positions are its rows (B = 1, no left padding or holes)")
+        fed = [int(t) for t in (plan.fed.tolist() if isinstance(plan.fed, torch.Tensor) else plan.fed)]
+        R = len(fed)
+        d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
+        if R < 1 or tuple(plan.seg_start.shape) != (R,) or tuple(plan.rel_pos.shape) != (R,):
+            raise ValueError(f"extend_branches takes a plan of R >= 1 rows with seg_start and rel_pos [R], got {R} fed tokens")
+        if any(not 0 <= t < V for t in fed):
+            raise ValueError(f"extend_branches: fed token ids must lie in [0, {V})")
+        seg_h, rel_h = [int(v) for v in plan.seg_start.tolist()], [int(v) for v in plan.rel_pos.tolist()]
+        # the kernel's tile skips rely on it: a segment starts at its own first row, so seg_start is non-decreasing and <= r
+        if any(not (s == r or (r > 0 and s == seg_h[r - 1])) or rel_h[r] != r - s for r, s in enumerate(seg_h)):
+            raise ValueError("extend_branches: seg_start[r] must be the packed index of the first row of r's own continuation "
+                             "(non-decreasing, seg_start[r] <= r, a new value only at r itself) and rel_pos[r] = r - seg_start[r]")
+        P = int(cache.lens[0]) if pos is None else int(pos)
+        if P < 0 or P + R > cache.Smax:
+            raise ValueError(f"extend_branches: {P} cached + {R} rows exceed the cache's {cache.Smax} rows (grow_cache makes a larger one)")
+        A = self.ensure_arena()
+        dev = A.flat.device
+        eps = cfg.rms_norm_eps
+        seg = plan.seg_start.to(device=dev, dtype=torch.int32).contiguous()
+        rel = plan.rel_pos.to(device=dev, dtype=torch.int64)
+        rope = self._rope_table(cache.Smax, dev).index_select(0, rel + P)  # row r: position P + rel_pos[r] (< P + R <= Smax)
+        ids = torch.tensor(fed, dtype=torch.int64, device=dev)
+        emb = A.view("model.embed_tokens.weight", shape=(V, d))
+        x = (O.embed_splice_fwd_f32 if self.fp32_residual else O.embed_splice_fwd)(ids, None, emb, None)
+        for li, W in enumerate(self.llama):
+            h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
+            qkv = O.gemm_nt_rope(h1, W.wqkv, rope, R, H, D)
+            q, k, v = self._qkv(qkv)
+            if cache.fp8:
+                k8, v8, ks, vs = cache.layer(li)
+                O.kv8_fill(k, k8, ks, 1, R, H, D, row0=P)
+                O.kv8_fill(v, v8, vs, 1, R, H, D, row0=P)
+                o = O.attn_extend_branches_kv8(q, k8, v8, ks, vs, seg, P, H, D)
+            else:
+                cache.k[li][:, P:P + R].copy_(k.view(1, R, d))
+                cache.v[li][:, P:P + R].copy_(v.view(1, R, d))
+                o = O.attn_extend_branches(q, cache.k[li], cache.v[li], seg, P, H, D)
+            x = self._stream_add(x, o, W.wo)
+            h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
+            _, act = O.gemm_swiglu_fwd(h2, W.wgu)
+            x = self._stream_add(x, act, W.wd)
+        hn, _ = self._stream_norm(x, A.view("model.norm.weight"), eps, want_x16=False)
+        if not return_logits:
+            return hn
+        step = self.HEAD_CHUNK
+        return hn, torch.cat([self.head_logits(hn[r0:r0 + step])[:, :V] for r0 in range(0, R, step)])
+
     def grow_cache(self, cache, Smax):
         """A new KVCache of Smax >= cache.Smax rows per sequence holding the rows of `cache` (the scales [B, H, Smax] of the fp8 form
         included), same format, lengths and positions.  Off the hot path: plain copies, once per growth of a session."""

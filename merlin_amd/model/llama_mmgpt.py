@@ -285,6 +285,16 @@ class MMGPTLlamaForCausalLM(nn.Module):
 
         return Session(self, capacity=capacity, fp8_kv=fp8_kv)
 
+    def score(self, input_ids, continuations, images=None, fp8_kv=False, session=None, attention_mask=None):
+        """Log-likelihoods of C text continuations of one prompt (merlin_amd/scoring.py) -> ScoreOutput(token_logprobs, logprobs, is_greedy,
+        stats).  The prompt (image spans as in generate) runs once; all candidates' rows run in one packed pass over the weights, every
+        row seeing the prompt and its own candidate only.  Multiple-choice evaluation, re-ranking, reward and filter scores.  session:
+        the prompt's reusable prefix comes from the session's cache and the session holds the prompt afterwards; fp8_kv: the cache format;
+        attention_mask: accepted only without zeros (a padded prompt is refused)."""
+        from ..scoring import score as _score
+
+        return _score(self, input_ids, continuations, images=images, fp8_kv=fp8_kv, session=session, attention_mask=attention_mask)
+
     # ---- construction helpers ----------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path, config=None, cache_dir=None, torch_dtype=None, dtype=None, **kw):

@@ -476,6 +476,33 @@ def attn_extend_kv8(q, k8, v8, kscale, vscale, lens, n, H, D, out=None):
     return out
 
 
+def attn_extend_branches(q, kcache, vcache, seg_start, P, H, D, out=None):
+    """The packed rows of several continuations of one prompt: q [R, H*D] view (row stride ldq) against the one-sequence cache
+    [1, Smax, H*D] whose rows [0, P) hold the prompt and rows [P, P + R) the rows' own keys; seg_start int32 [R] is the packed index of the
+    first row of the row's continuation.  Query r sees keys [0, P) and [P + seg_start[r], P + r] (mh_attn_extend_branches)."""
+    R = seg_start.shape[0]
+    assert q.shape == (R, H * D) and q.stride(1) == 1 and seg_start.dtype == torch.int32 and seg_start.is_contiguous()
+    assert kcache.is_contiguous() and vcache.is_contiguous() and kcache.shape == vcache.shape and kcache.shape[0] == 1 and kcache.shape[2] == H * D
+    out = torch.empty(R, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    assert out.shape == (R, H * D) and out.is_contiguous()
+    L.call("mh_attn_extend_branches", q, q.stride(0), kcache, vcache, out, seg_start, int(P), R, H, D, kcache.shape[1], dt_of(q), _stream())
+    return out
+
+
+def attn_extend_branches_kv8(q, k8, v8, kscale, vscale, seg_start, P, H, D, out=None):
+    """attn_extend_branches against the fp8 KV cache (k8, v8 uint8 [1, Smax, H*D]; kscale, vscale fp32 [1, H, Smax])."""
+    R = seg_start.shape[0]
+    Smax = k8.shape[1]
+    assert q.shape == (R, H * D) and q.stride(1) == 1 and seg_start.dtype == torch.int32 and seg_start.is_contiguous()
+    assert k8.dtype == v8.dtype == torch.uint8 and k8.shape == v8.shape == (1, Smax, H * D) and k8.is_contiguous() and v8.is_contiguous()
+    assert kscale.dtype == vscale.dtype == torch.float32 and kscale.shape == vscale.shape == (1, H, Smax)
+    assert kscale.is_contiguous() and vscale.is_contiguous()
+    out = torch.empty(R, H * D, dtype=q.dtype, device=q.device) if out is None else out
+    assert out.shape == (R, H * D) and out.is_contiguous()
+    L.call("mh_attn_extend_branches_kv8", q, q.stride(0), k8, v8, kscale, vscale, out, seg_start, int(P), R, H, D, Smax, dt_of(q), _stream())
+    return out
+
+
 def beam_ancestry(anc_in, anc_out, beam_idx, gen):
     """The table step of HF `_reorder_cache` on a shared prompt cache (mh_beam_ancestry): anc_out[m, :gen[m]] = anc_in[beam_idx[m], :gen[m]],
     anc_out[m, gen[m]] = m; anc int32 [rows, G] (two buffers), beam_idx int64 [rows], gen int32 [rows], all on the device."""
@@ -1231,6 +1258,21 @@ def log_softmax_rows(logits, V=None, row_bias=None):
     out = torch.empty(R, V, dtype=torch.float32, device=logits.device)
     L.call("mh_log_softmax_rows", logits, logits.stride(0), R, V, out, V, row_bias, _stream())
     return out
+
+
+def token_logprobs(logits, targets, V=None, logprob=None, greedy=None):
+    """logits fp32 [R, >=V], targets int64 [R] on the device -> (log_softmax(logits[r, :V])[targets[r]] fp32 [R], targets[r] is the lowest
+    index of row r's maximum, int32 [R]) without a [R, V] log-softmax (mh_token_logprobs).  A target outside [0, V): NaN and 0.
+    logits may be one row expanded to R (row stride 0): R targets on the same distribution."""
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and targets.dtype == torch.int64 and targets.shape == (R,) and targets.is_contiguous()
+    logprob = torch.empty(R, dtype=torch.float32, device=logits.device) if logprob is None else logprob
+    greedy = torch.empty(R, dtype=torch.int32, device=logits.device) if greedy is None else greedy
+    assert logprob.shape == greedy.shape == (R,) and logprob.dtype == torch.float32 and greedy.dtype == torch.int32
+    assert logprob.is_contiguous() and greedy.is_contiguous()
+    L.call("mh_token_logprobs", logits, logits.stride(0), R, V, targets, logprob, greedy, _stream())
+    return logprob, greedy
 
 
 def gather_rows2d(src, idx, dst, cols=None):

@@ -3,7 +3,7 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend | --bans]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend | --bans | --score]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
@@ -31,7 +31,18 @@ one mh_attn_extend launch alone (from a graph over the 32 layers' caches).  Medi
 step + the selection as generate() runs them per token (graph replay, mh_select_tokens greedy, the token copied back), without and with the
 one mh_ban_tokens launch in front of the selection, over a history of `context` tokens.  The two arms alternate step by step in the same
 process on the same cache (cache.lens put back before each), every step between its own events, after warm-up; medians.  Then the
-mh_ban_tokens and mh_select_tokens launches alone, each replayed from a graph of 32 launches."""
+mh_ban_tokens and mh_select_tokens launches alone, each replayed from a graph of 32 launches.
+
+--score: the scoring arm instead (model.score: the log-likelihoods of C candidate continuations of n tokens each on one prompt), B = 1, one
+process per (context, cache format): a prompt of one image and text, `context` tokens.  For (C, n) = (4, 2), (4, 8), (16, 32) (--cn
+"C:n,C:n"), three arms that alternate in this process, every run between its own events after a warm-up, medians of 5 (min and max of the two whole-call arms are printed too): (i) model.score - without
+a session (the whole prompt runs) and on a session that holds the prompt (one prompt token runs: the candidates' pass alone); (ii) what the
+API offered before score: a session prefill, then per candidate engine.extend of its fed tokens, lm_head on its rows and log_softmax_rows
+through the existing ops, cache.truncate - after session.reset() and on the held prompt (extend hands out the last row's logits only, so
+the lm_head of the other n - 2 rows runs on a stand-in hidden-state buffer: the same launches on the same shapes); (iii) C full forward
+calls of prompt + candidate with the log-softmax of the candidate's rows.  Then the attention launches per layer of (i) and (ii), counted
+at the library boundary, and one mh_attn_extend_branches launch on the R = C (n - 1) packed rows against the C mh_attn_extend launches it
+replaces, each from a graph over the 32 layers' caches."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -69,6 +80,14 @@ if EXTEND:
 BANS = "--bans" in sys.argv
 if BANS:
     sys.argv.remove("--bans")
+SCORE = "--score" in sys.argv
+if SCORE:
+    sys.argv.remove("--score")
+SCORE_CN = [(4, 2), (4, 8), (16, 32)]
+if "--cn" in sys.argv:  # --score: the candidate sets, "C:n,C:n"
+    _i = sys.argv.index("--cn")
+    SCORE_CN = [tuple(int(v) for v in a.split(":")) for a in sys.argv[_i + 1].split(",")]
+    del sys.argv[_i:_i + 2]
 EXTEND_NS = None
 if "--n" in sys.argv:  # --extend: the tail lengths
     _i = sys.argv.index("--n")
@@ -268,6 +287,117 @@ def extend_arm():
                           "prefill_over_extend": round(ms_prefill / ms_extend, 2), "us_attn_extend_launch": round(us, 2)}), flush=True)
 
 
+def score_arm(warm=1, reps=5):
+    """model.score against C extends on a session and against C full forwards (module docstring)."""
+    from merlin_amd import _lib as L
+
+    eng = model.engine
+    P, V, d = S, model.config.vocab_size, 4096
+    span = synth._image_span(576, 32000)
+    if B != 1 or P < 1 + len(span):
+        raise SystemExit("--score takes B = 1 and a context that holds BOS and one image span (579 tokens)")
+    img = torch.randn(1, 3, 336, 336, generator=g).to(dev)
+    ids_t = torch.tensor([[1] + span + torch.randint(3, 32000, (P - 1 - len(span),), generator=g).tolist()]).to(dev)
+    for C_, n in SCORE_CN:
+        conts = [torch.randint(3, 31000, (n,), generator=g).tolist() for _ in range(C_)]
+        R = C_ * (n - 1)
+        cand_t = [torch.tensor([c], device=dev) for c in conts]
+        full_t = [torch.cat([ids_t, c], dim=1) for c in cand_t]
+        s1 = model.new_session(capacity=P + R + 8, fp8_kv=KV8)
+        s2 = model.new_session(capacity=P + n + 8, fp8_kv=KV8)
+        stand_in = torch.randn(max(n - 2, 1), d, dtype=torch.bfloat16, device=dev)
+
+        def arm_ii():
+            logits, cache = s2._prefill(ids_t, [img], n)
+            first = _O.log_softmax_rows(logits, V)
+            got = []
+            for c in cand_t:  # the targets are gathered on the device; one read-back at the end, like score()
+                got.append(first[0, c[0, :1]])
+                if n > 1:
+                    cache.truncate(P)
+                    got.append(_O.log_softmax_rows(eng.extend(cache, c[:, :-1], None, pos=P), V)[0, c[0, -1:]])
+                    if n > 2:
+                        x = stand_in[:n - 2]
+                        head = _O.gemv(x, eng._lm_head_w(), out_f32=True, n=V) if n - 2 <= 16 else _O.gemm_nt(x, eng._lm_head_w(), out_f32=True)
+                        got.append(_O.log_softmax_rows(head, V).gather(1, c[0, 1:-1, None])[:, 0])
+            cache.truncate(P)
+            return torch.cat(got).cpu()
+
+        def arm_ii_full():
+            s2.reset()
+            return arm_ii()
+
+        def arm_iii():
+            for c, f in zip(conts, full_t):
+                lg = model(input_ids=f, images=[img]).logits[0, P - 1:-1, :V].float()
+                torch.log_softmax(lg, -1).gather(1, torch.tensor(c, device=dev)[:, None]).sum().item()
+
+        arms = {"i_score": lambda: model.score(ids_t, conts, images=[img], fp8_kv=KV8),
+                "i_score_prompt_held": lambda: model.score(ids_t, conts, images=[img], fp8_kv=KV8, session=s1),
+                "ii_extends": arm_ii_full, "ii_extends_prompt_held": arm_ii, "iii_forwards": arm_iii}
+        names = list(arms)
+        ms = {k: [] for k in names}
+        for t in range(warm + reps):
+            for k in names[t % len(names):] + names[:t % len(names)]:  # the arms alternate, and so does which one goes first
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                a.record()
+                arms[k]()
+                b.record(); torch.cuda.synchronize()
+                if t >= warm:
+                    ms[k].append(a.elapsed_time(b))
+        spread = {k: (min(v), max(v)) for k, v in ms.items()}
+        ms = {k: _median(v) for k, v in ms.items()}
+        # attention launches per layer, at the library boundary
+        seen, real = [], L.call
+
+        def recording(name, *args):
+            seen.append(name)
+            return real(name, *args)
+
+        L.call = recording
+        try:
+            arms["i_score_prompt_held"]()
+            n_i = sum(x.startswith("mh_attn_extend_branches") for x in seen) / 32
+            del seen[:]
+            arm_ii()
+            n_ii = sum(x.startswith("mh_attn_extend") for x in seen) / 32 - 1  # (without the one-token extend of the held prompt's last position)
+        finally:
+            L.call = real
+        out = {"score": "16-bit weights", "kv": KV, "context": P, "C": C_, "n": n, "rows": R}
+        out.update({"ms_" + k: round(v, 3) for k, v in ms.items()})
+        out.update({"min_max_" + k: [round(v, 2) for v in spread[k]] for k in ("i_score", "ii_extends")})
+        out.update(ratio_i_over_ii=round(ms["i_score"] / ms["ii_extends"], 3), ratio_i_over_iii=round(ms["i_score"] / ms["iii_forwards"], 3),
+                   ratio_prompt_held_i_over_ii=round(ms["i_score_prompt_held"] / ms["ii_extends_prompt_held"], 3),
+                   attn_launches_per_layer_i=n_i, attn_launches_per_layer_ii=n_ii)
+        if R:  # one packed launch against the C launches it replaces
+            cache = s1.cache
+            q = torch.randn(R, d, dtype=torch.bfloat16, device=dev)
+            seg = torch.arange(C_, dtype=torch.int32, device=dev).repeat_interleave(n - 1) * (n - 1)
+            lens1 = torch.full((1,), P + 1, dtype=torch.int32, device=dev)
+            if KV8:
+                packed = lambda li: _O.attn_extend_branches_kv8(q, *cache.layer(li), seg, P, 32, 128)  # noqa: E731
+                single = lambda li: _O.attn_extend_kv8(q[:n - 1], *cache.layer(li), lens1, n - 1, 32, 128)  # noqa: E731
+            else:
+                packed = lambda li: _O.attn_extend_branches(q, cache.k[li], cache.v[li], seg, P, 32, 128)  # noqa: E731
+                single = lambda li: _O.attn_extend(q[:n - 1], cache.k[li], cache.v[li], lens1, n - 1, 32, 128)  # noqa: E731
+            packed(0); single(0)
+            torch.cuda.synchronize()
+            gp, gs = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gp):
+                for li in range(32):
+                    packed(li)
+            with torch.cuda.graph(gs):
+                for li in range(32):
+                    for _ in range(C_):
+                        single(li)
+            out.update(us_attn_extend_branches_launch=round(_replay_ms(gp, n=8, warm=2) / 32 * 1e3, 2),
+                       us_C_attn_extend_launches=round(_replay_ms(gs, n=8, warm=2) / 32 * 1e3, 2))
+            del gp, gs
+        print(json.dumps(out), flush=True)
+        del s1, s2
+
+
 def bans_arm(logits, cache, warm=6, steps=40):
     """Decode step + selection without and with mh_ban_tokens, alternating (module docstring)."""
     from merlin_amd import generation as G
@@ -323,6 +453,9 @@ def bans_arm(logits, cache, warm=6, steps=40):
 with torch.no_grad():
     if EXTEND:
         extend_arm()
+        sys.exit(0)
+    if SCORE:
+        score_arm()
         sys.exit(0)
     t0 = time.time()
     logits, cache = model.engine.prefill(ids, None, None, BEAMS_NEW if BEAMS else NEW + 8, kv_fp8=KV8)
