@@ -506,6 +506,16 @@ int mh_select_tokens_warp(const float* logits, int64_t ldl, int rows, int V, int
 int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int len0, int len_step, int ngram,
                   const int64_t* words, const int32_t* word_off, int n_words, const int64_t* always, int n_always, const int64_t* begin,
                   int n_begin, int begin_index, const int64_t* eos, int n_eos, int min_total, void* stream);
+/* Classifier-free guidance for decoder-only generation (transformers UnbatchedClassifierFreeGuidanceLogitsProcessor, the first processor
+ * of its chain): for `rows` row pairs, out[r, i] = lu_i + scale * (lc_i - lu_i) for i < V, lc = log_softmax(cond[r, :V]) and lu =
+ * log_softmax(uncond[r, :V]) in fp32 (l_i = (x_i - max) - log sum exp(x - max)).  cond and uncond are separate pointers with their own row
+ * strides (two tensors at the prefill; rows 0 and 1 of one buffer in a decode step; rows t and T + t in a verify step); out may be the cond
+ * rows (in place) or a third buffer, and must not overlap uncond.  Columns [V, ld) are neither read nor written; uncond is not written.
+ * Contract: the inputs are raw head outputs and FINITE - the mix always runs before mh_ban_tokens, so -inf never reaches it (a -inf in
+ * both rows would give inf - inf).  One 256-thread block per pair, one launch, nothing allocated or read back.  rows = 0: nothing to do.
+ * Refused (MH_ERR_ARG, nothing written): V < 1, rows < 0, a null pointer, a row stride below V. */
+int mh_guidance_mix(const float* cond, int64_t ldc, const float* uncond, int64_t ldu, int rows, int V, float scale, float* out, int64_t ldo,
+                    void* stream);
 /* out[r, :V] = log_softmax(logits[r, :V]) + row_bias[r] (fp32; row_bias nullable): beam search's accumulated scores
  * log_probs + running_beam_scores (transformers/generation/utils.py `_beam_search`) */
 int mh_log_softmax_rows(const float* logits, int64_t ldl, int rows, int V, float* out, int64_t ldo, const float* row_bias, void* stream);

@@ -7,6 +7,8 @@
 //   mh_select_tokens   argmax (do_sample=0) or temperature -> top-k -> top-p -> multinomial (inverse CDF in index order; the
 //                      uniform comes from a counter-based generator keyed on (seed, step, row): no host RNG traffic, replayable)
 //   mh_select_tokens_warp  the same kernel with two more warpers behind top-p: min_p, then epsilon_cutoff
+//   mh_guidance_mix    classifier-free guidance: log_softmax of a conditional and an unconditional row mixed into the guided scores,
+//                      in front of the bans and the selection
 //   mh_log_softmax_rows  fp32 log-probabilities for beam search
 //   mh_token_logprobs  log p(target) and "target is the greedy token" per row, nothing of size V written (model.score)
 //   mh_gather_rows2d   dst[i, :cols] = src[idx[i], :cols], zeros where idx[i] < 0  (KV-cache reorder by beam index, batch expansion,
@@ -234,6 +236,70 @@ __global__ __launch_bounds__(256) void ban_tokens_k(float* __restrict__ logits, 
     for (int i = tid; i < n_eos; i += 256) ban(eos[i]);
 }
 
+// One block per row pair: out_i = lu_i + g (lc_i - lu_i), lc = log_softmax(cond row), lu = log_softmax(uncond row) (transformers'
+// UnbatchedClassifierFreeGuidanceLogitsProcessor).  Pass 1 keeps a running maximum and the sum of exp(x - maximum) per thread and row
+// (rescaled to the new maximum every round), merged over the block at the end; pass 2 re-reads both rows (L2) and writes.  l = (x - max) - log(sum),
+// not x - (max + log(sum)): a token near the maximum keeps its small log-probability to its own precision however large the logits are.
+// The exponentials are __expf, as in select_tokens_k: a term's relative error of a few 2^-24 averages out over the sum, which enters the
+// result only through log(sum).  Inputs are finite.  out may be the cond row: element i is read and written by the same thread, after
+// pass 1 has finished with it (the block reductions in between are barriers) - which is why cond and out carry no __restrict__.
+__global__ __launch_bounds__(256) void guidance_mix_k(const float* cond, int64_t ldc, const float* __restrict__ uncond, int64_t ldu, int V,
+                                                      float g, float* out, int64_t ldo) {
+  __shared__ float fs[4];
+  __shared__ int is[4];
+  BlockRed red{fs, is};
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* c = cond + (int64_t)row * ldc;
+  const float* u = uncond + (int64_t)row * ldu;
+  float* o = out + (int64_t)row * ldo;
+  float mc = -INFINITY, sc = 0.f, mu = -INFINITY, su = 0.f;
+  // W columns (256 apart) per round and row: their loads and exponentials are independent, the running sum is rescaled once per round
+  constexpr int W = 8;
+  for (int i = tid; i < V; i += 256 * W) {
+    float xc[W], xu[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const int j = i + 256 * k;
+      xc[k] = j < V ? c[j] : -INFINITY;  // (a column past V: exp(-inf - max) = 0; the round's first column is always inside)
+      xu[k] = j < V ? u[j] : -INFINITY;
+    }
+    float nc = mc, nu = mu, ac = 0.f, au = 0.f;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      nc = fmaxf(nc, xc[k]);
+      nu = fmaxf(nu, xu[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      ac += __expf(xc[k] - nc);
+      au += __expf(xu[k] - nu);
+    }
+    sc = fmaf(sc, __expf(mc - nc), ac);  // (first round: 0 * exp(-inf))
+    su = fmaf(su, __expf(mu - nu), au);
+    mc = nc;
+    mu = nu;
+  }
+  const float gmc = red.max(mc), gmu = red.max(mu);
+  sc = red.sum(sc * __expf(mc - gmc));  // (a thread without columns, V < 256: 0 * exp(-inf) = 0)
+  su = red.sum(su * __expf(mu - gmu));
+  const float lsc = logf(sc), lsu = logf(su);
+  for (int i = tid; i < V; i += 256 * W) {  // a round's loads all come before its stores: out may be the cond row
+    float xc[W], xu[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const int j = i + 256 * k;
+      xc[k] = j < V ? c[j] : 0.f;
+      xu[k] = j < V ? u[j] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const int j = i + 256 * k;
+      const float lc = (xc[k] - gmc) - lsc, lu = (xu[k] - gmu) - lsu;
+      if (j < V) o[j] = fmaf(g, lc - lu, lu);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void log_softmax_rows_k(const float* __restrict__ logits, int64_t ldl, int V, float* __restrict__ out,
                                                           int64_t ldo, const float* __restrict__ row_bias) {
   __shared__ float fs[4];
@@ -338,6 +404,14 @@ extern "C" int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const 
   if ((n_words > 0 && (!words || !word_off)) || (n_always > 0 && !always) || (n_begin > 0 && !begin) || (n_eos > 0 && !eos)) return MH_ERR_ARG;
   hipLaunchKernelGGL(ban_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, ids, ld_ids, len0, len_step, ngram, words,
                      word_off, n_words, always, n_always, begin, n_begin, begin_index, eos, n_eos, min_total);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_guidance_mix(const float* cond, int64_t ldc, const float* uncond, int64_t ldu, int rows, int V, float scale, float* out,
+                               int64_t ldo, void* stream) {
+  if (!cond || !uncond || !out || rows < 0 || V < 1 || ldc < V || ldu < V || ldo < V) return MH_ERR_ARG;
+  if (rows == 0) return MH_OK;
+  hipLaunchKernelGGL(guidance_mix_k, dim3(rows), dim3(256), 0, as_stream(stream), cond, ldc, uncond, ldu, V, scale, out, ldo);
   MH_LAUNCH_CHECK();
 }
 

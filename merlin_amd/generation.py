@@ -24,6 +24,14 @@ once, _ban_tables), the sequence is kept in one preallocated ids buffer, and eve
 right before the selection (beam search: on log_probs + running scores before the top-k) - no ids come back to the host.  _banned is the
 restatement of the five clauses on a Python list.  Two more warpers, min_p and epsilon_cutoff, are thresholds of the selection kernel
 (mh_select_tokens_warp), behind top-p in transformers' order.  A call with none of these options launches what it launched before them.
+
+Classifier-free guidance (transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor, the first processor of its chain: guidance_scale,
+negative_prompt_ids, negative_prompt_attention_mask; negative_images is this package's addition for negative prompts with image spans):
+a second, unconditional sequence - the negative prompt (default: the prompt's last token) followed by every generated token - is decoded
+beside the conditional one, and the step's scores become lu + g (lc - lu) of the two rows' log-softmaxes (mh_guidance_mix) before the bans,
+the warpers and the selection.  With a KV cache the two sequences are the two rows of ONE cache (engine.pair_cache), so a step streams the
+weights once: a B = 2 decode step (or a [2, T] verify step) plus one mix launch.  _resolve_guidance, _uncond_context and _guided_ref are
+the host side as pure functions.
 """
 from __future__ import annotations
 
@@ -177,7 +185,8 @@ def _resolve_lengths(prompt_len, max_new_tokens, max_length):
 _DEFAULTS = dict(max_new_tokens=None, max_length=None, eos_token_id=None, pad_token_id=None, do_sample=False, temperature=1.0, top_k=50,
                  top_p=1.0, num_beams=1, length_penalty=1.0, early_stopping=False, use_cache=True, prompt_lookup_num_tokens=None,
                  max_matching_ngram_size=2, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None,
-                 begin_suppress_tokens=None, min_p=None, epsilon_cutoff=0.0)
+                 begin_suppress_tokens=None, min_p=None, epsilon_cutoff=0.0, guidance_scale=None, negative_prompt_ids=None,
+                 negative_prompt_attention_mask=None)
 # options that are accepted only at the value that leaves the implemented modes unchanged (anything else is a decoding mode the
 # reference's scripts never reach: refuse it instead of silently returning something different)
 _NEUTRAL = dict(repetition_penalty=(1.0, None), num_return_sequences=(1, None), num_beam_groups=(1, None),
@@ -187,7 +196,7 @@ _NEUTRAL = dict(repetition_penalty=(1.0, None), num_return_sequences=(1, None), 
                 encoder_no_repeat_ngram_size=(0, None), diversity_penalty=(0.0, None), eta_cutoff=(0.0, None),
                 renormalize_logits=(False, None), forced_bos_token_id=(None,), forced_eos_token_id=(None,), sequence_bias=(None,),
                 assistant_model=(None,), synced_gpus=(False, None),
-                bos_token_id=None, use_beam_search=None, negative_prompt_ids=(None,), num_assistant_tokens=None, trust_remote_code=None)
+                bos_token_id=None, use_beam_search=None, num_assistant_tokens=None, trust_remote_code=None)
 
 
 def _resolve_options(generation_config, kw):
@@ -258,6 +267,63 @@ def _validate_constraints(opt):
     if isinstance(e, bool) or not isinstance(e, (int, float)) or not 0 <= e < 1:
         raise ValueError(f"`epsilon_cutoff` has to be a float > 0 and < 1, but is {e}")
     opt["epsilon_cutoff"] = float(e)
+    g = opt["guidance_scale"]
+    if g is not None:
+        if isinstance(g, bool) or not isinstance(g, (int, float)) or g != g or g in (float("inf"), float("-inf")):
+            raise ValueError(f"`guidance_scale` has to be a real number (1 or None: off), but is {g!r}")
+        opt["guidance_scale"] = None if g == 1 else float(g)  # (transformers adds the processor only when the scale is not None and != 1)
+
+
+def _resolve_guidance(opt, negative_images=None, session=None, input_ids=None, attention_mask=None):
+    """Classifier-free guidance of one call, from the resolved options: None when it is off, else dict(scale, ids, images) - ids the negative
+    prompt int64 [1, Pn], or None for transformers' default (the prompt's last token alone), images its images.  Everything that cannot be
+    served is refused here by name, before any device work: first what needs no tensor (a negative prompt without guidance - nothing is
+    silently dropped -, num_beams > 1, session, prompt_lookup_num_tokens > 7), then the shapes (one un-padded prompt, one un-padded negative
+    prompt).  A pure function of host data."""
+    g, neg, nam = opt["guidance_scale"], opt["negative_prompt_ids"], opt["negative_prompt_attention_mask"]
+    if g is None:
+        for name, v in (("negative_prompt_ids", neg), ("negative_prompt_attention_mask", nam), ("negative_images", negative_images)):
+            if v is not None:
+                raise ValueError(f"`{name}` is given but guidance is off (`guidance_scale` is None or 1): it would be dropped")
+        return None
+    if opt["num_beams"] > 1:
+        raise ValueError("`guidance_scale` cannot be combined with num_beams > 1 (beam search applies the processors to log-probabilities that "
+                         "must not be renormalised: a different flow)")
+    if session is not None:
+        raise ValueError("`guidance_scale` cannot be combined with session=: a session holds one sequence, guidance decodes two")
+    k = opt["prompt_lookup_num_tokens"]
+    if _is_int(k) and k > 7:  # (anything that is no count is refused by the lookup's own check)
+        raise ValueError(f"prompt_lookup_num_tokens = {k} with `guidance_scale`: the verify step runs 2 x (k + 1) rows of at most 16, so k <= 7")
+    if input_ids.shape[0] != 1:
+        raise ValueError(f"`guidance_scale` takes batch_size = 1 (transformers' processor is unbatched too), input_ids has batch_size = {input_ids.shape[0]}")
+    if attention_mask is not None and not bool(torch.as_tensor(attention_mask).to(torch.bool).all()):
+        raise ValueError("`guidance_scale` takes an un-padded prompt (attention_mask with zeros)")
+    if neg is None:
+        for name, v in (("negative_prompt_attention_mask", nam), ("negative_images", negative_images)):
+            if v is not None:
+                raise ValueError(f"`{name}` is given without `negative_prompt_ids` (the default negative prompt is the prompt's last token)")
+        return dict(scale=g, ids=None, images=None)
+    if not isinstance(neg, torch.Tensor) or neg.dim() != 2 or neg.shape[0] != 1 or neg.shape[1] < 1 or neg.dtype != torch.int64:
+        raise ValueError(f"`negative_prompt_ids` has to be an int64 tensor [1, Pn >= 1], but is {tuple(neg.shape) if isinstance(neg, torch.Tensor) else type(neg).__name__}")
+    if nam is not None:
+        nam = torch.as_tensor(nam)
+        if tuple(nam.shape) != tuple(neg.shape) or not bool(nam.to(torch.bool).all()):
+            raise ValueError("`negative_prompt_attention_mask` has to be all ones in the shape of `negative_prompt_ids`: a padded negative prompt is refused")
+    return dict(scale=g, ids=neg, images=negative_images)
+
+
+def _uncond_context(negative_ids, prompt_ids, new_tokens):
+    """The unconditional sequence of a guided step, as a list of ints: the negative prompt (None: the prompt's last token, transformers'
+    default) followed by every token generated so far."""
+    head = [int(prompt_ids[-1])] if negative_ids is None else [int(t) for t in negative_ids]
+    return head + [int(t) for t in new_tokens]
+
+
+def _guided_ref(cond, uncond, g):
+    """The guided scores of raw logits cond, uncond [..., V] in their own dtype: lu + g (lc - lu), lc / lu their log-softmaxes (transformers'
+    UnbatchedClassifierFreeGuidanceLogitsProcessor; the restatement mh_guidance_mix is tested against)."""
+    lc, lu = torch.log_softmax(cond, dim=-1), torch.log_softmax(uncond, dim=-1)
+    return g * (lc - lu) + lu
 
 
 def _pack_words(words):
@@ -323,7 +389,7 @@ def _ban_tables(plan, eos_ids, P, dev):
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, negative_images=None, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
@@ -348,7 +414,18 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     stopping criteria are handed at that step: the call's whole prompt, its pads wherever they sit, then the new tokens - also with a
     session, however much of the prompt came from its cache.  min_p and epsilon_cutoff (do_sample=True only) follow top-p.  All of these
     work on the logits alone, so they compose with every mode and with use_graph, use_cache=False, prompt_lookup_num_tokens, fp8_kv,
-    fp8_weights, fp4_weights, share_prompt_kv and sessions without further work."""
+    fp8_weights, fp4_weights, share_prompt_kv and sessions without further work.
+    Classifier-free guidance - guidance_scale=g (a real number; None or 1: off, and every path runs and launches as without it), with
+    transformers' semantics: the scores of a step are lu + g (lc - lu), lc the log-softmax of the logits given the prompt and lu given the
+    unconditional context, which is negative_prompt_ids [1, Pn] (negative_prompt_attention_mask: all ones or None; default: the prompt's
+    last token) followed by every generated token; the bans, the warpers and the selection act on these scores, greedy takes their argmax.
+    negative_images: the images whose spans lie in the negative prompt, in the form of `images` (None: text only) - e.g. the prompt with
+    its image against the same text without it.  One un-padded prompt; greedy and sampling (selection key (seed, step, row 0)); with
+    use_cache the two sequences share one B = 2 cache (engine.pair_cache: one pass over the weights per token, plus one mh_guidance_mix
+    launch), use_cache=False runs two forwards per token; composes with use_graph, fp8_kv, fp8_weights, fp4_weights, the bans, min_p,
+    epsilon_cutoff, streamer and stopping criteria (both see the conditional ids only) and prompt_lookup_num_tokens <= 7 (2 (k + 1) <= 16
+    verify rows).  Refused by name: num_beams > 1, session=, batch_size > 1, a padded prompt or negative prompt, and a negative prompt or
+    negative_images while guidance is off.  engine.last_generate_stats["guided_steps"]: the steps whose scores were mixed."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
@@ -363,6 +440,7 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         raise ValueError("share_prompt_kv=True shares the prompt's KV cache among the beams of beam search: it needs num_beams > 1")
     if share_prompt_kv and num_beams > 16:
         raise ValueError("share_prompt_kv=True takes num_beams <= 16 (the beams of a prompt are one query tile of the attention kernel)")
+    guide = _resolve_guidance(o, negative_images, session, input_ids, attention_mask)  # (refusals by name, before any device work)
     if session is not None:  # a session continues ONE un-padded sequence on its own KV cache: refused before any device work otherwise
         if input_ids.shape[0] != 1:
             raise ValueError(f"session: a session holds one sequence, input_ids has batch_size = {input_ids.shape[0]}")
@@ -412,18 +490,21 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     if streamer is not None:
         streamer.put(input_ids.cpu())
     stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
+    gkw = {} if guide is None else dict(guide=guide)  # (without guidance the modes get the arguments they always got)
     if getattr(model, "engine", None) is not None:
         model.engine.last_generate_stats = stats
     skw = {} if session is None else dict(session=session)  # (without a session the modes get the arguments they always got)
     if lookup is not None:
         out = _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                             fp4_weights, lookup, max_ngram, stats, **skw, **bkw)
+                             fp4_weights, lookup, max_ngram, stats, **skw, **bkw, **gkw)
     elif not use_cache:
-        out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer, **bkw)
+        out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer, **bkw, **gkw)
     else:
         out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights,
-                             **skw, **bkw)
+                             **skw, **bkw, **gkw)
         stats["plain_steps"] = max(0, out.shape[1] - input_ids.shape[1] - 1)  # every new token but the first (the prefill's) is one decode step
+    if guide is not None:  # (a key of guided calls only) the prefill pair, then every decode and verify step (use_cache=False: every forward pair)
+        stats["guided_steps"] = 1 + stats["plain_steps"] + stats["verify_steps"] if use_cache else out.shape[1] - input_ids.shape[1]
     if session is not None:
         stats.update(session.last)
     if streamer is not None:
@@ -437,8 +518,18 @@ def _select(logits, V, sel, step):
                            seed=sel["seed"], step=step, **extra)
 
 
-def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer=None, bans=None):
-    """use_cache=False: full-sequence forward per token (the cross-check of the cached path)."""
+def _guided_prefill(eng, guide, input_ids, images, room, fp8_kv, V):
+    """The guided form of engine.prefill: the prompt and the unconditional context prefilled one after the other, their caches paired
+    (engine.pair_cache: row 0 conditional, row 1 unconditional, `room` free rows behind the longer one) -> (guided scores fp32 [1, >= V],
+    the B = 2 cache)."""
+    lc, cc = eng.prefill(input_ids, None, images, 0, kv_fp8=fp8_kv)
+    lu, cu = eng.prefill(guide["ids"] if guide["ids"] is not None else input_ids[:, -1:], None, guide["images"], 0, kv_fp8=fp8_kv)
+    return O.guidance_mix(lc, lu, guide["scale"], V, out=lc), eng.pair_cache(cc, cu, room)
+
+
+def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer=None, bans=None, guide=None):
+    """use_cache=False: full-sequence forward per token (the cross-check of the cached path).  guide: a second forward on the
+    unconditional context per token, then the mix."""
     V = model.config.vocab_size
     unfinished = torch.ones(ids.shape[0], dtype=torch.bool, device=ids.device)
     step = 0
@@ -447,6 +538,11 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
     while True:
         out = model.forward(input_ids=ids, attention_mask=attention_mask, images=images)
         logits = out.logits[:, -1, :].float().contiguous()
+        if guide is not None:
+            neg = None if guide["ids"] is None else guide["ids"][0].tolist()
+            un = torch.tensor([_uncond_context(neg, ids[0, :P].tolist(), ids[0, P:].tolist())], dtype=torch.int64, device=ids.device)
+            un = model.forward(input_ids=un, images=guide["images"]).logits[:, -1, :].float().contiguous()
+            O.guidance_mix(logits, un, guide["scale"], V, out=logits)
         if bans is not None:
             if tables is None:  # the history lives on the logits' device in one [B, max_len] buffer
                 tables = _ban_tables(bans[0], bans[1], P, logits.device)
@@ -470,12 +566,15 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
 
 
 def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False,
-                   session=None, bans=None):
+                   session=None, bans=None, guide=None):
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
-    if session is not None:
+    if guide is not None:  # one sequence to the caller; rows (conditional, unconditional) to the decode step
+        logits, cache = _guided_prefill(eng, guide, input_ids, images, max_new, fp8_kv, V)
+        attention_mask = None  # (all ones, or guidance is refused)
+    elif session is not None:
         logits, cache = session._prefill(input_ids, images, max_new)
     else:
         logits, cache = eng.prefill(input_ids, attention_mask, images, max_new, kv_fp8=fp8_kv)
@@ -517,11 +616,13 @@ def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, p
         if not bool(unfinished.any()) or step + 1 == max_new:
             break
         if graph is not None:
-            g_tok.copy_(nxt)
+            g_tok.copy_(nxt)  # (guided: the one token goes to both rows)
             graph.replay()
             logits = g_logits
         else:
-            logits = eng.decode_step(nxt, cache, fp8=fp8_weights, fp4=fp4_weights)
+            logits = eng.decode_step(nxt if guide is None else nxt.repeat(2), cache, fp8=fp8_weights, fp4=fp4_weights)
+        if guide is not None:  # row 0 becomes the guided scores, in place; the bans and the selection see that row alone
+            logits = O.guidance_mix(logits[:1], logits[1:], guide["scale"], V, out=logits[:1])
     if padded:  # right-padded prompts (an extension; HF wants left padding): each row's continuation starts at its own length
         cur = _compact(ids, lens, torch.stack(new, dim=1), pad)
     if session is not None:
@@ -568,17 +669,23 @@ def _accept(draft, selected, room, stops):
 
 
 def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                   fp4_weights, k, max_ngram, stats, session=None, bans=None):
+                   fp4_weights, k, max_ngram, stats, session=None, bans=None, guide=None):
     """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
     (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
     once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
-    one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step."""
+    one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step.
+    guide: the steps run on the paired cache with the same tokens in both rows ([2, T] verify rows, 2 T <= 16), row pair t is mixed into
+    conditional row t before the bans and the selection, and both sequences keep the same accepted count."""
     eng = model.engine
     B, P = input_ids.shape
     V = model.config.vocab_size
     max_new = max_len - P
     T = k + 1
-    if session is not None:
+    R = 1 if guide is None else 2  # rows of a step: the sequence, or (conditional, unconditional)
+    if guide is not None:
+        logits, cache = _guided_prefill(eng, guide, input_ids, images, max_new + k, fp8_kv, V)
+        attention_mask = None  # (all ones, or guidance is refused)
+    elif session is not None:
         logits, cache = session._prefill(input_ids, images, max_new + k)
     else:
         logits, cache = eng.prefill(input_ids, attention_mask, images, max_new + k, kv_fp8=fp8_kv)  # k rows of room for a rejected draft's tail
@@ -627,13 +734,15 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
                 graph.replay()
                 logits = g_logits
             else:
-                logits = eng.decode_step(last, cache, fp8=fp8_weights, fp4=fp4_weights)
+                logits = eng.decode_step(last if guide is None else last.repeat(2), cache, fp8=fp8_weights, fp4=fp4_weights)
+            if guide is not None:
+                logits = O.guidance_mix(logits[:1], logits[1:], guide["scale"], V, out=logits[:1])
             stats["plain_steps"] += 1
             if tables is not None:
                 O.ban_tokens(logits, V, seq, len0=n, **tables)
             out, _, stopped = emit(_select(logits, V, sel, emitted).tolist(), [])
             continue
-        toks = v_tok if vgraph is not None else torch.empty(1, T, dtype=torch.int64, device=dev)
+        toks = v_tok if vgraph is not None else torch.empty(R, T, dtype=torch.int64, device=dev)
         toks[:, 0] = last
         toks[:, 1:] = pad  # a short draft is padded to the step's k + 1 rows; their logits are not looked at
         toks[:, 1:1 + c] = draft_dev[:, :c]
@@ -642,6 +751,9 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
             logits = v_logits
         else:
             logits = eng.verify_step(toks, cache, fp8=fp8_weights, fp4=fp4_weights)
+        if guide is not None:  # rows t and T + t of the step's buffer -> conditional row t, in place
+            O.guidance_mix(logits[0], logits[1], guide["scale"], V, out=logits[0])
+            logits = logits[:1]
         if tables is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
             seq[0, n:n + c] = draft_dev[0, :c]
             O.ban_tokens(logits[0], V, seq, len0=n, len_step=1, ld_ids=0, **tables)

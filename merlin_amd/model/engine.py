@@ -1552,6 +1552,28 @@ class HipEngine:
         out.lens.copy_(cache.lens.expand(nb))
         return out
 
+    def pair_cache(self, cond_cache, uncond_cache, max_new):
+        """A plain KVCache of B = 2 for guided decoding (generate(guidance_scale=...)): row 0 holds the rows of the conditional prompt's
+        cache, row 1 the unconditional's, lens per row, Smax = max(len) + max_new, the format of its inputs (16-bit, or fp8 with ks / vs).
+        Both inputs are one-sequence, un-padded caches of one format.  Once per call, plain copies; the inputs are not written.
+        decode_step and verify_step run on it like on any right-padded batch."""
+        pair = (cond_cache, uncond_cache)
+        if any(not isinstance(c, HipEngine.KVCache) or c.B != 1 or c.rpos is not None for c in pair):
+            raise ValueError("pair_cache takes two plain KVCaches of one un-padded sequence each (B = 1, no left padding or holes)")
+        if cond_cache.fp8 != uncond_cache.fp8 or max_new < 0:
+            raise ValueError(f"pair_cache takes two caches of one format and max_new >= 0, got fp8 = {cond_cache.fp8} / {uncond_cache.fp8}, max_new = {max_new}")
+        n = [int(c.lens[0]) for c in pair]
+        out = self.new_cache(2, max(n) + int(max_new), fp8=cond_cache.fp8)
+        for b, (c, P) in enumerate(zip(pair, n)):
+            for li in range(len(c.k)):
+                out.k[li][b, :P].copy_(c.k[li][0, :P])
+                out.v[li][b, :P].copy_(c.v[li][0, :P])
+                if c.fp8:
+                    out.ks[li][b, :, :P].copy_(c.ks[li][0, :, :P])
+                    out.vs[li][b, :, :P].copy_(c.vs[li][0, :, :P])
+        out.lens.copy_(torch.cat([cond_cache.lens, uncond_cache.lens]))
+        return out
+
     def expand_cache(self, cache, rows):
         """New cache whose row i is a copy of `cache` row rows[i] (int64 on the device): a prefilled batch expanded to
         num_beams rows per prompt (the reference: inputs_embeds.repeat_interleave(5), base_mmgpt.py:162-163)."""

@@ -272,7 +272,10 @@ class MMGPTLlamaForCausalLM(nn.Module):
         seed (counter-based sampling stream; default drawn from torch's global generator),
         session (a Session from new_session(): the call continues from the KV cache the session kept - the prefix of the prompt that the
         cache already holds, tokens and image pixels alike, is not run again, and the tower encodes only the images behind it; one
-        un-padded prompt per call; for evaluation loops over one image and for multi-turn chat)."""
+        un-padded prompt per call; for evaluation loops over one image and for multi-turn chat),
+        guidance_scale / negative_prompt_ids / negative_prompt_attention_mask (transformers' classifier-free guidance for decoder-only
+        models: every step's scores are mixed from the prompt's and a negative prompt's log-softmaxes; both sequences share one B = 2 KV
+        cache) and negative_images (the images of the negative prompt's spans)."""
         from ..generation import generate as _generate
 
         return _generate(self, input_ids, images=images, **kwargs)

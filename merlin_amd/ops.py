@@ -1260,6 +1260,21 @@ def log_softmax_rows(logits, V=None, row_bias=None):
     return out
 
 
+def guidance_mix(cond, uncond, scale, V=None, out=None):
+    """Classifier-free guidance (mh_guidance_mix; generation._guided_ref is its restatement): cond, uncond fp32 [R, >=V] (finite raw logits;
+    any row strides - two tensors, or strided views of one buffer) -> out[r, :V] = lu + scale * (lc - lu), lc / lu = log_softmax of the two
+    rows.  out: None (a new [R, V] tensor), `cond` itself (in place) or a third fp32 [R, >=V] buffer; columns >= V and uncond are not
+    written."""
+    R = cond.shape[0]
+    V = cond.shape[1] if V is None else V
+    assert cond.dtype == uncond.dtype == torch.float32 and cond.dim() == uncond.dim() == 2 and cond.stride(1) == uncond.stride(1) == 1
+    assert uncond.shape[0] == R and cond.shape[1] >= V and uncond.shape[1] >= V and cond.device == uncond.device
+    out = torch.empty(R, V, dtype=torch.float32, device=cond.device) if out is None else out
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == R and out.shape[1] >= V and out.device == cond.device
+    L.call("mh_guidance_mix", cond, cond.stride(0), uncond, uncond.stride(0), R, V, float(scale), out, out.stride(0), _stream())
+    return out
+
+
 def token_logprobs(logits, targets, V=None, logprob=None, greedy=None):
     """logits fp32 [R, >=V], targets int64 [R] on the device -> (log_softmax(logits[r, :V])[targets[r]] fp32 [R], targets[r] is the lowest
     index of row r's maximum, int32 [R]) without a [R, V] log-softmax (mh_token_logprobs).  A target outside [0, V): NaN and 0.

@@ -3,7 +3,7 @@ decode steps eagerly and (optionally) as a replayed HIP graph.  Reports ms/token
 (weights + K/V cache streamed once per step).  The graph replay runs with 16-bit, fp8 (e4m3, one scale per 128 k) and MXFP4 (e2m1, one scale
 byte per 32 k) weights in turn; every such line also carries `weights_tb_s`, the weight bytes of its format over the step time.
 
-    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend | --bans | --score]
+    python tools/bench_decode.py [B] [context] [--kv fp8] [--verify | --beams | --extend | --bans | --score | --guidance]
 
 --kv fp8: the KV cache as e4m3 bytes + power-of-two scales (prefill(kv_fp8=True)); the HBM figure counts the bytes of the cache format
 in use.  Every arm also reports the time of one decode-attention launch (mh_attn_decode / mh_attn_decode_kv8 + the split merge), replayed
@@ -42,7 +42,14 @@ through the existing ops, cache.truncate - after session.reset() and on the held
 the lm_head of the other n - 2 rows runs on a stand-in hidden-state buffer: the same launches on the same shapes); (iii) C full forward
 calls of prompt + candidate with the log-softmax of the candidate's rows.  Then the attention launches per layer of (i) and (ii), counted
 at the library boundary, and one mh_attn_extend_branches launch on the R = C (n - 1) packed rows against the C mh_attn_extend launches it
-replaces, each from a graph over the 32 layers' caches."""
+replaces, each from a graph over the 32 layers' caches.
+
+--guidance: the classifier-free guidance arm instead (generate(guidance_scale=g, negative_prompt_ids=...)), B = 1: the plain decode step on
+the prompt's cache against the guided step - the B = 2 step on engine.pair_cache(prompt cache, negative prompt's cache) plus the one
+mh_guidance_mix launch on its two rows of logits, in place, as generate() runs it per token.  The negative prompt is the prompt without
+its first 576 tokens (an image span: context 613 leaves 37 tokens of text).  Both as replayed HIP graphs (the mix launched behind the
+replay) and as eager steps; the four arms alternate step by step in this process (the lengths put back before each), every step between
+its own events, after warm-up; medians, and guided / plain of each pair.  Then the mix launch alone, replayed from a graph of 32."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -80,6 +87,9 @@ if EXTEND:
 BANS = "--bans" in sys.argv
 if BANS:
     sys.argv.remove("--bans")
+GUIDANCE = "--guidance" in sys.argv
+if GUIDANCE:
+    sys.argv.remove("--guidance")
 SCORE = "--score" in sys.argv
 if SCORE:
     sys.argv.remove("--score")
@@ -450,6 +460,61 @@ def bans_arm(logits, cache, warm=6, steps=40):
                       "us_mh_ban_tokens_launch": round(out["mh_ban_tokens"], 2), "us_mh_select_tokens_launch": round(out["mh_select_tokens"], 2)}), flush=True)
 
 
+def guidance_arm(logits, cache, warm=6, steps=40):
+    """Plain B = 1 step against the guided step (B = 2 step on the paired cache + mh_guidance_mix), alternating (module docstring)."""
+    eng = model.engine
+    V, scale = 32000, 1.5
+    neg = ids[:, min(576, S - 1):]
+    _, cu = eng.prefill(neg, None, None, 0, kv_fp8=KV8)
+    pair = eng.pair_cache(cache, cu, NEW + 8)
+    del cu
+    g1, tok1, log1 = eng.capture_decode_graph(cache)
+    g2, tok2, log2 = eng.capture_decode_graph(pair)
+    keep1, keep2 = cache.lens.clone(), pair.lens.clone()
+    tok1.copy_(logits.argmax(-1))
+    tok2.copy_(tok1)  # (broadcast: the one token goes to both rows)
+
+    def step(graph, guided):
+        if guided:
+            lg = (g2.replay() or log2) if graph else eng.decode_step(tok2, pair)
+            _O.guidance_mix(lg[:1], lg[1:], scale, V, out=lg[:1])
+        elif graph:
+            g1.replay()
+        else:
+            eng.decode_step(tok1, cache)
+
+    arms = [(True, False), (True, True), (False, False), (False, True)]
+    ev = {arm: [] for arm in arms}
+    for t in range(warm + steps):
+        for arm in (arms if t % 2 == 0 else arms[::-1]):  # the arms alternate, and so does their order
+            cache.lens.copy_(keep1)
+            pair.lens.copy_(keep2)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            step(*arm)
+            b.record()
+            if t >= warm:
+                ev[arm].append((a, b))
+    torch.cuda.synchronize()
+    ms = {arm: _median([a.elapsed_time(b) for a, b in ev[arm]]) for arm in arms}
+    cache.lens.copy_(keep1)
+    pair.lens.copy_(keep2)
+    x = torch.randn(2, log2.shape[1], device=dev)
+    _O.guidance_mix(x[:1], x[1:], scale, V, out=x[:1])
+    torch.cuda.synchronize()
+    ga = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(ga):
+        for _ in range(32):
+            _O.guidance_mix(x[:1], x[1:], scale, V, out=x[:1])
+    us_mix = _replay_ms(ga, n=8, warm=2) / 32 * 1e3
+    del ga
+    print(json.dumps({"guidance": "B = 2 step on the paired cache + mh_guidance_mix vs the plain B = 1 step", "kv": KV, "context": S, "negative_context": int(neg.shape[1]),
+                      "ms_plain_step_graph": round(ms[(True, False)], 4), "ms_guided_step_graph": round(ms[(True, True)], 4),
+                      "guided_over_plain_graph": round(ms[(True, True)] / ms[(True, False)], 3),
+                      "ms_plain_step_eager": round(ms[(False, False)], 4), "ms_guided_step_eager": round(ms[(False, True)], 4),
+                      "guided_over_plain_eager": round(ms[(False, True)] / ms[(False, False)], 3), "us_mh_guidance_mix_launch": round(us_mix, 2)}), flush=True)
+
+
 with torch.no_grad():
     if EXTEND:
         extend_arm()
@@ -471,6 +536,11 @@ with torch.no_grad():
         if B != 1:
             raise SystemExit("--bans takes B = 1")
         bans_arm(logits, cache)
+        sys.exit(0)
+    if GUIDANCE:
+        if B != 1:
+            raise SystemExit("--guidance takes B = 1")
+        guidance_arm(logits, cache)
         sys.exit(0)
     tok = logits.argmax(-1)
     for _ in range(3):
