@@ -35,6 +35,8 @@ the host side as pure functions.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
 from . import ops as O
@@ -387,6 +389,34 @@ def _ban_tables(plan, eos_ids, P, dev):
     return kw
 
 
+@dataclass
+class _Call:
+    """One generate() call with its arguments resolved once: everything a decoding loop needs, nothing it has to decide again."""
+    model: object
+    images: object
+    attention_mask: object
+    max_len: int
+    eos_ids: list
+    pad: int
+    stop: _Stopper
+    sel: dict = None             # the selection's arguments (_select); None: beam search
+    streamer: object = None
+    use_graph: bool = True
+    fp8_weights: bool = False    # the decode step's weight format: at most one of the two
+    fp4_weights: bool = False
+    fp8_kv: bool = False
+    session: Session = None
+    bans: dict = None            # _ban_plan; None: the call bans nothing
+    guide: dict = None           # _resolve_guidance; None: guidance is off
+    stats: dict = None           # engine.last_generate_stats of the call (greedy search and sampling)
+    lookup: int = None           # prompt_lookup_num_tokens and, with it, max_matching_ngram_size
+    max_ngram: int = None
+    num_beams: int = 1
+    length_penalty: float = 1.0
+    early_stopping: object = False
+    share_prompt_kv: bool = False
+
+
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
              use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, negative_images=None, **kw):
@@ -471,37 +501,37 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         return input_ids
     if seed is None:  # torch.manual_seed governs the stream, like HF's torch.multinomial
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if do_sample else 0
-    stop = _Stopper(max_len, eos_ids, stopping_criteria)
-    plan = _ban_plan(o, eos_ids)
-    bkw = {} if plan is None else dict(bans=(plan, eos_ids))  # (without bans the modes get the arguments they always got)
-    if num_beams > 1:
+    beams = num_beams > 1
+    if beams:
         if do_sample:
             raise NotImplementedError("beam-sample is not one of the reference's decoding modes (eval scripts: num_beams=5, do_sample unset)")
         if streamer is not None:  # (transformers raises the same way)
             raise ValueError("`streamer` cannot be used with beam search. Make sure that `num_beams` is set to 1.")
         if attention_mask is not None and not bool(attention_mask.to(torch.bool).all()):
             raise NotImplementedError("beam search takes un-padded prompts (the reference's eval scripts decode one prompt at a time)")
-        skw = {} if session is None else dict(session=session)
-        return _beam_search(model, input_ids, images, num_beams, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv, fp4_weights,
-                            share_prompt_kv=bool(share_prompt_kv), **skw, **bkw)
-    sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
-    if do_sample and (o["min_p"] is not None or o["epsilon_cutoff"] > 0.0):
-        sel.update(min_p=o["min_p"], epsilon_cutoff=o["epsilon_cutoff"])
+        sel = stats = None
+    else:
+        sel = dict(do_sample=bool(do_sample), temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p), seed=seed)
+        if do_sample and (o["min_p"] is not None or o["epsilon_cutoff"] > 0.0):
+            sel.update(min_p=o["min_p"], epsilon_cutoff=o["epsilon_cutoff"])
+        stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
+    call = _Call(model=model, images=images, attention_mask=None if beams else attention_mask,  # (beam search: all ones, as checked)
+                 max_len=max_len, eos_ids=eos_ids, pad=pad, stop=_Stopper(max_len, eos_ids, stopping_criteria), sel=sel, streamer=streamer,
+                 use_graph=use_graph, fp8_weights=bool(fp8_weights), fp4_weights=bool(fp4_weights), fp8_kv=bool(fp8_kv), session=session,
+                 bans=_ban_plan(o, eos_ids), guide=guide, stats=stats, lookup=lookup, max_ngram=None if lookup is None else max_ngram,
+                 num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping, share_prompt_kv=bool(share_prompt_kv))
+    if beams:
+        return _beam_search(call, input_ids)
     if streamer is not None:
         streamer.put(input_ids.cpu())
-    stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
-    gkw = {} if guide is None else dict(guide=guide)  # (without guidance the modes get the arguments they always got)
     if getattr(model, "engine", None) is not None:
         model.engine.last_generate_stats = stats
-    skw = {} if session is None else dict(session=session)  # (without a session the modes get the arguments they always got)
     if lookup is not None:
-        out = _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                             fp4_weights, lookup, max_ngram, stats, **skw, **bkw, **gkw)
+        out = _sample_lookup(call, input_ids)
     elif not use_cache:
-        out = _sample_recompute(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer, **bkw, **gkw)
+        out = _sample_recompute(call, input_ids)
     else:
-        out = _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer, fp4_weights,
-                             **skw, **bkw, **gkw)
+        out = _sample_cached(call, input_ids)
         stats["plain_steps"] = max(0, out.shape[1] - input_ids.shape[1] - 1)  # every new token but the first (the prefill's) is one decode step
     if guide is not None:  # (a key of guided calls only) the prefill pair, then every decode and verify step (use_cache=False: every forward pair)
         stats["guided_steps"] = 1 + stats["plain_steps"] + stats["verify_steps"] if use_cache else out.shape[1] - input_ids.shape[1]
@@ -513,9 +543,9 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
 
 
 def _select(logits, V, sel, step):
-    extra = {key: sel[key] for key in ("min_p", "epsilon_cutoff") if key in sel}
-    return O.select_tokens(logits, V, do_sample=sel["do_sample"], temperature=sel["temperature"], top_k=sel["top_k"], top_p=sel["top_p"],
-                           seed=sel["seed"], step=step, **extra)
+    """sel: the selection kernel's keyword arguments as generate() resolved them (do_sample, temperature, top_k, top_p, seed and, only
+    where they are set, min_p and epsilon_cutoff)."""
+    return O.select_tokens(logits, V, step=step, **sel)
 
 
 def _guided_prefill(eng, guide, input_ids, images, room, fp8_kv, V):
@@ -527,9 +557,11 @@ def _guided_prefill(eng, guide, input_ids, images, room, fp8_kv, V):
     return O.guidance_mix(lc, lu, guide["scale"], V, out=lc), eng.pair_cache(cc, cu, room)
 
 
-def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, streamer=None, bans=None, guide=None):
+def _sample_recompute(call, ids):
     """use_cache=False: full-sequence forward per token (the cross-check of the cached path).  guide: a second forward on the
     unconditional context per token, then the mix."""
+    model, images, attention_mask, max_len, eos_ids, pad = call.model, call.images, call.attention_mask, call.max_len, call.eos_ids, call.pad
+    stop, sel, streamer, bans, guide = call.stop, call.sel, call.streamer, call.bans, call.guide
     V = model.config.vocab_size
     unfinished = torch.ones(ids.shape[0], dtype=torch.bool, device=ids.device)
     step = 0
@@ -545,7 +577,7 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
             O.guidance_mix(logits, un, guide["scale"], V, out=logits)
         if bans is not None:
             if tables is None:  # the history lives on the logits' device in one [B, max_len] buffer
-                tables = _ban_tables(bans[0], bans[1], P, logits.device)
+                tables = _ban_tables(bans, eos_ids, P, logits.device)
                 hist = torch.full((ids.shape[0], max_len), pad, dtype=torch.int64, device=logits.device)
                 hist[:, :P] = ids
             O.ban_tokens(logits, V, hist, len0=P + step, **tables)
@@ -565,69 +597,126 @@ def _sample_recompute(model, ids, images, attention_mask, max_len, eos_ids, pad,
             return ids
 
 
-def _sample_cached(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv=False, streamer=None, fp4_weights=False,
-                   session=None, bans=None, guide=None):
-    eng = model.engine
-    B, P = input_ids.shape
-    V = model.config.vocab_size
-    max_new = max_len - P
-    if guide is not None:  # one sequence to the caller; rows (conditional, unconditional) to the decode step
-        logits, cache = _guided_prefill(eng, guide, input_ids, images, max_new, fp8_kv, V)
-        attention_mask = None  # (all ones, or guidance is refused)
-    elif session is not None:
-        logits, cache = session._prefill(input_ids, images, max_new)
-    else:
-        logits, cache = eng.prefill(input_ids, attention_mask, images, max_new, kv_fp8=fp8_kv)
-    dev = logits.device
-    graph = None
-    if use_graph and logits.is_cuda and max_new > 2:
-        graph, g_tok, g_logits = eng.capture_decode_graph(cache, fp8=fp8_weights, fp4=fp4_weights)  # the decode step as one replayable HIP graph
-    am = attention_mask.to(dev).to(torch.bool) if attention_mask is not None else None
-    # right-padded prompts (ones then zeros; an extension - HF wants left padding): each row continues from its own length.
-    # Anything else (HF's left padding, holes) follows transformers: new tokens are appended after the padded prompt, keys are the
-    # valid positions only, rotary positions stay absolute (the engine's unpad / pad attention path + compacted KV cache).
-    # ONE decision, the engine's (made on the device from the mask in forward(): a right-padded prefix keeps the lens fast path, anything
-    # else - or engine.force_unpad - compacts the valid keys and sets cache.rpos): generate() follows it instead of classifying again
-    padded = am is not None and not bool(am.all()) and cache.rpos is None
-    ids = input_ids.to(dev)
-    lens = am.sum(dim=1) if padded else None
-    unfinished = torch.ones(B, dtype=torch.bool, device=dev)
-    new = []
-    hist = None
-    if bans is not None:  # the sequence as the criteria see it, kept on the device in one buffer: what mh_ban_tokens reads
-        tables = _ban_tables(bans[0], bans[1], P, dev)
-        hist = torch.full((B, max_len), pad, dtype=torch.int64, device=dev)
-        hist[:, :P] = ids
-    for step in range(max_new):
-        if hist is not None:
-            O.ban_tokens(logits, V, hist, len0=P + step, **tables)
-        nxt = _select(logits, V, sel, step)
-        if eos_ids:
-            nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
-        new.append(nxt)
-        if streamer is not None:
-            streamer.put(nxt.cpu())
-        if hist is not None:
-            hist[:, P + step] = nxt
-            cur = hist[:, :P + step + 1]
+class _Stepper:
+    """What the loops on a KV cache share, built from the resolved call: the prefill choice, graph capture, the decode and the verify step
+    with the guided mix, the ban launch on tables built once, and the ids buffer of the two sampling loops.  The loops keep their policy."""
+
+    def __init__(self, call):
+        self.call, self.eng, self.V = call, call.model.engine, call.model.config.vocab_size
+        self.weights = dict(fp8=call.fp8_weights, fp4=call.fp4_weights)
+        self.cache = self.graph = self.vgraph = self.tables = self.lens = None
+
+    def prefill(self, input_ids, room):
+        """The prompt into a cache with `room` free rows behind it - the guided pair, the session's cache or a new one -> the scores that
+        select the first token; the cache is self.cache."""
+        c = self.call
+        if c.guide is not None:  # one sequence to the caller; rows (conditional, unconditional) to the decode step
+            logits, self.cache = _guided_prefill(self.eng, c.guide, input_ids, c.images, room, c.fp8_kv, self.V)
+        elif c.session is not None:
+            logits, self.cache = c.session._prefill(input_ids, c.images, room)
         else:
-            cur = torch.cat([ids, torch.stack(new, dim=1)], dim=1)  # (right-padded prompts: criteria see the pads in the middle)
-        unfinished = unfinished & ~stop(cur, None)
+            logits, self.cache = self.eng.prefill(input_ids, c.attention_mask, c.images, room, kv_fp8=c.fp8_kv)
+        self.input_ids, self.P, self.logits0 = input_ids, input_ids.shape[1], logits
+        if c.bans is not None:
+            self.tables = _ban_tables(c.bans, c.eos_ids, self.P, logits.device)
+        return logits
+
+    def capture(self, T=0):
+        """The decode step as one replayable HIP graph on self.cache and, T >= 1 (the lookup loop), the [rows, T] verify step as another."""
+        c = self.call
+        if c.use_graph and self.logits0.is_cuda and c.max_len - self.P > 2:
+            self.graph, self.g_tok, self.g_logits = self.eng.capture_decode_graph(self.cache, **self.weights)
+            if T:
+                self.vgraph, self.v_tok, self.v_logits = self.eng.capture_verify_graph(self.cache, T, **self.weights)
+
+    def ids_buffer(self, cells):
+        """The sequence as the criteria, the bans and the drafter see it, in one preallocated buffer [B, cells] on the device: the prompt,
+        pads behind it.
+        Right-padded prompts (ones then zeros; an extension - HF wants left padding): each row continues from its own length, the criteria
+        see the pads in the middle and finish() compacts.  Anything else (HF's left padding, holes) follows transformers: new tokens are
+        appended after the padded prompt, keys are the valid positions only, rotary positions stay absolute (the engine's unpad / pad
+        attention path + compacted KV cache).  ONE decision, the engine's (made on the device from the mask in forward(): a right-padded
+        prefix keeps the lens fast path, anything else - or engine.force_unpad - compacts the valid keys and sets cache.rpos): generate()
+        follows it instead of classifying again."""
+        c, dev = self.call, self.logits0.device
+        if c.attention_mask is not None and c.guide is None:  # (guided: all ones, or guidance is refused)
+            am = c.attention_mask.to(dev).to(torch.bool)
+            if not bool(am.all()) and self.cache.rpos is None:
+                self.lens = am.sum(dim=1)
+        self.seq = torch.full((self.input_ids.shape[0], cells), c.pad, dtype=torch.int64, device=dev)
+        self.seq[:, :self.P] = self.input_ids.to(dev)
+        return self.seq
+
+    def step(self, tokens):
+        """One decode step on tokens int64 [B] (guided: the one token goes to both rows) -> the scores of the next token."""
+        guide = self.call.guide
+        if self.graph is not None:
+            self.g_tok.copy_(tokens)
+            self.graph.replay()
+            logits = self.g_logits
+        else:
+            logits = self.eng.decode_step(tokens if guide is None else tokens.repeat(2), self.cache, **self.weights)
+        if guide is not None:  # row 0 becomes the guided scores, in place; the bans and the selection see that row alone
+            logits = O.guidance_mix(logits[:1], logits[1:], guide["scale"], self.V, out=logits[:1])
+        return logits
+
+    def verify(self, last, draft, c):
+        """One verify step of T rows per cache row on `last` [1] followed by the c drafted tokens draft[:, :c] -> scores [1, T, >= V]; does
+        not advance the cache.  A short draft is padded to the step's T rows; their scores are not looked at."""
+        call, guide = self.call, self.call.guide
+        toks = self.v_tok if self.vgraph is not None else torch.empty(self.cache.B, call.lookup + 1, dtype=torch.int64, device=last.device)
+        toks[:, 0] = last
+        toks[:, 1:] = call.pad
+        toks[:, 1:1 + c] = draft[:, :c]
+        if self.vgraph is not None:
+            self.vgraph.replay()
+            logits = self.v_logits
+        else:
+            logits = self.eng.verify_step(toks, self.cache, **self.weights)
+        if guide is not None:  # rows t and T + t of the step's buffer -> conditional row t, in place
+            O.guidance_mix(logits[0], logits[1], guide["scale"], self.V, out=logits[0])
+            logits = logits[:1]
+        return logits
+
+    def ban(self, logits, len0, ids=None, **kw):
+        """-inf into the banned columns of the step's scores given the sequences ids (default: the ids buffer) of length len0: ONE
+        mh_ban_tokens launch; nothing when the call bans nothing."""
+        if self.tables is not None:
+            O.ban_tokens(logits, self.V, self.seq if ids is None else ids, len0=len0, **kw, **self.tables)
+
+    def finish(self, n):
+        """The first n cells of the ids buffer as the call's result; a session keeps what was fed."""
+        c, P = self.call, self.P
+        cur = self.seq[:, :n]
+        if self.lens is not None:  # right-padded prompts: each row's continuation starts at its own length
+            cur = _compact(self.seq[:, :P], self.lens, self.seq[:, P:n], c.pad)
+        if c.session is not None:  # (the last emitted token was never fed to the decoder, a rejected draft's tail is behind cache.lens)
+            c.session._fed(cur)
+        return cur.to(self.input_ids.device).contiguous()
+
+
+def _sample_cached(call, input_ids):
+    """Greedy search / sampling on the KV cache: one decode step per token."""
+    c, st = call, _Stepper(call)
+    B, P = input_ids.shape
+    max_new = c.max_len - P
+    logits = st.prefill(input_ids, max_new)
+    st.capture()
+    seq = st.ids_buffer(c.max_len)
+    unfinished = torch.ones(B, dtype=torch.bool, device=seq.device)
+    for step in range(max_new):
+        st.ban(logits, P + step)
+        nxt = _select(logits, st.V, c.sel, step)
+        if c.eos_ids:
+            nxt = torch.where(unfinished, nxt, torch.full_like(nxt, c.pad))
+        if c.streamer is not None:
+            c.streamer.put(nxt.cpu())
+        seq[:, P + step] = nxt
+        unfinished = unfinished & ~c.stop(seq[:, :P + step + 1], None)
         if not bool(unfinished.any()) or step + 1 == max_new:
             break
-        if graph is not None:
-            g_tok.copy_(nxt)  # (guided: the one token goes to both rows)
-            graph.replay()
-            logits = g_logits
-        else:
-            logits = eng.decode_step(nxt if guide is None else nxt.repeat(2), cache, fp8=fp8_weights, fp4=fp4_weights)
-        if guide is not None:  # row 0 becomes the guided scores, in place; the bans and the selection see that row alone
-            logits = O.guidance_mix(logits[:1], logits[1:], guide["scale"], V, out=logits[:1])
-    if padded:  # right-padded prompts (an extension; HF wants left padding): each row's continuation starts at its own length
-        cur = _compact(ids, lens, torch.stack(new, dim=1), pad)
-    if session is not None:
-        session._fed(cur)  # (the last emitted token was never fed to the decoder: it is not in the cache)
-    return cur.to(input_ids.device)
+        logits = st.step(nxt)
+    return st.finish(P + step + 1)
 
 
 def _prompt_lookup(ids, k, max_ngram, max_length):
@@ -668,41 +757,21 @@ def _accept(draft, selected, room, stops):
     return out, a, stopped
 
 
-def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, pad, stop, sel, use_graph, fp8_weights, fp8_kv, streamer,
-                   fp4_weights, k, max_ngram, stats, session=None, bans=None, guide=None):
+def _sample_lookup(call, input_ids):
     """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
     (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
     once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
     one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step.
     guide: the steps run on the paired cache with the same tokens in both rows ([2, T] verify rows, 2 T <= 16), row pair t is mixed into
     conditional row t before the bans and the selection, and both sequences keep the same accepted count."""
-    eng = model.engine
-    B, P = input_ids.shape
-    V = model.config.vocab_size
-    max_new = max_len - P
-    T = k + 1
-    R = 1 if guide is None else 2  # rows of a step: the sequence, or (conditional, unconditional)
-    if guide is not None:
-        logits, cache = _guided_prefill(eng, guide, input_ids, images, max_new + k, fp8_kv, V)
-        attention_mask = None  # (all ones, or guidance is refused)
-    elif session is not None:
-        logits, cache = session._prefill(input_ids, images, max_new + k)
-    else:
-        logits, cache = eng.prefill(input_ids, attention_mask, images, max_new + k, kv_fp8=fp8_kv)  # k rows of room for a rejected draft's tail
-    dev = logits.device
-    graph = vgraph = None
-    if use_graph and logits.is_cuda and max_new > 2:
-        graph, g_tok, g_logits = eng.capture_decode_graph(cache, fp8=fp8_weights, fp4=fp4_weights)
-        vgraph, v_tok, v_logits = eng.capture_verify_graph(cache, T, fp8=fp8_weights, fp4=fp4_weights)
-    am = attention_mask.to(dev).to(torch.bool) if attention_mask is not None else None
-    padded = am is not None and not bool(am.all()) and cache.rpos is None  # right-padded prompt: as _sample_cached
-    lens = am.sum(dim=1) if padded else None
-    # the sequence as the criteria and the drafter see it (with bans: k cells more, a draft is written behind it before it is verified)
-    seq = torch.full((1, max_len + (k if bans is not None else 0)), pad, dtype=torch.int64, device=dev)
-    seq[:, :P] = input_ids.to(dev)
-    tables = _ban_tables(bans[0], bans[1], P, dev) if bans is not None else None
+    c, st = call, _Stepper(call)
+    k, max_len, stats, sel, stop = c.lookup, c.max_len, c.stats, c.sel, c.stop
+    P, V, T = input_ids.shape[1], st.V, k + 1
+    logits = st.prefill(input_ids, max_len - P + k)  # k rows of room for a rejected draft's tail
+    st.capture(T)
+    # (with bans: k cells more, a draft is written behind the sequence before it is verified)
+    seq = st.ids_buffer(max_len + (k if c.bans is not None else 0))
     n = P  # valid length of seq
-    sel_kw = {key: sel[key] for key in ("do_sample", "temperature", "top_k", "top_p", "seed", "min_p", "epsilon_cutoff") if key in sel}
 
     def emit(cand, draft):
         """Append the accepted part of `cand` (selected tokens, on the host) to seq; -> (tokens emitted, accepted, stopped)."""
@@ -715,61 +784,36 @@ def _sample_lookup(model, input_ids, images, attention_mask, max_len, eos_ids, p
 
         out, a, stopped = _accept(draft, cand, max_len - n, stops)
         n = base + len(out)
-        if streamer is not None:
-            streamer.put(torch.tensor([out], dtype=torch.int64))
+        if c.streamer is not None:
+            c.streamer.put(torch.tensor([out], dtype=torch.int64))
         return out, a, stopped
 
-    if tables is not None:
-        O.ban_tokens(logits, V, seq, len0=P, **tables)
+    st.ban(logits, P)
     first = _select(logits, V, sel, 0)
     out, _, stopped = emit(first.tolist(), [])
     while not stopped and n < max_len:
         emitted = n - P
-        draft_dev, cnt = O.ngram_draft(seq, n, max_ngram, k, max_len)
-        c = int(cnt[0])
+        draft_dev, cnt = O.ngram_draft(seq, n, c.max_ngram, k, max_len)
+        d = int(cnt[0])
         last = seq[:, n - 1]
-        if c == 0:
-            if graph is not None:
-                g_tok.copy_(last)
-                graph.replay()
-                logits = g_logits
-            else:
-                logits = eng.decode_step(last if guide is None else last.repeat(2), cache, fp8=fp8_weights, fp4=fp4_weights)
-            if guide is not None:
-                logits = O.guidance_mix(logits[:1], logits[1:], guide["scale"], V, out=logits[:1])
+        if d == 0:
+            logits = st.step(last)
             stats["plain_steps"] += 1
-            if tables is not None:
-                O.ban_tokens(logits, V, seq, len0=n, **tables)
+            st.ban(logits, n)
             out, _, stopped = emit(_select(logits, V, sel, emitted).tolist(), [])
             continue
-        toks = v_tok if vgraph is not None else torch.empty(R, T, dtype=torch.int64, device=dev)
-        toks[:, 0] = last
-        toks[:, 1:] = pad  # a short draft is padded to the step's k + 1 rows; their logits are not looked at
-        toks[:, 1:1 + c] = draft_dev[:, :c]
-        if vgraph is not None:
-            vgraph.replay()
-            logits = v_logits
-        else:
-            logits = eng.verify_step(toks, cache, fp8=fp8_weights, fp4=fp4_weights)
-        if guide is not None:  # rows t and T + t of the step's buffer -> conditional row t, in place
-            O.guidance_mix(logits[0], logits[1], guide["scale"], V, out=logits[0])
-            logits = logits[:1]
-        if tables is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
-            seq[0, n:n + c] = draft_dev[0, :c]
-            O.ban_tokens(logits[0], V, seq, len0=n, len_step=1, ld_ids=0, **tables)
-        picked = O.select_tokens_multi(logits, V, step0=emitted, **sel_kw)[:, 0]  # [T]
+        logits = st.verify(last, draft_dev, d)
+        if c.bans is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
+            seq[0, n:n + d] = draft_dev[0, :d]
+            st.ban(logits[0], n, len_step=1, ld_ids=0)
+        picked = O.select_tokens_multi(logits, V, step0=emitted, **sel)[:, 0]  # [T]
         both = torch.cat([picked, draft_dev[0]]).tolist()  # one transfer
-        out, a, stopped = emit(both[:c + 1], both[T:T + c])
-        cache.advance(a + 1)  # the last token and the a accepted drafts are keys now; the stale rows behind them get overwritten
+        out, a, stopped = emit(both[:d + 1], both[T:T + d])
+        st.cache.advance(a + 1)  # the last token and the a accepted drafts are keys now; the stale rows behind them get overwritten
         stats["verify_steps"] += 1
-        stats["drafted"] += c
+        stats["drafted"] += d
         stats["accepted"] += min(a, len(out))  # (a draft token that agreed beyond a stop or max_length was not emitted)
-    cur = seq[:, :n]
-    if padded:
-        cur = _compact(seq[:, :P], lens, seq[:, P:n], pad)
-    if session is not None:
-        session._fed(cur)  # (a rejected draft's tail is behind cache.lens: not counted)
-    return cur.to(input_ids.device)
+    return st.finish(n)
 
 
 def _compact(ids, lens, new, pad):
@@ -789,32 +833,31 @@ def _gather_beams(t, idx):
     return torch.gather(t, 1, idx.expand(-1, -1, *t.shape[2:]))
 
 
-def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_penalty, early_stopping, stop, fp8_weights, fp8_kv=False, fp4_weights=False,
-                 share_prompt_kv=False, session=None, bans=None):
+def _beam_search(call, input_ids):
     """Beam search as transformers' `_beam_search` runs it (do_sample=False, num_return_sequences=1).  The prompt is
     prefilled ONCE per prompt and its KV cache expanded to num_beams rows (the reference reaches the same state through
     `inputs_embeds.repeat_interleave(5)`, base_mmgpt.py:162-163, after computing one row); every step the cache rows are
     re-ordered by the surviving beams' parents (HF `_reorder_cache`) with one gather kernel per layer.
     share_prompt_kv: the prefilled cache stays the one copy of the prompt's K/V (engine.share_cache) and the re-ordering is a table step."""
-    eng = model.engine
+    c, st = call, _Stepper(call)
+    eng, V = st.eng, st.V
+    nb, max_len, eos_ids, pad, stop, length_penalty, early_stopping = c.num_beams, c.max_len, c.eos_ids, c.pad, c.stop, c.length_penalty, c.early_stopping
     B, P = input_ids.shape
-    V = model.config.vocab_size
     max_new = max_len - P
-    # (the shared prompt cache appends to the beams' own rows: its prefill gets no spare rows, so the prefix holds the prompt and nothing else)
-    if session is not None:  # the session's cache is the prompt cache: read by both paths, written by neither - it keeps the prompt
-        logits0, cache0 = session._prefill(input_ids, images, 0)
-    else:
-        logits0, cache0 = eng.prefill(input_ids, None, images, 0 if share_prompt_kv else max_new, kv_fp8=fp8_kv)
+    # No spare rows behind the prompt where the beams append to rows of their own: the shared prompt cache's prefix holds the prompt and
+    # nothing else, and a session's cache is the prompt cache - read by both paths, written by neither, it keeps the prompt
+    logits0 = st.prefill(input_ids, 0 if c.share_prompt_kv or c.session is not None else max_new)
+    cache0 = st.cache
     dev = logits0.device
     ids = input_ids.to(dev)
     expand = torch.arange(B, device=dev).repeat_interleave(nb)
-    if share_prompt_kv:
-        cache = eng.share_cache(cache0, nb, max_new)  # cache0 lives on inside it: it is the prefix
-    elif session is not None:
-        cache = eng.expand_prefix(cache0, nb, P, P + max_new)  # (P + max_new rows per beam, not the session's capacity)
+    if c.share_prompt_kv:
+        st.cache = eng.share_cache(cache0, nb, max_new)  # cache0 lives on inside it: it is the prefix
+    elif c.session is not None:
+        st.cache = eng.expand_prefix(cache0, nb, P, P + max_new)  # (P + max_new rows per beam, not the session's capacity)
     else:
-        cache = eng.expand_cache(cache0, expand)
-        del cache0
+        st.cache = eng.expand_cache(cache0, expand)
+    del cache0
     logits = torch.empty(B * nb, logits0.shape[1], dtype=torch.float32, device=dev)
     O.gather_rows2d(logits0, expand, logits)
 
@@ -833,11 +876,10 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
     unsat = torch.ones(B, 1, dtype=torch.bool, device=dev)          # "early-stop heuristic unsatisfied"
     batch_off = (torch.arange(B, device=dev) * nb)[:, None]
     cur = P
-    tables = _ban_tables(bans[0], bans[1], P, dev) if bans is not None else None
     while True:
         acc = O.log_softmax_rows(logits, V, row_bias=running_scores.reshape(-1).contiguous())  # log_probs + running_beam_scores
-        if tables is not None:  # HF: the processors run on log_softmax(logits) of flat_running_sequences; a ban only writes -inf, so after the add
-            O.ban_tokens(acc, V, running.view(B * nb, max_len), len0=cur, **tables)
+        # HF: the processors run on log_softmax(logits) of flat_running_sequences; a ban only writes -inf, so after the add
+        st.ban(acc, cur, ids=running.view(B * nb, max_len))
         top_lp, top_i = torch.topk(acc.view(B, nb * V), k=keep)
         parent = top_i // V
         tok = top_i % V
@@ -871,10 +913,7 @@ def _beam_search(model, input_ids, images, nb, max_len, eos_ids, pad, length_pen
         go_on = bool(unsat.any()) and not (bool(finished.all()) and early_stopping is True) and not bool(hits.all())
         if not go_on:
             break
-        if share_prompt_kv:
-            cache.reorder(beam_idx)
-        else:
-            eng.reorder_cache(cache, beam_idx, cur - 1)
-        logits = eng.decode_step(running[:, :, cur - 1].reshape(-1).contiguous(), cache, fp8=fp8_weights, fp4=fp4_weights)
+        st.cache.reorder(beam_idx, cur - 1)  # (cur - 1 valid rows: what the copying cache moves; the shared one rewrites its table)
+        logits = st.step(running[:, :, cur - 1].reshape(-1).contiguous())
     out_len = P + int(seq_len[:, 0].max())
     return sequences[:, 0, :out_len].to(input_ids.device)

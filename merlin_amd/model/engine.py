@@ -31,6 +31,7 @@ import torch
 from .. import ops as O
 from .arena import Arena
 from .config import head_dim_of, rope_theta_of
+from .kv_cache import BeamKVCache, KVCache
 
 VT = "model.vision_tower.vision_tower.vision_model."
 
@@ -637,31 +638,18 @@ class HipEngine:
     def _attn_fwd(self, qkv, B, S, H, D, lens, unpad, kv_out=None):
         if unpad is None:
             q, k, v = self._qkv(qkv)
-            if kv_out is not None:  # prefill: rotated keys and values go to the decode cache [B, Smax, d]
-                self._fill_cache(kv_out, k, v, B, S, H, D)
+            if kv_out is not None:  # prefill: rotated keys and values go to rows [:, :S] of the decode cache, kv_out = (cache, layer)
+                kv_out[0].append_rows(kv_out[1], k, v, S, 0, H, D)
             o, lse = O.attn_fwd2(q, k, v, B, S, H, D, causal=True, seqlens=lens)
             return o, lse, None
         fwd, inv, cnt = unpad
         qkv_c = O.gather_rows2d(qkv, fwd, torch.empty_like(qkv))
         q, k, v = self._qkv(qkv_c)
         if kv_out is not None:  # the cache keeps only the VALID keys (rows 0..count-1); their rotation already carries the position
-            self._fill_cache(kv_out, k, v, B, S, H, D)
+            kv_out[0].append_rows(kv_out[1], k, v, S, 0, H, D)
         o_c, lse = O.attn_fwd2(q, k, v, B, S, H, D, causal=True, seqlens=cnt)
         o = O.gather_rows2d(o_c, inv, torch.empty_like(o_c))
         return o, lse, (qkv_c, o_c)
-
-    @staticmethod
-    def _fill_cache(kv_out, k, v, B, S, H, D):
-        """Rows [:, :S] of one layer's decode cache from the prompt's rotated keys and values (views of the q|k|v buffer): 16-bit copies
-        (k, v), or e4m3 bytes and their scales (k8, v8, ks, vs) for the fp8 cache - only what is STORED is quantised, the prompt's own
-        attention runs on the 16-bit k, v."""
-        if kv_out[0].dtype == torch.uint8:  # KVCache(fp8=True).layer(li)
-            k8, v8, ks, vs = kv_out
-            O.kv8_fill(k, k8, ks, B, S, H, D)
-            O.kv8_fill(v, v8, vs, B, S, H, D)
-        else:
-            kv_out[0][:, :S].copy_(k.view(B, S, H * D))
-            kv_out[1][:, :S].copy_(v.view(B, S, H * D))
 
     def _attn_bwd(self, qkv, o, do, lse, B, S, H, D, lens, unpad, packed):
         """-> dqkv [T, 3 H D] w.r.t. the UN-rotated q, k (inverse RoPE applied)."""
@@ -1020,7 +1008,7 @@ class HipEngine:
         else:
             layer = lambda li, x, kv: self._llama_layer_fwd(self.llama[li], x, B, S, lens, keep, kv_out=kv, unpad=unpad, need_x16=want_grad)  # noqa: E731
         for li in range(len(self.llama)):
-            x16, x, sv = layer(li, x, kv_cache.layer(li) if kv_cache is not None else None)
+            x16, x, sv = layer(li, x, (kv_cache, li) if kv_cache is not None else None)
             if want_grad:
                 xs.append(x16)
             saves.append(sv)
@@ -1221,122 +1209,8 @@ class HipEngine:
     # ------------------------------------------------------------------------------------------
     # KV-cache decode (llama_mmgpt.py:114-134, HF LlamaAttention with past_key_values)
     # ------------------------------------------------------------------------------------------
-    class KVCache:
-        """Per-layer rotated keys and values, [B, Smax, H*D] each, plus the valid length of every sequence.
-        fp8=True (H heads): k, v hold OCP e4m3 bytes (uint8) and ks, vs [B, H, Smax] one power-of-two fp32 scale per (sequence, head,
-        token) - include/merlin_hip.h "fp8 KV cache"; (1 + 4/D) / 2 of the 16-bit cache's bytes."""
-
-        def __init__(self, n_layers, B, Smax, d, dtype, device, fp8=False, H=None):
-            self.fp8, self.H = bool(fp8), H
-            if fp8:
-                dtype = torch.uint8
-                self.ks = [torch.zeros(B, H, Smax, dtype=torch.float32, device=device) for _ in range(n_layers)]
-                self.vs = [torch.zeros(B, H, Smax, dtype=torch.float32, device=device) for _ in range(n_layers)]
-                self.ks_alt = self.vs_alt = None
-            self.k = [torch.zeros(B, Smax, d, dtype=dtype, device=device) for _ in range(n_layers)]
-            self.v = [torch.zeros(B, Smax, d, dtype=dtype, device=device) for _ in range(n_layers)]
-            self.lens = torch.zeros(B, dtype=torch.int32, device=device)
-            # rotary position of the next token when it differs from its cache row (prompts with padding in front of / inside
-            # them keep only their valid keys, positions stay absolute as HF numbers them); None: == lens
-            self.rpos = None
-            self.B, self.Smax = B, Smax
-            self.k_alt = self.v_alt = None
-
-        def layer(self, li):
-            """The tensors of layer li: (k, v), or (k8, v8, ks, vs) of the fp8 cache."""
-            return (self.k[li], self.v[li], self.ks[li], self.vs[li]) if self.fp8 else (self.k[li], self.v[li])
-
-        def sets(self):
-            """The per-layer tensor lists that make up the cache: k, v, and the scales ks, vs of the fp8 cache."""
-            return [self.k, self.v, self.ks, self.vs] if self.fp8 else [self.k, self.v]
-
-        @property
-        def nbytes(self):
-            return sum(t.numel() * t.element_size() for lst in self.sets() for t in lst)
-
-        def advance(self, n):
-            """lens += n (an int, or int32 [B] on the device), and rpos with it: the tokens of a verify_step that are kept.  Rows beyond the
-            new length are stale; the next step overwrites them - that is the whole roll-back of a rejected draft."""
-            self.lens.add_(n)
-            if self.rpos is not None:
-                self.rpos.add_(n)
-
-        def truncate(self, n):
-            """lens = n for every sequence: roll the cache back to its first n rows (a session that keeps a prefix of what it holds).  The
-            rows behind them are stale and the next prefill / extend / decode step overwrites them, as after a rejected draft."""
-            if not 0 <= int(n) <= self.Smax:
-                raise ValueError(f"truncate({n}): the cache has rows [0, {self.Smax})")
-            if self.rpos is not None:
-                raise ValueError("truncate takes a cache whose rotary positions are its rows (no left padding or holes in the prompt)")
-            self.lens.fill_(int(n))
-
-    class BeamKVCache:
-        """Beam search on a shared prompt cache (generate(num_beams=n, share_prompt_kv=True); include/merlin_hip.h "beam search on a shared
-        prompt cache").  prefix: the prefilled KVCache of the Bp prompts itself - its tensors are used where they lie, never copied;
-        pre_lens = prefix.lens.  Suffix: per-layer k, v [Bp*nb, G, H*D] (fp8: + ks, vs [Bp*nb, H, G]) in the prefix's dtype and layout, one
-        row per generated token and beam.  gen int32 [Bp*nb]: suffix rows written (the append kernels' pos); apos = rotary position of
-        the next token (their rope_pos); anc int32 [Bp*nb, G]: anc[m, g] is the suffix row that holds key / value g of beam m's history.
-        Everything a step reads lives on the device."""
-
-        def __init__(self, prefix, nb, G):
-            Bp, dev = prefix.B, prefix.lens.device
-            self.prefix, self.nb, self.Bp, self.G = prefix, int(nb), Bp, int(G)
-            self.fp8, self.H = prefix.fp8, prefix.H
-            self.B = n = Bp * self.nb
-            self.pre_lens = prefix.lens
-            d = prefix.k[0].shape[-1]
-            self.k = [torch.zeros(n, G, d, dtype=t.dtype, device=dev) for t in prefix.k]
-            self.v = [torch.zeros(n, G, d, dtype=t.dtype, device=dev) for t in prefix.v]
-            if self.fp8:
-                self.ks = [torch.zeros(n, self.H, G, dtype=torch.float32, device=dev) for _ in prefix.ks]
-                self.vs = [torch.zeros(n, self.H, G, dtype=torch.float32, device=dev) for _ in prefix.vs]
-            self.gen = torch.zeros(n, dtype=torch.int32, device=dev)
-            base = prefix.rpos if prefix.rpos is not None else prefix.lens
-            self.apos = base.repeat_interleave(self.nb).contiguous()
-            # every column of a row starts as the row itself: a beam that is never re-ordered reads its own rows
-            self.anc = torch.arange(n, dtype=torch.int32, device=dev)[:, None].repeat(1, G).contiguous()
-            self._anc_alt = self.anc.clone()
-
-        def layer(self, li):
-            """The suffix tensors of layer li: (k, v), or (k8, v8, ks, vs) of the fp8 cache."""
-            return (self.k[li], self.v[li], self.ks[li], self.vs[li]) if self.fp8 else (self.k[li], self.v[li])
-
-        def sets(self):
-            """The per-layer suffix tensor lists: k, v, and the scales ks, vs of the fp8 cache."""
-            return [self.k, self.v, self.ks, self.vs] if self.fp8 else [self.k, self.v]
-
-        @property
-        def nbytes(self):
-            """Resident K/V bytes: the prefix once plus the suffix rows (the two ancestry tables, 8 G bytes per beam, are not K/V)."""
-            return self.prefix.nbytes + sum(t.numel() * t.element_size() for lst in self.sets() for t in lst)
-
-        def reorder(self, beam_idx):
-            """HF `_reorder_cache`: beam m continues beam beam_idx[m] (int64 [Bp*nb] on the device, in-group).  One table kernel
-            (mh_beam_ancestry); no key or value moves."""
-            O.beam_ancestry(self.anc, self._anc_alt, beam_idx, self.gen)
-            self.anc, self._anc_alt = self._anc_alt, self.anc
-
-        def materialize(self):
-            """An ordinary KVCache of Bp*nb rows and Smax = Pmax + G: row m holds its prompt's prefix followed by its ancestry's suffix
-            rows.  For tests and debugging only (host loops, copies everything); not on the decode path."""
-            pre, n, G = self.prefix, self.B, self.G
-            d = pre.k[0].shape[-1]
-            out = HipEngine.KVCache(len(pre.k), n, pre.Smax + G, d, pre.k[0].dtype, pre.lens.device, fp8=self.fp8, H=self.H)
-            gen, pl, anc = self.gen.tolist(), pre.lens.tolist(), self.anc.long()
-            for m in range(n):
-                p, g, at = m // self.nb, gen[m], pl[m // self.nb]
-                col = torch.arange(g, device=anc.device)
-                for src_pre, src_suf, dst in zip(pre.sets()[:2], self.sets()[:2], out.sets()[:2]):
-                    for li in range(len(dst)):
-                        dst[li][m, :at] = src_pre[li][p, :at]
-                        dst[li][m, at:at + g] = src_suf[li][anc[m, :g], col]
-                for src_pre, src_suf, dst in zip(pre.sets()[2:], self.sets()[2:], out.sets()[2:]):
-                    for li in range(len(dst)):
-                        dst[li][m, :, :at] = src_pre[li][p, :, :at]
-                        dst[li][m, :, at:at + g] = src_suf[li][anc[m, :g], :, col].t()
-            out.lens = (pre.lens.repeat_interleave(self.nb) + self.gen).contiguous()
-            out.rpos = (self.apos.clone() if pre.rpos is not None else None)
-            return out
+    # the cache types own their storage format and their part of a step (kv_cache.py); kept here under the names they always had
+    KVCache, BeamKVCache = KVCache, BeamKVCache
 
     def share_cache(self, cache, num_beams, max_new):
         """BeamKVCache on the prefilled `cache` of Bp prompts: num_beams beams per prompt, room for max_new generated tokens each.  The
@@ -1354,12 +1228,10 @@ class HipEngine:
         cache: an existing KVCache to fill from row 0 instead of a new one (a session's: generation.Session); it keeps its own format and
         must have B rows and room for the prompt and max_new_tokens."""
         self.ensure_arena()
-        cfg = self.model.config
         B, S = (input_ids.shape if input_ids is not None else inputs_embeds.shape[:2])
         A = self.arena
         if cache is None:
-            cache = HipEngine.KVCache(len(self.llama), B, S + max_new_tokens, cfg.hidden_size, A.flat.dtype, A.flat.device, fp8=kv_fp8,
-                                      H=cfg.num_attention_heads)
+            cache = self.new_cache(B, S + max_new_tokens, fp8=kv_fp8)
         elif cache.B != B or S + max_new_tokens > cache.Smax:
             raise ValueError(f"prefill into a cache of {cache.B} x {cache.Smax} rows: the prompt needs {B} x {S + max_new_tokens}")
         else:
@@ -1398,7 +1270,6 @@ class HipEngine:
         A = self.ensure_arena()
         dev = A.flat.device
         d, H, D, V = cfg.hidden_size, cfg.num_attention_heads, head_dim_of(cfg), cfg.vocab_size
-        eps = cfg.rms_norm_eps
         rope = self._rope_table(cache.Smax, dev)[P:]  # row t of the slice is position P + t: the GEMM epilogue's table with S = n
         ids = input_ids.to(dev).contiguous()
         tower = getattr(m.get_model(), "vision_tower", None)
@@ -1416,27 +1287,29 @@ class HipEngine:
         x = splice(ids.view(-1), src.view(-1) if src is not None else None, emb, feats)
         del feats
         lens1 = cache.lens + 1  # what the first new query sees: the cached rows and its own key
+        hn = self._extend_layers(cache, x, rope, n, P, O.attn_extend, lens1, n, H, D)
+        logits = O.gemv(hn[n - 1:n], self._lm_head_w(), out_f32=True, n=V)
+        cache.advance(n)
+        return logits
+
+    def _extend_layers(self, cache, x, rope, n, P, attn, *attn_args):
+        """The layer loop of extend and extend_branches over the n embedded rows x of one sequence: the prefill's GEMMs with `rope` as the
+        RoPE epilogue's table (row t: the position of row t), the rotated keys and the values appended to cache rows [P, P + n), then
+        attn (ops.attn_extend or ops.attn_extend_branches, with attn_args behind q and the layer's tensors) over the cache AFTER the
+        append.  -> the normalised final hidden rows [n, d]."""
+        cfg = self.model.config
+        H, D, eps = cfg.num_attention_heads, head_dim_of(cfg), cfg.rms_norm_eps
         for li, W in enumerate(self.llama):
             h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
             qkv = O.gemm_nt_rope(h1, W.wqkv, rope, n, H, D)
             q, k, v = self._qkv(qkv)
-            if cache.fp8:
-                k8, v8, ks, vs = cache.layer(li)
-                O.kv8_fill(k, k8, ks, 1, n, H, D, row0=P)
-                O.kv8_fill(v, v8, vs, 1, n, H, D, row0=P)
-                o = O.attn_extend_kv8(q, k8, v8, ks, vs, lens1, n, H, D)
-            else:
-                cache.k[li][:, P:P + n].copy_(k.view(1, n, d))
-                cache.v[li][:, P:P + n].copy_(v.view(1, n, d))
-                o = O.attn_extend(q, cache.k[li], cache.v[li], lens1, n, H, D)
+            cache.append_rows(li, k, v, n, P, H, D)
+            o = cache.attend(attn, li, q, *attn_args)
             x = self._stream_add(x, o, W.wo)
             h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
             _, act = O.gemm_swiglu_fwd(h2, W.wgu)
             x = self._stream_add(x, act, W.wd)
-        hn, _ = self._stream_norm(x, A.view("model.norm.weight"), eps, want_x16=False)
-        logits = O.gemv(hn[n - 1:n], self._lm_head_w(), out_f32=True, n=V)
-        cache.lens.add_(n)
-        return logits
+        return self._stream_norm(x, self.arena.view("model.norm.weight"), eps, want_x16=False)[0]
 
     HEAD_CHUNK = 256  # rows of fp32 logits held at a time by the scoring pass (256 x V floats: 33 MB at V = 32003)
 
@@ -1479,31 +1352,13 @@ class HipEngine:
             raise ValueError(f"extend_branches: {P} cached + {R} rows exceed the cache's {cache.Smax} rows (grow_cache makes a larger one)")
         A = self.ensure_arena()
         dev = A.flat.device
-        eps = cfg.rms_norm_eps
         seg = plan.seg_start.to(device=dev, dtype=torch.int32).contiguous()
         rel = plan.rel_pos.to(device=dev, dtype=torch.int64)
         rope = self._rope_table(cache.Smax, dev).index_select(0, rel + P)  # row r: position P + rel_pos[r] (< P + R <= Smax)
         ids = torch.tensor(fed, dtype=torch.int64, device=dev)
         emb = A.view("model.embed_tokens.weight", shape=(V, d))
         x = (O.embed_splice_fwd_f32 if self.fp32_residual else O.embed_splice_fwd)(ids, None, emb, None)
-        for li, W in enumerate(self.llama):
-            h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
-            qkv = O.gemm_nt_rope(h1, W.wqkv, rope, R, H, D)
-            q, k, v = self._qkv(qkv)
-            if cache.fp8:
-                k8, v8, ks, vs = cache.layer(li)
-                O.kv8_fill(k, k8, ks, 1, R, H, D, row0=P)
-                O.kv8_fill(v, v8, vs, 1, R, H, D, row0=P)
-                o = O.attn_extend_branches_kv8(q, k8, v8, ks, vs, seg, P, H, D)
-            else:
-                cache.k[li][:, P:P + R].copy_(k.view(1, R, d))
-                cache.v[li][:, P:P + R].copy_(v.view(1, R, d))
-                o = O.attn_extend_branches(q, cache.k[li], cache.v[li], seg, P, H, D)
-            x = self._stream_add(x, o, W.wo)
-            h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
-            _, act = O.gemm_swiglu_fwd(h2, W.wgu)
-            x = self._stream_add(x, act, W.wd)
-        hn, _ = self._stream_norm(x, A.view("model.norm.weight"), eps, want_x16=False)
+        hn = self._extend_layers(cache, x, rope, R, P, O.attn_extend_branches, seg, P, H, D)
         if not return_logits:
             return hn
         step = self.HEAD_CHUNK
@@ -1512,20 +1367,8 @@ class HipEngine:
     def grow_cache(self, cache, Smax):
         """A new KVCache of Smax >= cache.Smax rows per sequence holding the rows of `cache` (the scales [B, H, Smax] of the fp8 form
         included), same format, lengths and positions.  Off the hot path: plain copies, once per growth of a session."""
-        if Smax < cache.Smax:
-            raise ValueError(f"grow_cache({Smax}): the cache already has {cache.Smax} rows")
-        A = self.ensure_arena()
-        old = cache.Smax
-        out = HipEngine.KVCache(len(cache.k), cache.B, int(Smax), cache.k[0].shape[-1], A.flat.dtype, A.flat.device, fp8=cache.fp8, H=cache.H)
-        for li in range(len(cache.k)):
-            out.k[li][:, :old].copy_(cache.k[li])
-            out.v[li][:, :old].copy_(cache.v[li])
-            if cache.fp8:
-                out.ks[li][:, :, :old].copy_(cache.ks[li])
-                out.vs[li][:, :, :old].copy_(cache.vs[li])
-        out.lens.copy_(cache.lens)
-        out.rpos = cache.rpos.clone() if cache.rpos is not None else None
-        self._rope_table(int(Smax), A.flat.device)
+        out = cache.grown(Smax)
+        self._rope_table(int(Smax), out.lens.device)
         return out
 
     def new_cache(self, B, Smax, fp8=False):
@@ -1540,16 +1383,8 @@ class HipEngine:
         """New cache of nb rows and Smax rows per sequence whose every row holds the first P rows of the one-sequence `cache` (beam search
         from a session's cache, which may be far larger than the prompt: expand_cache would copy all of it per beam).  Once per call,
         plain copies; `cache` is not written."""
-        if cache.B != 1 or P > min(Smax, cache.Smax):
-            raise ValueError(f"expand_prefix takes a one-sequence cache holding {P} <= {min(Smax, cache.Smax)} rows")
-        out = self.new_cache(nb, Smax, fp8=cache.fp8)
-        for li in range(len(cache.k)):
-            out.k[li][:, :P].copy_(cache.k[li][:, :P].expand(nb, -1, -1))
-            out.v[li][:, :P].copy_(cache.v[li][:, :P].expand(nb, -1, -1))
-            if cache.fp8:
-                out.ks[li][:, :, :P].copy_(cache.ks[li][:, :, :P].expand(nb, -1, -1))
-                out.vs[li][:, :, :P].copy_(cache.vs[li][:, :, :P].expand(nb, -1, -1))
-        out.lens.copy_(cache.lens.expand(nb))
+        out = cache.expanded_prefix(nb, P, Smax)
+        self._rope_table(int(Smax), out.lens.device)
         return out
 
     def pair_cache(self, cond_cache, uncond_cache, max_new):
@@ -1557,21 +1392,8 @@ class HipEngine:
         cache, row 1 the unconditional's, lens per row, Smax = max(len) + max_new, the format of its inputs (16-bit, or fp8 with ks / vs).
         Both inputs are one-sequence, un-padded caches of one format.  Once per call, plain copies; the inputs are not written.
         decode_step and verify_step run on it like on any right-padded batch."""
-        pair = (cond_cache, uncond_cache)
-        if any(not isinstance(c, HipEngine.KVCache) or c.B != 1 or c.rpos is not None for c in pair):
-            raise ValueError("pair_cache takes two plain KVCaches of one un-padded sequence each (B = 1, no left padding or holes)")
-        if cond_cache.fp8 != uncond_cache.fp8 or max_new < 0:
-            raise ValueError(f"pair_cache takes two caches of one format and max_new >= 0, got fp8 = {cond_cache.fp8} / {uncond_cache.fp8}, max_new = {max_new}")
-        n = [int(c.lens[0]) for c in pair]
-        out = self.new_cache(2, max(n) + int(max_new), fp8=cond_cache.fp8)
-        for b, (c, P) in enumerate(zip(pair, n)):
-            for li in range(len(c.k)):
-                out.k[li][b, :P].copy_(c.k[li][0, :P])
-                out.v[li][b, :P].copy_(c.v[li][0, :P])
-                if c.fp8:
-                    out.ks[li][b, :, :P].copy_(c.ks[li][0, :, :P])
-                    out.vs[li][b, :, :P].copy_(c.vs[li][0, :, :P])
-        out.lens.copy_(torch.cat([cond_cache.lens, uncond_cache.lens]))
+        out = KVCache.paired(cond_cache, uncond_cache, max_new)
+        self._rope_table(out.Smax, out.lens.device)
         return out
 
     def expand_cache(self, cache, rows):
@@ -1594,25 +1416,7 @@ class HipEngine:
     def reorder_cache(self, cache, beam_idx, n_valid):
         """cache row i <- cache row beam_idx[i] for the first n_valid positions (HF `_reorder_cache` under beam search):
         one gather kernel per layer and tensor into a second buffer set, then the sets swap."""
-        d = cache.k[0].shape[-1]
-        if getattr(cache, "k_alt", None) is None:
-            cache.k_alt = [torch.empty_like(t) for t in cache.k]
-            cache.v_alt = [torch.empty_like(t) for t in cache.v]
-        n = cache.B
-        for li in range(len(cache.k)):
-            O.gather_rows2d(cache.k[li].view(n, -1), beam_idx, cache.k_alt[li].view(n, -1), cols=n_valid * d)
-            O.gather_rows2d(cache.v[li].view(n, -1), beam_idx, cache.v_alt[li].view(n, -1), cols=n_valid * d)
-        cache.k, cache.k_alt = cache.k_alt, cache.k
-        cache.v, cache.v_alt = cache.v_alt, cache.v
-        if cache.fp8:  # the scales too: head-major rows [H, Smax] have no valid prefix and move whole
-            if cache.ks_alt is None:
-                cache.ks_alt = [torch.empty_like(t) for t in cache.ks]
-                cache.vs_alt = [torch.empty_like(t) for t in cache.vs]
-            for li in range(len(cache.ks)):
-                O.gather_rows2d(cache.ks[li].view(n, -1), beam_idx, cache.ks_alt[li].view(n, -1))
-                O.gather_rows2d(cache.vs[li].view(n, -1), beam_idx, cache.vs_alt[li].view(n, -1))
-            cache.ks, cache.ks_alt = cache.ks_alt, cache.ks
-            cache.vs, cache.vs_alt = cache.vs_alt, cache.vs
+        cache.reorder(beam_idx, n_valid)
 
     def quantize_decode_weights(self):
         """fp8 (OCP e4m3, one scale per 128 k) copies of the decoder's Linear weights for the decode step (BASELINE cfg 5's
@@ -1645,13 +1449,7 @@ class HipEngine:
         (one of the two).  An fp8 cache (prefill(kv_fp8=True)) appends and attends in its own kernels (mh_decode_rope_append_kv8,
         mh_attn_decode_kv8), with any weight format."""
         logits = self._decode_rows(tokens, cache, fp8, fp4, 0)
-        if isinstance(cache, HipEngine.BeamKVCache):  # (a shared prompt cache: tokens [Bp*nb]; the prefix does not grow)
-            cache.gen.add_(1)
-            cache.apos.add_(1)
-            return logits
-        cache.lens.add_(1)  # in place (after every kernel that read it as `pos`): the captured graph sees the same buffer
-        if cache.rpos is not None:
-            cache.rpos.add_(1)
+        cache.advance(1)  # in place, after every kernel that read the positions: the captured graph sees the same buffers
         return logits
 
     def verify_step(self, tokens, cache, fp8=False, fp4=False):
@@ -1686,37 +1484,18 @@ class HipEngine:
             layers = [(W.wqkv, W.wo, W.wgu, W.wd) for W in self.llama]
         emb = A.view("model.embed_tokens.weight", shape=(V, d))
         x = O.gather_rows(emb, tokens.to(A.flat.device).view(-1))
-        beams = isinstance(cache, HipEngine.BeamKVCache)
-        if beams and T:
+        if T and isinstance(cache, BeamKVCache):
             raise ValueError("verify_step takes a KVCache: a BeamKVCache decodes one token per beam (decode_step)")
-        # a shared prompt cache appends to the beams' suffix rows (row gen, rotary position apos) and attends prefix + suffix
-        pos, rpos = (cache.gen, cache.apos) if beams else (cache.lens, cache.rpos)
-        lens1 = pos + 1
-        pre = cache.prefix if beams else None
+        lens1 = cache.pos + 1  # what a step's first query sees: the cached rows and its own key
         for li, (wqkv, wo, wgu, wd) in enumerate(layers):
             W = self.llama[li]
-            if T:  # several positions per sequence: the projection, then RoPE + append and attention over the T rows of a sequence
+            if not cache.fp8 and T == 0:
+                # a 16-bit cache's single-token step: input_layernorm + q|k|v projection + RoPE + K/V append in one launch
+                qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, cache.pos, *cache.layer(li), H, D, rope_pos=cache.rope_pos)
+            else:  # the projection, then RoPE + append as a launch of the cache's own
                 qkv = gemv_norm(x, W.ln1, eps, wqkv)
-                if cache.fp8:
-                    O.decode_rope_append_multi_kv8(qkv, self.rope, pos, *cache.layer(li), T, H, D, rope_pos=cache.rpos)
-                    o = O.attn_decode_multi_kv8(qkv[:, :d], *cache.layer(li), lens1, T, H, D)
-                else:
-                    O.decode_rope_append_multi(qkv, self.rope, pos, cache.k[li], cache.v[li], T, H, D, rope_pos=cache.rpos)
-                    o = O.attn_decode_multi(qkv[:, :d], cache.k[li], cache.v[li], lens1, T, H, D)
-            elif cache.fp8:  # fp8 KV cache: the projection, then RoPE + quantised append as a launch of its own
-                qkv = gemv_norm(x, W.ln1, eps, wqkv)
-                O.decode_rope_append_kv8(qkv, self.rope, pos, *cache.layer(li), H, D, rope_pos=rpos)
-                if beams:
-                    o = O.attn_decode_beams_kv8(qkv[:, :d], *pre.layer(li), pre.lens, *cache.layer(li), cache.anc, lens1, cache.nb, H, D)
-                else:
-                    o = O.attn_decode_kv8(qkv[:, :d], *cache.layer(li), lens1, H, D)
-            else:
-                # input_layernorm + q|k|v projection + RoPE + K/V append: one launch
-                qkv = O.gemv_qkv_rope(x, W.ln1, eps, wqkv, self.rope, pos, cache.k[li], cache.v[li], H, D, rope_pos=rpos)
-                if beams:
-                    o = O.attn_decode_beams(qkv[:, :d], pre.k[li], pre.v[li], pre.lens, cache.k[li], cache.v[li], cache.anc, lens1, cache.nb, H, D)
-                else:
-                    o = O.attn_decode(qkv[:, :d], cache.k[li], cache.v[li], lens1, H, D)
+                cache.append_step(li, qkv, self.rope, T, H, D)
+            o = cache.attend_step(li, qkv[:, :d], lens1, T, H, D)
             x2 = gemv(o, wo, resid=x)
             act = gemv_norm(x2, W.ln2, eps, wgu, swiglu=True)  # post_attention_layernorm + gate|up + SwiGLU: one launch
             x = gemv(act, wd, resid=x2)

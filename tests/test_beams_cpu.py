@@ -41,7 +41,8 @@ def test_share_prompt_kv_keyword_and_refusals():
 
 
 def test_default_and_flag_reach_beam_search(monkeypatch):
-    """share_prompt_kv=False (the default) calls _beam_search as before; True is passed on as a keyword."""
+    """share_prompt_kv=False (the default) and True reach _beam_search in the resolved call, fp8_kv beside them, and nothing of the modes
+    the calls do not ask for: no session, bans or guide."""
     seen = []
 
     class Cfg:
@@ -50,15 +51,16 @@ def test_default_and_flag_reach_beam_search(monkeypatch):
     class M:
         config = Cfg()
 
-    def beam(model, input_ids, *a, **kw):
-        seen.append((len(a), kw))
+    def beam(call, input_ids):
+        assert call.model.config is M.config and (call.num_beams, call.max_len) == (3, 7)
+        seen.append((call.share_prompt_kv, call.fp8_kv, call.session, call.bans, call.guide))
         return input_ids
 
     monkeypatch.setattr(G, "_beam_search", beam)
     ids = torch.ones(1, 4, dtype=torch.int64)
     G.generate(M(), ids, num_beams=3, max_new_tokens=3)
     G.generate(M(), ids, num_beams=3, max_new_tokens=3, share_prompt_kv=True, fp8_kv=True)
-    assert seen == [(11, dict(share_prompt_kv=False)), (11, dict(share_prompt_kv=True))]
+    assert seen == [(False, False, None, None, None), (True, True, None, None, None)]
 
 
 @pytest.mark.parametrize("seed", range(6))

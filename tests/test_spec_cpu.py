@@ -105,8 +105,9 @@ def test_options_and_refusals():
 
 
 def test_none_takes_the_plain_path(monkeypatch):
-    """prompt_lookup_num_tokens=None (the default) goes to _sample_cached with the arguments it always got; a number goes to the lookup
-    loop; every call fills engine.last_generate_stats."""
+    """prompt_lookup_num_tokens=None (the default) goes to _sample_cached with the lookup fields of the resolved call unset - and no
+    session, bans or guide, as in every call that does not ask for them; a number goes to the lookup loop; every call fills
+    engine.last_generate_stats."""
     calls = []
 
     class Cfg:
@@ -118,12 +119,13 @@ def test_none_takes_the_plain_path(monkeypatch):
     class M:
         config, engine = Cfg(), Eng()
 
-    def plain(model, input_ids, *a, **kw):
-        calls.append(("plain", len(a)))
+    def plain(call, input_ids):
+        assert call.model.config is M.config and call.max_len == 7 and call.stats is M.engine.last_generate_stats
+        calls.append(("plain", call.lookup, call.max_ngram, call.session, call.bans, call.guide))
         return torch.cat([input_ids, torch.zeros(1, 3, dtype=torch.int64)], dim=1)
 
-    def lookup(model, input_ids, *a, **kw):
-        calls.append(("lookup", a[-3], a[-2]))
+    def lookup(call, input_ids):
+        calls.append(("lookup", call.lookup, call.max_ngram, call.session, call.bans, call.guide))
         return input_ids
 
     monkeypatch.setattr(G, "_sample_cached", plain)
@@ -131,8 +133,8 @@ def test_none_takes_the_plain_path(monkeypatch):
     ids = torch.ones(1, 4, dtype=torch.int64)
     G.generate(M(), ids, max_new_tokens=3)
     G.generate(M(), ids, max_new_tokens=3, prompt_lookup_num_tokens=None)
-    assert calls == [("plain", 12), ("plain", 12)]  # the arguments _sample_cached always got
+    assert calls == [("plain", None, None, None, None, None)] * 2  # the plain loop, nothing of the other modes set
     assert M.engine.last_generate_stats == dict(plain_steps=2, verify_steps=0, drafted=0, accepted=0)
     G.generate(M(), ids, max_new_tokens=3, prompt_lookup_num_tokens=4, max_matching_ngram_size=3)
-    assert calls[-1] == ("lookup", 4, 3)
+    assert calls[-1] == ("lookup", 4, 3, None, None, None)
     assert M.engine.last_generate_stats == dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
