@@ -73,6 +73,54 @@ same fp32 value.  Where the summation order matters - decode attention, fp32 sto
 (The two "gemv fp8w" rows: fp8 weights with per-128-block scales, worst over every arm of mh_gemv_fp8w and the shapes of
 tests/test_fp8_componentwise_gpu.py, 16-bit stores with and without a residual.)
 
+Structured softmax rows (tests/attn_inputs.py; tests/test_attention_structured_gpu.py), measured on an MI355X on 2026-10-19, worst over the
+three prefill shapes, the forward forms 0 / 1 / 2, the fused-kv modes 0 / 1 / 2 and, for the cache kernels, over every placement and arm
+(16-bit and fp8 cache, merge launch / fused merge / one block).  F3 = the one-hot placements together, F4 = the sink with its two shifted
+copies.  A one-hot row's o IS a row of v and its dS cancels to nothing, so model and kernel both score 0.000 there: what those rows can show
+is a wrong reference or weight, which scores in the thousands (tests/test_attention_structured_cpu.py).  lse is held to
+|lse - lse64| <= c 2^-24 (|lse64| + A_row + 1) (`lse_c`), its model being fp32 scores and an fp32 logsumexp (`attention_lse_model`):
+
+    operation                         bf16 model  bf16 kernel   fp16 model  fp16 kernel
+    --------------------------------  ----------  -----------   ----------  -----------
+    F1 attention o                         0.626        0.750        0.653        0.653
+    F1 attention lse                       1.663        1.580        2.562        1.482
+    F1 attention dq 7-product              0.403        0.403        0.319        0.302
+    F1 attention dq 5-product              0.284        0.284        0.263        0.263
+    F1 attention dk 7-product              0.423        0.423        0.559        0.559
+    F1 attention dk 5-product              0.348        0.320        0.328        0.296
+    F1 attention dv 7-product              0.835        0.835        0.777        0.777
+    F1 attention dv 5-product              0.835        0.835        0.651        0.651
+    F2 attention o                         0.574        0.574        0.608        0.608
+    F2 attention lse                       1.663        1.580        1.662        1.482
+    F2 attention dq 7-product              0.344        0.344        0.299        0.299
+    F2 attention dq 5-product              0.284        0.284        0.263        0.263
+    F2 attention dk 7-product              0.556        0.556        0.857        0.857
+    F2 attention dk 5-product              0.484        0.484        0.118        0.118
+    F2 attention dv 7-product              0.871        0.871        0.970        0.970
+    F2 attention dv 5-product              0.871        0.871        0.268        0.268
+    F3 attention o                         0.000        0.000        0.000        0.000
+    F3 attention lse                       3.251        2.100        6.649        2.054
+    F3 attention dq 7-product              0.000        0.000        0.000        0.000
+    F3 attention dq 5-product              0.000        0.000        0.000        0.000
+    F3 attention dk 7-product              0.328        0.328        0.000        0.000
+    F3 attention dk 5-product              0.277        0.277        0.000        0.000
+    F3 attention dv 7-product              0.731        0.731        0.164        0.164
+    F3 attention dv 5-product              0.662        0.662        0.088        0.088
+    F4 attention o                         0.471        0.471        0.897        0.897
+    F4 attention lse                       9.939        2.866        8.169        3.793
+    F4 attention dq 7-product              0.003        0.003        0.021        0.021
+    F4 attention dq 5-product              0.003        0.003        0.021        0.021
+    F4 attention dk 7-product              0.324        0.324        0.975        0.975
+    F4 attention dk 5-product              0.252        0.252        0.960        0.960
+    F4 attention dv 7-product              0.782        0.782        0.972        0.972
+    F4 attention dv 5-product              0.661        0.661        0.914        0.914
+    placed one-hot key, all cache kernels  0.000        0.000        0.000        0.000
+    placed sink: attention decode          0.740        0.446        0.849        0.495
+    placed sink: attention decode multi    0.857        0.490        0.813        0.493
+    placed sink: attention extend          0.811        0.799        0.883        0.773
+    placed sink: attention extend branches 0.773        0.656        0.762        0.685
+    placed sink: attention decode beams    0.844        0.495        2.170        0.489
+
 The scaled-fp8 GEMMs are held to |got - want| <= ulp_out(want) + C_ACC 2^-24 sum|ab| instead (see the fp8 section below).  Worst observed
 (|got - want| - ulp) / (2^-24 sum|ab|) on an MI355X, against C_ACC = 512: the 4-wave kernel ~140 (K = 256, fp32 store); the 8-wave kernel over
 the shapes, weight forms and epilogues of tests/test_fp8_componentwise_gpu.py 167 (bf16 store), 185 (fp16 store), 175 (fp32 store), 71 / 104
@@ -458,6 +506,49 @@ def attention(q, k, v, do=None, *, causal, n_valid=None, model=None, allowed=Non
         for nm in ("dq", "dk", "dv"):
             out[nm] = rd(out[nm])
     return out
+
+
+def attention_magnitude(q, k, *, causal, n_valid=None):
+    """A_row [S]: the row's largest scale sum_d |q_id k_jd| over the pairs it attends (0 for a row that attends nothing): what one fp32
+    rounding of a partial sum of the score can move that score - and with it lse - by, in units of 2^-24."""
+    S, D = q.shape
+    n = S if n_valid is None else int(n_valid)
+    ar = torch.arange(S, device=q.device)
+    ok = (ar[None, :] < n) & (ar[:, None] < n)
+    if causal:
+        ok = ok & (ar[None, :] <= ar[:, None])
+    A = (q.double().abs() @ k.double().abs().t()) / math.sqrt(D)
+    return A.masked_fill(~ok, 0.0).amax(1)
+
+
+def attention_lse_model(q, k, *, causal, n_valid=None):
+    """The rounding model of lse: fp32 scores (one fp32 matmul, one multiply by scale), fp32 logsumexp; 0 for a row that attends nothing."""
+    S, D = q.shape
+    n = S if n_valid is None else int(n_valid)
+    ar = torch.arange(S, device=q.device)
+    ok = (ar[None, :] < n) & (ar[:, None] < n)
+    if causal:
+        ok = ok & (ar[None, :] <= ar[:, None])
+    s = ((q.float() @ k.float().t()) * torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32, device=q.device)).masked_fill(~ok, float("-inf"))
+    any_ok = ok.any(1)
+    s = torch.where(any_ok[:, None], s, torch.zeros_like(s))
+    return torch.where(any_ok, torch.logsumexp(s, 1), torch.zeros_like(s[:, 0]))
+
+
+def lse_c(got, lse64, A_row):
+    """lse (fp32, nats) is held to |lse - lse64| <= c 2^-24 (|lse64| + A_row + 1): lse is a score plus log l with l in [1, S], so it carries the
+    fp32 roundings of the score's partial sums (A_row), of its own magnitude, and of log l (the + 1).  -> (worst c, row).  Rows that attend
+    nothing (A_row == 0 and lse64 == 0) must be exactly zero."""
+    lse64 = lse64.double()
+    got = got.double().reshape(lse64.shape)
+    A_row = A_row.double().reshape(lse64.shape)
+    exact = (lse64 == 0) & (A_row == 0)
+    assert not bool((exact & (got != 0)).any()), "lse of a row that attends nothing must be exactly zero"
+    assert bool(torch.isfinite(got).all()), f"{int((~torch.isfinite(got)).sum())} non-finite lse values"
+    ratio = (got - lse64).abs() / (EPS16[torch.float32] * (lse64.abs() + A_row + 1.0))
+    ratio = torch.where(exact, torch.zeros_like(ratio), ratio)
+    c, i = ratio.reshape(-1).max(0)
+    return float(c), _unravel(int(i), lse64.shape)
 
 
 def f16_subnormal_B(ref, name, dtype):
