@@ -31,6 +31,8 @@
 //   mh_attn_extend_branches (+ _kv8)   the packed rows of several continuations of one prompt (model.score, engine.extend_branches): the
 //                       kernel of mh_attn_extend with a two-part horizon - the prompt's keys and the query's own continuation's.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
+#include <climits>
+
 #include "mh_common.h"
 
 // Weights and KV-cache rows are read ONCE per decode step by ONE CU: non-temporal loads (MI355X_MICROARCH.md "nt-weights": issued -> landed
@@ -151,194 +153,6 @@ __device__ __forceinline__ void stage_rmsnorm(const uint16_t* __restrict__ x, in
   __syncthreads();
 }
 
-// ROWS weight rows per wave, 4 waves per block.  LDSX: the block first stages a K-chunk of the MM activation rows in
-// LDS (MM x 4096 x 2 B = 64 KiB at MM = 8) and every wave reads it from there: without it each wave re-fetches all
-// activations through L1/L2 (8x the weight bytes at MM = 8; measured 1.9 TB/s of weights instead of 5).
-constexpr int GEMV_KC = 2048;  // 32 KiB at MM = 8: four blocks (16 waves) per CU keep enough weight loads in flight
-// NSTEP 512-element steps of every weight row are requested before any is consumed (2; 8 measured the same at N = 4096, where a
-// launch is 2048 short-lived waves: profiles/r02_decode_bench.txt).
-// NORM: x is the input of the RMSNorm that precedes the projection (HF LlamaRMSNorm, weight norm_w): every block normalises the MM
-// rows itself (8 KB each, L2-resident) into LDS - same chunk assignment, summation order and rounding as rmsnorm_fwd_row_k, so the
-// result equals the two launches bit for bit - instead of a separate kernel per norm (65 per decode step).
-template <int DT, int MM, int ROWS, bool LDSX, int NSTEP, bool NORM = false>
-__global__ __launch_bounds__(256) void gemv_k(const uint16_t* __restrict__ x, int64_t ldx, const uint16_t* __restrict__ W,
-                                              int64_t ldw, void* __restrict__ out, int64_t ldo, const uint16_t* __restrict__ resid,
-                                              int64_t ldr, int N, int K, int out_f32, int swi_ff, const uint16_t* __restrict__ norm_w,
-                                              float eps, RopeAppend ra) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [MM][GEMV_KC] when LDSX, [MM][K] when NORM
-  __shared__ float red[NORM ? MM : 1][4];
-  const int xstride = NORM ? K : GEMV_KC;
-  const int lane = threadIdx.x & 63;
-  // swi_ff > 0 (fused SwiGLU of the gate|up projection, W = [2 ff, K], N = ff outputs): the wave's rows are ROWS/2 gate rows n and
-  // the matching up rows ff + n, and it writes act[n] = silu(gate) * up of the ROUNDED 16-bit gate / up values (= mh_swiglu_fwd on
-  // the stored projection)
-  const int NR = swi_ff > 0 ? ROWS / 2 : ROWS;  // output columns per wave
-  const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
-  float acc[ROWS][MM];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
-  const uint16_t* wrow[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    int wr_ = swi_ff > 0 ? (r < NR ? min(n0 + r, N - 1) : swi_ff + min(n0 + r - NR, N - 1)) : min(n0 + r, N - 1);
-    if (ROWS == 2 && ra.tab) {  // rotary pair (c, c + D/2) of pair index n0 / 2 (N = 3 H D outputs, N / 2 pairs)
-      const int half = ra.D >> 1, pidx = min(n0 >> 1, (N >> 1) - 1), per_sec = ra.H * half;
-      const int sec = pidx / per_sec, rem = pidx - sec * per_sec, h = rem / half;
-      wr_ = sec * ra.H * ra.D + h * ra.D + (rem - h * half) + r * half;
-    }
-    wrow[r] = W + (int64_t)wr_ * ldw;
-  }
-  for (int kc = 0; kc < K; kc += GEMV_KC) {
-    const int klen = (LDSX && !NORM) ? min(GEMV_KC, K - kc) : K;  // (without LDS staging, or with the whole row staged, the K loop is not chunked)
-    if constexpr (NORM) {
-      stage_rmsnorm<DT, MM>(x, ldx, norm_w, eps, K, xs, red);
-    } else if constexpr (LDSX) {
-      if (kc) __syncthreads();
-      for (int i = threadIdx.x * 8; i < MM * klen; i += 256 * 8) {
-        const int m = i / klen, k = i - m * klen;
-        *(uint4*)(xs + m * GEMV_KC + k) = *(const uint4*)(x + (int64_t)m * ldx + kc + k);
-      }
-      __syncthreads();
-    }
-    if (n0 < N) {
-      for (int k0 = lane * 8; k0 < klen; k0 += 512 * NSTEP) {
-        uint4 wv[NSTEP][ROWS];
-#pragma unroll
-        for (int h2 = 0; h2 < NSTEP; ++h2)
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r)
-            wv[h2][r] = (k0 + h2 * 512 < klen) ? ld_stream16(wrow[r] + kc + k0 + h2 * 512) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int h2 = 0; h2 < NSTEP; ++h2) {
-          const int kk = k0 + h2 * 512;
-          if (kk >= klen) break;
-#pragma unroll
-          for (int m = 0; m < MM; ++m) {
-            uint4 xv;
-            if constexpr (LDSX || NORM) xv = *(const uint4*)(xs + m * xstride + kk);
-            else xv = *(const uint4*)(x + (int64_t)m * ldx + kc + kk);
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-              float a = acc[r][m];
-              a = dot2_acc<DT>(wv[h2][r].x, xv.x, a);
-              a = dot2_acc<DT>(wv[h2][r].y, xv.y, a);
-              a = dot2_acc<DT>(wv[h2][r].z, xv.z, a);
-              a = dot2_acc<DT>(wv[h2][r].w, xv.w, a);
-              acc[r][m] = a;
-            }
-          }
-        }
-      }
-    }
-    if constexpr (!LDSX || NORM) break;
-  }
-  if (n0 >= N) return;
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) acc[r][m] = wave_sum(acc[r][m]);
-  if constexpr (ROWS == 2) {
-    if (ra.tab) {
-      if (lane == 0) rope_append_store<DT, MM>(ra, n0 >> 1, acc[0], acc[1], (uint16_t*)out, ldo);
-      return;
-    }
-  }
-  if (lane == 0 && swi_ff > 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS / 2; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        const float g_ = ld16<DT>((uint16_t)st16<DT>(acc[r][m])), u_ = ld16<DT>((uint16_t)st16<DT>(acc[r + ROWS / 2][m]));
-        ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(swiglu_fwd1(g_, u_));
-      }
-    }
-    return;
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        float v = acc[r][m];
-        if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
-        if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
-        else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
-      }
-    }
-  }
-}
-
-// 1-2 activation rows and a SMALL N (the o / down projections: 4096 rows): one wave per ROWS weight rows gives 2048 waves for 256 CUs,
-// each streaming its rows for the whole of K - the launch is a ramp-up and a tail.  Here the four waves of a block share the same
-// ROWS rows and split K in four, i.e. four times as many waves with a quarter of the work each (all 32 wave slots of a CU busy); the
-// four partial sums meet in LDS and are added in a fixed order.
-template <int DT, int MM, int ROWS>
-__global__ __launch_bounds__(256) void gemv_ks_k(const uint16_t* __restrict__ x, int64_t ldx, const uint16_t* __restrict__ W, int64_t ldw,
-                                                 void* __restrict__ out, int64_t ldo, const uint16_t* __restrict__ resid, int64_t ldr, int N,
-                                                 int K, int out_f32) {
-  __shared__ float red[4][ROWS][MM];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n0 = blockIdx.x * ROWS;
-  const int kq = (((K >> 3) + 3) >> 2) << 3;  // elements per wave (a multiple of 8)
-  const int kb = wave * kq, ke = min(K, kb + kq);
-  float acc[ROWS][MM];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
-  const uint16_t* wrow[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) wrow[r] = W + (int64_t)min(n0 + r, N - 1) * ldw;
-  for (int k0 = kb + lane * 8; k0 < ke; k0 += 1024) {
-    uint4 wv[2][ROWS];
-    const bool two = k0 + 512 < ke;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) wv[0][r] = ld_stream16(wrow[r] + k0);
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) wv[1][r] = two ? ld_stream16(wrow[r] + k0 + 512) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2) {
-      if (h2 == 1 && !two) break;
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        const uint4 xv = *(const uint4*)(x + (int64_t)m * ldx + k0 + h2 * 512);
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          float a = acc[r][m];
-          a = dot2_acc<DT>(wv[h2][r].x, xv.x, a);
-          a = dot2_acc<DT>(wv[h2][r].y, xv.y, a);
-          a = dot2_acc<DT>(wv[h2][r].z, xv.z, a);
-          a = dot2_acc<DT>(wv[h2][r].w, xv.w, a);
-          acc[r][m] = a;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) {
-      const float t = wave_sum(acc[r][m]);
-      if (lane == 0) red[wave][r][m] = t;
-    }
-  __syncthreads();
-  if (threadIdx.x < ROWS * MM) {
-    const int r = threadIdx.x / MM, m = threadIdx.x % MM, n = n0 + r;
-    if (n < N) {
-      float v = (red[0][r][m] + red[1][r][m]) + (red[2][r][m] + red[3][r][m]);
-      if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
-      if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
-      else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
-    }
-  }
-}
-
 // ---- fp8 (OCP e4m3) weights with one fp32 scale per 128 consecutive k (BASELINE cfg 5's weight format), bf16/f16
 // activations: the decode step is weight-bandwidth-bound, so halving the weight bytes is worth ~2x on the GEMVs.
 // quant: q[n, k] = fp8(w[n, k] / s[n, k/128]),  s = max|w| over the block / 448 (1 if the block is all zero).
@@ -388,6 +202,24 @@ __device__ __forceinline__ void fp8x4_to_f32(uint32_t p, float* f) {
   const f2_ lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)p, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)p, true);
   f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
 }
+// eight e2m1 values (a dword of an MXFP4 row, the format at the end of this file) -> four packed 16-bit pairs, one instruction per pair
+// (gfx950 v_cvt_scalef32_pk_*_fp4 with scale 1: the third operand selects the byte, whose low nibble becomes the low half of the pair -
+// the stored order, so no swap); exact in both types
+template <int DT>
+__device__ __forceinline__ void fp4x8_to_pk16(uint32_t p, uint32_t* w) {
+  if constexpr (DT == MH_BF16) {
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 0));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 1));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 2));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 3));
+  } else {
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 0));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 1));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 2));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 3));
+  }
+}
+__device__ __forceinline__ float e8m0_to_f32(uint32_t byte) { return __uint_as_float(byte << 23); }  // byte in [1, 254]; 0 (a masked block) -> 0.0
 
 // ---- fp8 KV cache: K / V rows stored as e4m3 bytes [B, Smax, H*D] with one POWER-OF-TWO fp32 scale per (sequence, head, token), scales
 // [B, H, Smax] (head-major: one (b, h) block of the attention kernel reads its scales contiguously).  scale = 2^e, e the smallest integer
@@ -437,97 +269,217 @@ __global__ __launch_bounds__(256) void kv8_fill_k(const uint16_t* __restrict__ x
   if (part == 0) cs[((int64_t)b * H + h) * Smax + s] = kv8_pow2(e);
 }
 
-// y[m, n] = sum_kb s[n, kb] * sum_{k in block} q[n, k] x[m, k] (+ resid): one wave per weight row, 16 fp8 (16 B) per lane
-// and step (a lane's 16 values lie inside one 128-block), fp32 accumulate.  K % 16 == 0.
-// (NORM / swi_ff: the fused RMSNorm and SwiGLU of gemv_k, same semantics)
-template <int DT, int MM, int ROWS, bool LDSX, bool NORM = false>
-__global__ __launch_bounds__(256) void gemv_fp8w_k(const uint16_t* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ q,
-                                                   const float* __restrict__ sc, void* __restrict__ out, int64_t ldo,
-                                                   const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32, int swi_ff,
-                                                   const uint16_t* __restrict__ norm_w, float eps, RopeAppend ra) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t xs8[];  // [MM][GEMV_KC] when LDSX (as in gemv_k), [MM][K] when NORM
+// ---- 1..8 activation rows: ONE WAVE PER WEIGHT ROW -------------------------------------------------------------------------------
+// The projections of the decode step are one kernel over a weight-format policy.  A policy holds what differs between the formats and
+// nothing else: how a row is addressed, what 16 bytes of it are, which scale goes with them, and the per-format constants of the loop
+// and the launcher.  Everything in it resolves at compile time.
+//   EPL        elements per 16-byte lane load; a wave step is 64 * EPL elements, and K must be whole lane loads (K % EPL == 0)
+//   Row        a weight row: row(W, ldw, wsc, n, K)
+//   load       the streamed 16 bytes at element k of a row; ld_scale / scale: the stored scale of the block k lies in (a lane's EPL
+//              values lie inside one block) and its fp32 value.  SCALED: a load step's products are summed from 0 and join the
+//              accumulator by one fmaf(scale, partial, acc); otherwise they accumulate straight into it.
+//   pk16<DT>   values 8 d .. 8 d + 7 of a lane load -> four packed 16-bit pairs (exact), which meet the activations in dot2 instructions
+//   chunked    whether the K loop runs in chunks of GEMV_KC; nstep: wave steps of every row requested before any is consumed
+//   rows / has_rows   weight rows per wave for a launch, and the (activation rows, weight rows) forms that exist
+//   ks_span    elements per wave of the split-K form (HAS_KSPLIT)
+//   PAIR_MAX_K, MFMA_MIN, MFMA_PAIR_MIN   launcher limits, see gemv_wave_launch and the per-format fronts
+constexpr int GEMV_KC = 2048;  // 32 KiB at MM = 8: four blocks (16 waves) per CU keep enough weight loads in flight
+
+struct W16 {  // bf16 / f16 rows [N, ldw]
+  static constexpr int EPL = 8;
+  static constexpr bool SCALED = false, HAS_KSPLIT = true;
+  // chunked only where the chunk is what LDS holds.  nstep 2: 8 measured the same at N = 4096, where a launch is 2048 short-lived
+  // waves (profiles/r02_decode_bench.txt)
+  static constexpr bool chunked(bool ldsx, bool norm) { return ldsx && !norm; }
+  static constexpr int nstep(bool) { return 2; }
+  static constexpr int PAIR_MAX_K = INT_MAX;
+  // MFMA form from 3 rows (measured, profiles/r02_gemv_ab.txt: below that this kernel streams faster).  The paired epilogues (SwiGLU,
+  // RoPE + append) compete with one-wave-per-row-pair forms that fuse the same work and stream at 4.3-4.5 TB/s up to ~5 rows: measured
+  // crossover 6 rows with 16-bit weights, 4 with fp8
+  static constexpr int MFMA_MIN = 3, MFMA_PAIR_MIN = 6;
+  static inline int mfma_min = MFMA_MIN, mfma_pair_min = MFMA_PAIR_MIN;  // A/B: mh_gemv_mfma_min_rows, mh_gemv_mfma_pair_min_rows
+  // weight rows per wave: as many as keep >= ~1000 blocks in flight (N = 4096 with 4 rows per wave is 256 blocks = one per CU, measured
+  // at 1.4 TB/s; with 1 row per wave 3+ TB/s).  Fused SwiGLU: a wave's rows are gate/up PAIRS, so an even count
+  static int rows(int M, int N, bool swi, bool rope) { return rope ? 2 : M < 3 ? 2 : swi ? 4 : N >= 16384 ? 4 : N >= 8192 ? 2 : 1; }
+  static constexpr bool has_rows(int MM, int R) { return R == 2 || MM >= 3; }
+  static constexpr int ks_span(int K) { return (((K >> 3) + 3) >> 2) << 3; }  // a multiple of 8
+  struct Row { const uint16_t* w; };
+  struct Scale {};
+  static __device__ __forceinline__ Row row(const void* W, int64_t ldw, const void*, int n, int) { return {(const uint16_t*)W + (int64_t)n * ldw}; }
+  static __device__ __forceinline__ uint4 load(const Row& r, int k) { return ld_stream16(r.w + k); }
+  static __device__ __forceinline__ Scale ld_scale(const Row&, int) { return {}; }
+  static __device__ __forceinline__ float scale(Scale) { return 1.f; }
+  template <int DT>
+  static __device__ __forceinline__ void pk16(const uint4& v, int, uint32_t* w) { w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+};
+
+struct WFp8 {  // e4m3 bytes [N, K], one fp32 scale per 128 k [N, ceil(K / 128)] (mh_quant_fp8_b128)
+  static constexpr int EPL = 16;
+  static constexpr bool SCALED = true, HAS_KSPLIT = true;
+  // always chunked unless the whole row is staged, one step in flight: neither was measured against the 16-bit form's values
+  static constexpr bool chunked(bool, bool norm) { return !norm; }
+  static constexpr int nstep(bool) { return 1; }
+  static constexpr int PAIR_MAX_K = 8192;
+  static constexpr int MFMA_MIN = 3, MFMA_PAIR_MIN = 4;  // see W16
+  static inline int mfma_min = MFMA_MIN, mfma_pair_min = MFMA_PAIR_MIN;
+  static int rows(int M, int N, bool swi, bool rope) { return (swi || rope) ? 2 : M < 3 ? 1 : N >= 8192 ? 2 : 1; }  // (>= ~1000 blocks, see W16)
+  static constexpr bool has_rows(int, int R) { return R <= 2; }
+  static constexpr int ks_span(int K) { return ((((K + 127) / 128) + 3) >> 2) << 7; }  // whole 128-blocks
+  struct Row { const uint8_t* q; const float* s; };
+  using Scale = float;
+  static __device__ __forceinline__ Row row(const void* W, int64_t, const void* wsc, int n, int K) {
+    return {(const uint8_t*)W + (int64_t)n * K, (const float*)wsc + (int64_t)n * ((K + 127) / 128)};
+  }
+  static __device__ __forceinline__ uint4 load(const Row& r, int k) { return ld_stream16(r.q + k); }
+  static __device__ __forceinline__ Scale ld_scale(const Row& r, int k) { return r.s[k >> 7]; }
+  static __device__ __forceinline__ float scale(Scale s) { return s; }
+  template <int DT>
+  static __device__ __forceinline__ void pk16(const uint4& v, int d, uint32_t* w) {  // (4 cvt + 4 x MM dot2 per row instead of 4 cvt + 8 x MM fma)
+    fp8x4_to_pk16<DT>(d ? v.z : v.x, w[0], w[1]);
+    fp8x4_to_pk16<DT>(d ? v.w : v.y, w[2], w[3]);
+  }
+};
+
+struct WFp4 {  // MXFP4: e2m1 codes [N, K / 2], one E8M0 scale byte per 32 k [N, K / 32] (mh_quant_fp4_b32, at the end of this file)
+  static constexpr int EPL = 32;  // a lane load is exactly one scale block: 16 cvt + 16 x MM dot2 + MM fma per row and load
+  static constexpr bool SCALED = true, HAS_KSPLIT = false;
+  // chunked as the 16-bit form; a chunk is then exactly one wave step, so one step is in flight, and two where the loop is not
+  // chunked (1-2 rows, NORM).  No split-K form.  Not measured against the other formats' values
+  static constexpr bool chunked(bool ldsx, bool norm) { return ldsx && !norm; }
+  static constexpr int nstep(bool chunk) { return chunk ? 1 : 2; }
+  static constexpr int PAIR_MAX_K = 8192;
+  // the fp8 path's values.  Measured at Llama-7B size (profiles/decode_fp4_bench.txt, graph replay, context 613): with these thresholds
+  // the fp4 step is 1.78 ms at 1 row (fp8 1.97), 3.01 ms at 5 rows (fp8 3.57) and 3.53 ms at 8 rows (fp8 3.79); the same file holds the
+  // 3- and 5-row steps with the MFMA form switched off (mh_gemv_mfma_min_rows(17)).  The weights stream at ~2 TB/s at one row, well below
+  // the 16-bit path's 4.7: per byte the wave form issues twice the fp8 form's converts and dot2s, and a 2 KB row is two loads per lane -
+  // the step is faster than fp8 but not yet at the byte ratio.
+  static constexpr int MFMA_MIN = 3, MFMA_PAIR_MIN = 4;
+  static inline int mfma_min = MFMA_MIN, mfma_pair_min = MFMA_PAIR_MIN;
+  static int rows(int M, int N, bool swi, bool rope) { return WFp8::rows(M, N, swi, rope); }
+  static constexpr bool has_rows(int, int R) { return R <= 2; }
+  struct Row { const uint8_t* q; const uint8_t* s; };
+  using Scale = uint32_t;  // the stored byte
+  static __device__ __forceinline__ Row row(const void* W, int64_t, const void* wsc, int n, int K) {
+    return {(const uint8_t*)W + (int64_t)n * (K >> 1), (const uint8_t*)wsc + (int64_t)n * (K >> 5)};
+  }
+  static __device__ __forceinline__ uint4 load(const Row& r, int k) { return ld_stream16(r.q + (k >> 1)); }
+  static __device__ __forceinline__ Scale ld_scale(const Row& r, int k) { return r.s[k >> 5]; }
+  static __device__ __forceinline__ float scale(Scale b) { return e8m0_to_f32(b); }
+  template <int DT>
+  static __device__ __forceinline__ void pk16(const uint4& v, int d, uint32_t* w) { fp4x8_to_pk16<DT>(d == 0 ? v.x : d == 1 ? v.y : d == 2 ? v.z : v.w, w); }
+};
+
+template <int DT>
+__device__ __forceinline__ void gemv_store(void* out, int64_t ldo, const uint16_t* resid, int64_t ldr, int out_f32, int m, int n, float v) {
+  if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
+  if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
+  else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
+}
+
+// y[m, n] = sum_k x[m, k] W[n, k] (+ resid), W in the format Fmt (wsc: its scales): ROWS weight rows per wave, 4 waves per block, fp32
+// accumulate, shuffle reduction.  LDSX: the block first stages a K-chunk of the MM activation rows in LDS (MM x 4096 x 2 B = 64 KiB at
+// MM = 8) and every wave reads it from there: without it each wave re-fetches all activations through L1/L2 (8x the weight bytes at
+// MM = 8; measured 1.9 TB/s of weights instead of 5).
+// NORM: x is the input of the RMSNorm that precedes the projection (HF LlamaRMSNorm, weight norm_w): every block normalises the MM
+// rows itself (8 KB each, L2-resident) into LDS - same chunk assignment, summation order and rounding as rmsnorm_fwd_row_k, so the
+// result equals the two launches bit for bit - instead of a separate kernel per norm (65 per decode step).
+template <class Fmt, int DT, int MM, int ROWS, bool LDSX, bool NORM = false>
+__global__ __launch_bounds__(256) void gemv_k(const uint16_t* __restrict__ x, int64_t ldx, const void* __restrict__ W, int64_t ldw,
+                                              const void* __restrict__ wsc, void* __restrict__ out, int64_t ldo,
+                                              const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32, int swi_ff,
+                                              const uint16_t* __restrict__ norm_w, float eps, RopeAppend ra) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t xs[];  // [MM][GEMV_KC] when LDSX, [MM][K] when NORM
   __shared__ float red[NORM ? MM : 1][4];
+  constexpr bool CHUNK = Fmt::chunked(LDSX, NORM);  // (otherwise one pass over the whole of K)
+  constexpr int NSTEP = Fmt::nstep(CHUNK), EPL = Fmt::EPL, STEP = 64 * EPL;
   const int xstride = NORM ? K : GEMV_KC;
   const int lane = threadIdx.x & 63;
+  // swi_ff > 0 (fused SwiGLU of the gate|up projection, W = [2 ff, K], N = ff outputs): the wave's rows are ROWS/2 gate rows n and
+  // the matching up rows ff + n, and it writes act[n] = silu(gate) * up of the ROUNDED 16-bit gate / up values (= mh_swiglu_fwd on
+  // the stored projection)
   const int NR = swi_ff > 0 ? ROWS / 2 : ROWS;  // output columns per wave
   const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
-  const int nb = (K + 127) / 128;
   float acc[ROWS][MM];
 #pragma unroll
   for (int r = 0; r < ROWS; ++r)
 #pragma unroll
     for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
-  const uint8_t* qrow[ROWS];
-  const float* srow[ROWS];
+  typename Fmt::Row row[ROWS];
 #pragma unroll
   for (int r = 0; r < ROWS; ++r) {
     int n = swi_ff > 0 ? (r < NR ? min(n0 + r, N - 1) : swi_ff + min(n0 + r - NR, N - 1)) : min(n0 + r, N - 1);
-    if (ROWS == 2 && ra.tab) {  // rotary pair (as in gemv_k)
+    if (ROWS == 2 && ra.tab) {  // rotary pair (c, c + D/2) of pair index n0 / 2 (N = 3 H D outputs, N / 2 pairs)
       const int half = ra.D >> 1, pidx = min(n0 >> 1, (N >> 1) - 1), per_sec = ra.H * half;
       const int sec = pidx / per_sec, rem = pidx - sec * per_sec, h = rem / half;
       n = sec * ra.H * ra.D + h * ra.D + (rem - h * half) + r * half;
     }
-    qrow[r] = q + (int64_t)n * K;
-    srow[r] = sc + (int64_t)n * nb;
+    row[r] = Fmt::row(W, ldw, wsc, n, K);
   }
   for (int kc = 0; kc < K; kc += GEMV_KC) {
-    const int klen = NORM ? K : min(GEMV_KC, K - kc);
+    const int klen = CHUNK ? min(GEMV_KC, K - kc) : K;
     if constexpr (NORM) {
-      stage_rmsnorm<DT, MM>(x, ldx, norm_w, eps, K, xs8, red);
+      stage_rmsnorm<DT, MM>(x, ldx, norm_w, eps, K, xs, red);
     } else if constexpr (LDSX) {
       if (kc) __syncthreads();
       for (int i = threadIdx.x * 8; i < MM * klen; i += 256 * 8) {
         const int m = i / klen, k = i - m * klen;
-        *(uint4*)(xs8 + m * GEMV_KC + k) = *(const uint4*)(x + (int64_t)m * ldx + kc + k);
+        *(uint4*)(xs + m * GEMV_KC + k) = *(const uint4*)(x + (int64_t)m * ldx + kc + k);
       }
       __syncthreads();
     }
     if (n0 < N) {
-      for (int k0 = lane * 16; k0 < klen; k0 += 1024) {
-        uint4 qv[ROWS];
-        float s[ROWS];
+      for (int k0 = lane * EPL; k0 < klen; k0 += STEP * NSTEP) {
+        uint4 wv[NSTEP][ROWS];
+        typename Fmt::Scale sv[NSTEP][ROWS];
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          qv[r] = ld_stream16(qrow[r] + kc + k0);
-          s[r] = srow[r][(kc + k0) >> 7];
-        }
-        float p[ROWS][MM];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-          for (int m = 0; m < MM; ++m) p[r][m] = 0.f;
-#pragma unroll
-        for (int hlf = 0; hlf < 2; ++hlf) {  // 8 values at a time: the weights become packed 16-bit pairs (exact) and meet the activations in
-                                             // dot2 instructions, as in gemv_k (4 cvt + 4 x MM dot2 per row instead of 4 cvt + 8 x MM fma)
-          uint32_t w[ROWS][4];
+        for (int u = 0; u < NSTEP; ++u)
 #pragma unroll
           for (int r = 0; r < ROWS; ++r) {
-            fp8x4_to_pk16<DT>(hlf ? qv[r].z : qv[r].x, w[r][0], w[r][1]);
-            fp8x4_to_pk16<DT>(hlf ? qv[r].w : qv[r].y, w[r][2], w[r][3]);
+            const int kk = k0 + u * STEP;
+            const bool ok = kk < klen;  // (the first slot's test folds to the loop condition)
+            wv[u][r] = ok ? Fmt::load(row[r], kc + kk) : make_uint4(0, 0, 0, 0);
+            sv[u][r] = ok ? Fmt::ld_scale(row[r], kc + kk) : typename Fmt::Scale{};
           }
 #pragma unroll
-          for (int m = 0; m < MM; ++m) {
-            uint4 xa;
-            if constexpr (LDSX || NORM) xa = *(const uint4*)(xs8 + m * xstride + k0 + 8 * hlf);
-            else xa = *(const uint4*)(x + (int64_t)m * ldx + kc + k0 + 8 * hlf);
+        for (int u = 0; u < NSTEP; ++u) {
+          const int kk = k0 + u * STEP;
+          if (u > 0 && kk >= klen) break;
+          float p[ROWS][MM];
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-              float a = p[r][m];
-              a = dot2_acc<DT>(w[r][0], xa.x, a);
-              a = dot2_acc<DT>(w[r][1], xa.y, a);
-              a = dot2_acc<DT>(w[r][2], xa.z, a);
-              a = dot2_acc<DT>(w[r][3], xa.w, a);
-              p[r][m] = a;
+          for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+            for (int m = 0; m < MM; ++m) p[r][m] = Fmt::SCALED ? 0.f : acc[r][m];
+#pragma unroll
+          for (int d = 0; d < EPL / 8; ++d) {  // 8 values at a time
+            uint32_t w[ROWS][4];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) Fmt::template pk16<DT>(wv[u][r], d, w[r]);
+#pragma unroll
+            for (int m = 0; m < MM; ++m) {
+              uint4 xa;
+              if constexpr (LDSX || NORM) xa = *(const uint4*)(xs + m * xstride + kk + 8 * d);
+              else xa = *(const uint4*)(x + (int64_t)m * ldx + kc + kk + 8 * d);
+#pragma unroll
+              for (int r = 0; r < ROWS; ++r) {
+                float a = p[r][m];
+                a = dot2_acc<DT>(w[r][0], xa.x, a);
+                a = dot2_acc<DT>(w[r][1], xa.y, a);
+                a = dot2_acc<DT>(w[r][2], xa.z, a);
+                a = dot2_acc<DT>(w[r][3], xa.w, a);
+                p[r][m] = a;
+              }
             }
           }
+#pragma unroll
+          for (int r = 0; r < ROWS; ++r) {
+            const float s = Fmt::scale(sv[u][r]);
+#pragma unroll
+            for (int m = 0; m < MM; ++m) acc[r][m] = Fmt::SCALED ? fmaf(s, p[r][m], acc[r][m]) : p[r][m];
+          }
         }
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-          for (int m = 0; m < MM; ++m) acc[r][m] = fmaf(s[r], p[r][m], acc[r][m]);
       }
     }
-    if constexpr (NORM) break;
+    if constexpr (!CHUNK) break;
   }
   if (n0 >= N) return;
 #pragma unroll
@@ -559,82 +511,81 @@ __global__ __launch_bounds__(256) void gemv_fp8w_k(const uint16_t* __restrict__ 
       const int n = n0 + r;
       if (n >= N) break;
 #pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        float v = acc[r][m];
-        if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
-        if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
-        else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
-      }
+      for (int m = 0; m < MM; ++m) gemv_store<DT>(out, ldo, resid, ldr, out_f32, m, n, acc[r][m]);
     }
   }
 }
 
-
-// ---- 3..16 activation rows: the matrix cores do the multiplies --------------------------------------------------------------------
-// gemv_ks_k with fp8 weights: the four waves of a block share ROWS rows and split K (a multiple of 128 per wave, so a lane's 16 values
-// stay inside one scale block); partial sums meet in LDS, fixed order.
-template <int DT, int MM, int ROWS>
-__global__ __launch_bounds__(256) void gemv_fp8w_ks_k(const uint16_t* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ q,
-                                                      const float* __restrict__ sc, void* __restrict__ out, int64_t ldo,
-                                                      const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32) {
+// 1-2 activation rows and a SMALL N (the o / down projections: 4096 rows): one wave per ROWS weight rows gives 2048 waves for 256 CUs,
+// each streaming its rows for the whole of K - the launch is a ramp-up and a tail.  Here the four waves of a block share the same
+// ROWS rows and split K in four (Fmt::ks_span elements each, so a lane's values stay inside one scale block), i.e. four times as many
+// waves with a quarter of the work each (all 32 wave slots of a CU busy); the four partial sums meet in LDS and are added in a fixed order.
+template <class Fmt, int DT, int MM, int ROWS>
+__global__ __launch_bounds__(256) void gemv_ks_k(const uint16_t* __restrict__ x, int64_t ldx, const void* __restrict__ W, int64_t ldw,
+                                                 const void* __restrict__ wsc, void* __restrict__ out, int64_t ldo,
+                                                 const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32) {
   __shared__ float red[4][ROWS][MM];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = blockIdx.x * ROWS;
-  const int nb = (K + 127) / 128;
-  const int kq = ((nb + 3) >> 2) << 7;  // elements per wave: whole 128-blocks
-  const int kb = wave * kq, ke = min(K, kb + kq);
+  constexpr int NSTEP = Fmt::nstep(false), EPL = Fmt::EPL, STEP = 64 * EPL;
+  const int kq = Fmt::ks_span(K), kb = wave * kq, ke = min(K, kb + kq);
   float acc[ROWS][MM];
 #pragma unroll
   for (int r = 0; r < ROWS; ++r)
 #pragma unroll
     for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
-  const uint8_t* qrow[ROWS];
-  const float* srow[ROWS];
+  typename Fmt::Row row[ROWS];
 #pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, N - 1);
-    qrow[r] = q + (int64_t)n * K;
-    srow[r] = sc + (int64_t)n * nb;
-  }
-  for (int k0 = kb + lane * 16; k0 < ke; k0 += 1024) {
-    uint4 qv[ROWS];
-    float s[ROWS];
+  for (int r = 0; r < ROWS; ++r) row[r] = Fmt::row(W, ldw, wsc, min(n0 + r, N - 1), K);
+  // the K loop of gemv_k over the wave's range, x from global memory.  (Written out a second time: as one inlined function the two loops
+  // compile to different register allocations than today's - 38 -> 42 VGPRs in gemv_k<W16, bf16, 7, 1, true> - for no gain.)
+  for (int k0 = kb + lane * EPL; k0 < ke; k0 += STEP * NSTEP) {
+    uint4 wv[NSTEP][ROWS];
+    typename Fmt::Scale sv[NSTEP][ROWS];
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      qv[r] = ld_stream16(qrow[r] + k0);
-      s[r] = srow[r][k0 >> 7];
-    }
-    float p[ROWS][MM];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-      for (int m = 0; m < MM; ++m) p[r][m] = 0.f;
-#pragma unroll
-    for (int hlf = 0; hlf < 2; ++hlf) {
-      uint32_t w[ROWS][4];
+    for (int u = 0; u < NSTEP; ++u)
 #pragma unroll
       for (int r = 0; r < ROWS; ++r) {
-        fp8x4_to_pk16<DT>(hlf ? qv[r].z : qv[r].x, w[r][0], w[r][1]);
-        fp8x4_to_pk16<DT>(hlf ? qv[r].w : qv[r].y, w[r][2], w[r][3]);
+        const int kk = k0 + u * STEP;
+        const bool ok = kk < ke;
+        wv[u][r] = ok ? Fmt::load(row[r], kk) : make_uint4(0, 0, 0, 0);
+        sv[u][r] = ok ? Fmt::ld_scale(row[r], kk) : typename Fmt::Scale{};
       }
 #pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        const uint4 xa = *(const uint4*)(x + (int64_t)m * ldx + k0 + 8 * hlf);
+    for (int u = 0; u < NSTEP; ++u) {
+      const int kk = k0 + u * STEP;
+      if (u > 0 && kk >= ke) break;
+      float p[ROWS][MM];
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-          float a = p[r][m];
-          a = dot2_acc<DT>(w[r][0], xa.x, a);
-          a = dot2_acc<DT>(w[r][1], xa.y, a);
-          a = dot2_acc<DT>(w[r][2], xa.z, a);
-          a = dot2_acc<DT>(w[r][3], xa.w, a);
-          p[r][m] = a;
+      for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int m = 0; m < MM; ++m) p[r][m] = Fmt::SCALED ? 0.f : acc[r][m];
+#pragma unroll
+      for (int d = 0; d < EPL / 8; ++d) {  // 8 values at a time
+        uint32_t w[ROWS][4];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) Fmt::template pk16<DT>(wv[u][r], d, w[r]);
+#pragma unroll
+        for (int m = 0; m < MM; ++m) {
+          const uint4 xa = *(const uint4*)(x + (int64_t)m * ldx + kk + 8 * d);
+#pragma unroll
+          for (int r = 0; r < ROWS; ++r) {
+            float a = p[r][m];
+            a = dot2_acc<DT>(w[r][0], xa.x, a);
+            a = dot2_acc<DT>(w[r][1], xa.y, a);
+            a = dot2_acc<DT>(w[r][2], xa.z, a);
+            a = dot2_acc<DT>(w[r][3], xa.w, a);
+            p[r][m] = a;
+          }
         }
       }
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const float s = Fmt::scale(sv[u][r]);
+#pragma unroll
+        for (int m = 0; m < MM; ++m) acc[r][m] = Fmt::SCALED ? fmaf(s, p[r][m], acc[r][m]) : p[r][m];
+      }
     }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-      for (int m = 0; m < MM; ++m) acc[r][m] = fmaf(s[r], p[r][m], acc[r][m]);
   }
 #pragma unroll
   for (int r = 0; r < ROWS; ++r)
@@ -646,14 +597,11 @@ __global__ __launch_bounds__(256) void gemv_fp8w_ks_k(const uint16_t* __restrict
   __syncthreads();
   if (threadIdx.x < ROWS * MM) {
     const int r = threadIdx.x / MM, m = threadIdx.x % MM, n = n0 + r;
-    if (n < N) {
-      float v = (red[0][r][m] + red[1][r][m]) + (red[2][r][m] + red[3][r][m]);
-      if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
-      if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
-      else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
-    }
+    if (n < N) gemv_store<DT>(out, ldo, resid, ldr, out_f32, m, n, (red[0][r][m] + red[1][r][m]) + (red[2][r][m] + red[3][r][m]));
   }
 }
+
+// ---- 3..16 activation rows: the matrix cores do the multiplies --------------------------------------------------------------------
 
 // At batch 1-2 the one-wave-per-row kernel above is HBM-bound; from ~4 rows on its VALU work (rows x 8 dot2 per 16 B of weights, x 2
 // more with fp8 dequantisation) is what limits it.  Here a block owns 16 x RG weight rows and its NW waves split K: every lane loads
@@ -1614,108 +1562,130 @@ __global__ __launch_bounds__(256) void ngram_draft_k(const int64_t* __restrict__
 
 }  // namespace
 
-// activation-row count from which the MFMA form is used (measured, profiles/r02_gemv_ab.txt: 3 rows for both weight formats - below
-// that the one-wave-per-row kernels stream faster); mh_gemv_mfma_min_rows(r) overrides both (A/B switch; 17 = never)
-static int g_gemv_mfma_min_rows = 3, g_gemv_mfma_min_rows_fp8 = 3;
-// the forms with a paired epilogue (SwiGLU, RoPE + append) compete with one-wave-per-row-pair kernels that already fuse the same work
-// and stream at 4.3-4.5 TB/s up to ~5 rows: measured crossover 6 rows with 16-bit weights, 4 with fp8 (mh_gemv_mfma_pair_min_rows)
-static int g_gemv_mfma_pair_min = 6, g_gemv_mfma_pair_min_fp8 = 4;
-// MXFP4 weights (mh_gemv_fp4w*, at the end of this file): the same thresholds (see gemv_fp4w_impl)
-static int g_gemv_mfma_min_rows_fp4 = 3, g_gemv_mfma_pair_min_fp4 = 4;
+// A/B switches.  mh_gemv_mfma_min_rows(r): activation-row count from which the MFMA forms are used, all formats and epilogues
+// (17 = never, <= 0 = the defaults of the formats); mh_gemv_mfma_pair_min_rows: the paired forms' threshold, 16-bit and fp8 weights
 static int g_gemv_ksplit = 1;  // 1-2 rows, N <= 8192: K split over the four waves of a block (A-B switch: mh_gemv_ksplit)
 extern "C" void mh_gemv_ksplit(int on) { g_gemv_ksplit = on ? 1 : 0; }
+template <class Fmt>
+static void gemv_set_mfma_min(int rows, int rows_pair) {
+  Fmt::mfma_min = rows > 0 ? rows : Fmt::MFMA_MIN;
+  Fmt::mfma_pair_min = rows_pair > 0 ? rows_pair : Fmt::MFMA_PAIR_MIN;
+}
 extern "C" void mh_gemv_mfma_min_rows(int rows) {
-  if (rows <= 0) { g_gemv_mfma_min_rows = 3; g_gemv_mfma_min_rows_fp8 = 3; g_gemv_mfma_pair_min = 6; g_gemv_mfma_pair_min_fp8 = 4; }  // the defaults
-  else g_gemv_mfma_min_rows = g_gemv_mfma_min_rows_fp8 = g_gemv_mfma_pair_min = g_gemv_mfma_pair_min_fp8 = rows;
-  if (rows <= 0) { g_gemv_mfma_min_rows_fp4 = 3; g_gemv_mfma_pair_min_fp4 = 4; }
-  else g_gemv_mfma_min_rows_fp4 = g_gemv_mfma_pair_min_fp4 = rows;
+  gemv_set_mfma_min<W16>(rows, rows);
+  gemv_set_mfma_min<WFp8>(rows, rows);
+  gemv_set_mfma_min<WFp4>(rows, rows);
 }
 extern "C" void mh_gemv_mfma_pair_min_rows(int rows16, int rows_fp8) {
-  g_gemv_mfma_pair_min = rows16 > 0 ? rows16 : 6;
-  g_gemv_mfma_pair_min_fp8 = rows_fp8 > 0 ? rows_fp8 : 4;
+  gemv_set_mfma_min<W16>(W16::mfma_min, rows16);
+  gemv_set_mfma_min<WFp8>(WFp8::mfma_min, rows_fp8);
 }
 
-static int gemv_impl(const void* x, int64_t ldx, const void* W, int64_t ldw, void* out, int64_t ldo, const void* resid,
-                     int64_t ldr, int M, int N, int K, int dt, int out_f32, int swi_ff, const void* norm_w, float eps, const RopeAppend& ra,
-                     void* stream) {
-  if (!x || !W || !out || M <= 0 || M > 16 || N <= 0 || K <= 0 || (K & 7) || (ldx & 7) || (ldw & 7)) return MH_ERR_ARG;
-  if (!aligned16(x) || !aligned16(W)) return MH_ERR_ARG;
-  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  if (norm_w && (M > 8 || K > 8192 || !aligned16(norm_w))) return MH_ERR_ARG;  // fused RMSNorm: row-per-wave form, whole row in LDS
-  if (ra.tab && (swi_ff || (N & 1))) return MH_ERR_ARG;
-  if ((swi_ff || ra.tab) && (resid || out_f32)) return MH_ERR_ARG;
-  // 3+ rows: the MFMA form (above) is HBM-bound where this one turns VALU-bound (the rotary-pair form needs D/2 to be whole 16-row groups)
-  if (!norm_w && M >= ((swi_ff || ra.tab) ? g_gemv_mfma_pair_min : g_gemv_mfma_min_rows) && (K % 32) == 0 &&
-      (!ra.tab || ((ra.D >> 1) % 16 == 0 && N == 3 * ra.H * ra.D))) {
-    if (dt == MH_BF16) return launch_gemv_mfma<MH_BF16, false>(x, ldx, W, ldw, nullptr, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, ra, as_stream(stream));
-    return launch_gemv_mfma<MH_F16, false>(x, ldx, W, ldw, nullptr, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, ra, as_stream(stream));
+// one projection of the decode step as the entry points hand it to the launchers (W, ldw, wsc: the weights in the launcher's format)
+struct GemvArgs {
+  const void* x; int64_t ldx; const void* W; int64_t ldw; const void* wsc; void* out; int64_t ldo; const void* resid; int64_t ldr;
+  int M, N, K, dt, out_f32, swi_ff;
+  const void* norm_w; float eps; RopeAppend ra; void* stream;
+};
+
+// the argument checks every format shares; 0 or the error code
+template <class Fmt>
+static int gemv_check(const GemvArgs& a) {
+  if (!a.x || !a.W || (Fmt::SCALED && !a.wsc) || !a.out || a.M <= 0 || a.M > 16 || a.N <= 0 || a.K <= 0 || (a.K % Fmt::EPL) || (a.ldx & 7) ||
+      (a.ldw & 7))
+    return MH_ERR_ARG;
+  if (!aligned16(a.x) || !aligned16(a.W)) return MH_ERR_ARG;
+  if (a.dt != MH_BF16 && a.dt != MH_F16) return MH_ERR_DTYPE;
+  if (a.norm_w && (a.M > 8 || a.K > 8192 || !aligned16(a.norm_w))) return MH_ERR_ARG;  // fused RMSNorm: row-per-wave form, whole row in LDS
+  if (a.ra.tab && (a.swi_ff || (a.N & 1))) return MH_ERR_ARG;
+  if ((a.swi_ff || a.ra.tab) && (a.resid || a.out_f32)) return MH_ERR_ARG;
+  return MH_OK;
+}
+// whether a launch has the row count of the format's MFMA form (3+ rows: that form is HBM-bound where the wave form turns VALU-bound)
+template <class Fmt>
+static bool gemv_mfma_rows(const GemvArgs& a) {
+  return !a.norm_w && a.M >= ((a.swi_ff || a.ra.tab) ? Fmt::mfma_pair_min : Fmt::mfma_min);
+}
+
+template <class Fmt, int DT, int MM, int ROWS, bool LDSX, bool NORM>
+static void gemv_wave_go(const GemvArgs& a) {
+  const int cols = a.swi_ff ? ROWS / 2 : ROWS;  // output columns per wave (N counts outputs: gate/up pairs with SwiGLU)
+  const size_t lds = NORM ? (size_t)MM * a.K * 2 : LDSX ? (size_t)MM * GEMV_KC * 2 : 0;
+  static bool attr = false;
+  if (lds && !attr) {
+    hipFuncSetAttribute((const void*)gemv_k<Fmt, DT, MM, ROWS, LDSX, NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, MM * 8192 * 2);
+    attr = true;
   }
-  if (M > 8) return MH_ERR_ARG;
-  // weight rows per wave: as many as keep >= ~1000 blocks in flight (N = 4096 with 4 rows per wave is 256 blocks = one per
-  // CU, measured at 1.4 TB/s; with 1 row per wave 3+ TB/s)
-  if (g_gemv_ksplit && M <= 2 && !swi_ff && !norm_w && !ra.tab && N <= 8192 && K >= 2048) {  // small N, 1-2 rows: K split over the block's waves
-    const dim3 gridk((N + 1) / 2), blockk(256);
-    hipStream_t stk = as_stream(stream);
-    if (dt == MH_BF16) {
-      if (M == 1) hipLaunchKernelGGL((gemv_ks_k<MH_BF16, 1, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint16_t*)W, ldw, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-      else hipLaunchKernelGGL((gemv_ks_k<MH_BF16, 2, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint16_t*)W, ldw, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-    } else {
-      if (M == 1) hipLaunchKernelGGL((gemv_ks_k<MH_F16, 1, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint16_t*)W, ldw, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-      else hipLaunchKernelGGL((gemv_ks_k<MH_F16, 2, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint16_t*)W, ldw, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-    }
-    MH_LAUNCH_CHECK();
-  }
-  // (fused SwiGLU: a wave's rows are gate/up PAIRS, so an even count; N counts outputs = pairs)
-  const int rows = ra.tab ? 2 : swi_ff ? (M < 3 ? 2 : 4) : (M < 3 ? 2 : (N >= 16384 ? 4 : (N >= 8192 ? 2 : 1)));
-  const int cols = swi_ff ? rows / 2 : rows;  // output columns per wave
-  const dim3 grid((N + 4 * cols - 1) / (4 * cols)), block(256);
-  hipStream_t st = as_stream(stream);
-#define GO1(DT_, MM_, R_, L_, NS_, NRM_, LDS_)                                                                                     \
-  do {                                                                                                                             \
-    const size_t lds_ = (LDS_);                                                                                                    \
-    static bool attr_ = false;                                                                                                     \
-    if (lds_ && !attr_) {                                                                                                          \
-      hipFuncSetAttribute((const void*)gemv_k<DT_, MM_, R_, L_, NS_, NRM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MM_ * 8192 * 2)); \
-      attr_ = true;                                                                                                                \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((gemv_k<DT_, MM_, R_, L_, NS_, NRM_>), grid, block, lds_, st, (const uint16_t*)x, ldx, (const uint16_t*)W, ldw, out, ldo, \
-                       (const uint16_t*)resid, ldr, N, K, out_f32, swi_ff, (const uint16_t*)norm_w, eps, ra);                      \
+  hipLaunchKernelGGL((gemv_k<Fmt, DT, MM, ROWS, LDSX, NORM>), dim3((a.N + 4 * cols - 1) / (4 * cols)), dim3(256), lds, as_stream(a.stream),
+                     (const uint16_t*)a.x, a.ldx, a.W, a.ldw, a.wsc, a.out, a.ldo, (const uint16_t*)a.resid, a.ldr, a.N, a.K, a.out_f32,
+                     a.swi_ff, (const uint16_t*)a.norm_w, a.eps, a.ra);
+}
+template <class Fmt, int DT, int MM>
+static void gemv_wave_rows(const GemvArgs& a, int rows) {
+#define GO(R_)                                                                                                          \
+  do {                                                                                                                  \
+    if constexpr (Fmt::has_rows(MM, R_))                                                                                \
+      if (rows == R_) {                                                                                                 \
+        if (a.norm_w) return gemv_wave_go<Fmt, DT, MM, R_, true, true>(a);                                              \
+        return gemv_wave_go<Fmt, DT, MM, R_, (MM >= 3), false>(a); /* 1-2 activation rows: no LDS staging */            \
+      }                                                                                                                 \
   } while (0)
-#define GO(DT_, MM_, R_, L_, NS_)                                                                                                  \
-  do {                                                                                                                             \
-    if (norm_w) GO1(DT_, MM_, R_, true, NS_, true, (size_t)MM_ * K * 2);                                                           \
-    else GO1(DT_, MM_, R_, L_, NS_, false, L_ ? (size_t)MM_ * GEMV_KC * 2 : 0);                                                    \
-  } while (0)
-#define GOR(DT_, MM_)                                                                  \
-  do {                                                                                 \
-    if (rows == 4) GO(DT_, MM_, 4, true, 2); else if (rows == 2) GO(DT_, MM_, 2, true, 2); else GO(DT_, MM_, 1, true, 2); \
-  } while (0)
-#define GOS(DT_, MM_) GO(DT_, MM_, 2, false, 2) /* 1-2 activation rows: no LDS staging */
-#define GOM(DT_)                                                                                                       \
-  switch (M) {                                                                                                         \
-    case 1: GOS(DT_, 1); break; case 2: GOS(DT_, 2); break; case 3: GOR(DT_, 3); break;                               \
-    case 4: GOR(DT_, 4); break; case 5: GOR(DT_, 5); break; case 6: GOR(DT_, 6); break;                               \
-    case 7: GOR(DT_, 7); break; default: GOR(DT_, 8); break;                                                           \
-  }
-  if (dt == MH_BF16) { GOM(MH_BF16); } else { GOM(MH_F16); }
-#undef GOM
-#undef GOS
-#undef GOR
+  GO(1); GO(2); GO(4);
 #undef GO
-#undef GO1
+}
+template <class Fmt, int DT, int MM>
+static void gemv_ks_go(const GemvArgs& a) {
+  hipLaunchKernelGGL((gemv_ks_k<Fmt, DT, MM, 2>), dim3((a.N + 1) / 2), dim3(256), 0, as_stream(a.stream), (const uint16_t*)a.x, a.ldx, a.W, a.ldw,
+                     a.wsc, a.out, a.ldo, (const uint16_t*)a.resid, a.ldr, a.N, a.K, a.out_f32);
+}
+template <class Fmt, int DT>
+static int gemv_wave_dt(const GemvArgs& a) {
+  if constexpr (Fmt::HAS_KSPLIT) {
+    if (g_gemv_ksplit && a.M <= 2 && !a.swi_ff && !a.norm_w && !a.ra.tab && a.N <= 8192 && a.K >= 2048) {  // small N: K split over the block's waves
+      if (a.M == 1) gemv_ks_go<Fmt, DT, 1>(a); else gemv_ks_go<Fmt, DT, 2>(a);
+      MH_LAUNCH_CHECK();
+    }
+  }
+  const int rows = Fmt::rows(a.M, a.N, a.swi_ff != 0, a.ra.tab != nullptr);
+  switch (a.M) {
+    case 1: gemv_wave_rows<Fmt, DT, 1>(a, rows); break;
+    case 2: gemv_wave_rows<Fmt, DT, 2>(a, rows); break;
+    case 3: gemv_wave_rows<Fmt, DT, 3>(a, rows); break;
+    case 4: gemv_wave_rows<Fmt, DT, 4>(a, rows); break;
+    case 5: gemv_wave_rows<Fmt, DT, 5>(a, rows); break;
+    case 6: gemv_wave_rows<Fmt, DT, 6>(a, rows); break;
+    case 7: gemv_wave_rows<Fmt, DT, 7>(a, rows); break;
+    default: gemv_wave_rows<Fmt, DT, 8>(a, rows); break;
+  }
   MH_LAUNCH_CHECK();
+}
+// the one-wave-per-row form of a checked projection (gemv_check) that did not go to an MFMA form: M <= 8
+template <class Fmt>
+static int gemv_wave_launch(const GemvArgs& a) {
+  if (a.M > 8 || ((a.swi_ff || a.ra.tab) && a.K > Fmt::PAIR_MAX_K)) return MH_ERR_ARG;
+  return a.dt == MH_BF16 ? gemv_wave_dt<Fmt, MH_BF16>(a) : gemv_wave_dt<Fmt, MH_F16>(a);
+}
+
+static int gemv_impl(const GemvArgs& a) {
+  if (const int e = gemv_check<W16>(a)) return e;
+  // (the rotary-pair MFMA form needs D/2 to be whole 16-row groups)
+  if (gemv_mfma_rows<W16>(a) && (a.K % 32) == 0 && (!a.ra.tab || ((a.ra.D >> 1) % 16 == 0 && a.N == 3 * a.ra.H * a.ra.D))) {
+    auto mfma = a.dt == MH_BF16 ? launch_gemv_mfma<MH_BF16, false> : launch_gemv_mfma<MH_F16, false>;
+    return mfma(a.x, a.ldx, a.W, a.ldw, nullptr, a.out, a.ldo, a.resid, a.ldr, a.M, a.N, a.K, a.out_f32, a.swi_ff, a.ra, as_stream(a.stream));
+  }
+  return gemv_wave_launch<W16>(a);
 }
 
 extern "C" int mh_gemv(const void* x, int64_t ldx, const void* W, int64_t ldw, void* out, int64_t ldo, const void* resid,
                        int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream) {
-  return gemv_impl(x, ldx, W, ldw, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream);
+  return gemv_impl({x, ldx, W, ldw, nullptr, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream});
 }
 // act[M, ff] = silu(x Wg^T) * (x Wu^T) with Wgu = [Wg; Wu] [2 ff, K] (HF LlamaMLP gate / up of the decode step): one launch, the
 // gate|up projection never reaches memory (gate / up are rounded to 16 bits before the activation, as the two launches do).  M <= 16 rows (MFMA form from 3 rows on).
 extern "C" int mh_gemv_swiglu(const void* x, int64_t ldx, const void* Wgu, int64_t ldw, void* act, int64_t ldo, int M, int ff, int K, int dt,
                               void* stream) {
   if (ff <= 0) return MH_ERR_ARG;
-  return gemv_impl(x, ldx, Wgu, ldw, act, ldo, nullptr, 0, M, ff, K, dt, 0, ff, nullptr, 0.f, RopeAppend{}, stream);
+  return gemv_impl({x, ldx, Wgu, ldw, nullptr, act, ldo, nullptr, 0, M, ff, K, dt, 0, ff, nullptr, 0.f, RopeAppend{}, stream});
 }
 // The same two projections with the RMSNorm that precedes them (HF LlamaDecoderLayer: input_layernorm -> q|k|v, post_attention_layernorm ->
 // gate|up) applied by the GEMV blocks themselves: y = rmsnorm(x; norm_w, eps) W^T, and (ff > 0) act = silu(.) * (.) of the gate|up rows.
@@ -1723,7 +1693,7 @@ extern "C" int mh_gemv_swiglu(const void* x, int64_t ldx, const void* Wgu, int64
 extern "C" int mh_gemv_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* W, int64_t ldw, void* out, int64_t ldo, int M, int N,
                             int K, int ff, int dt, void* stream) {
   if (!norm_w || M > 8 || ff < 0) return MH_ERR_ARG;
-  return gemv_impl(x, ldx, W, ldw, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream);
+  return gemv_impl({x, ldx, W, ldw, nullptr, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream});
 }
 
 
@@ -2351,86 +2321,25 @@ extern "C" int mh_quant_fp8_b128(const void* w, int64_t ldw, void* q, float* sca
   MH_LAUNCH_CHECK();
 }
 
-static int gemv_fp8w_impl(const void* x, int64_t ldx, const void* q, const float* scales, void* out, int64_t ldo, const void* resid,
-                          int64_t ldr, int M, int N, int K, int dt, int out_f32, int swi_ff, const void* norm_w, float eps, const RopeAppend& ra,
-                          void* stream) {
-  if (!x || !q || !scales || !out || M <= 0 || M > 16 || N <= 0 || K <= 0 || (K & 15) || (ldx & 7)) return MH_ERR_ARG;
-  if (!aligned16(x) || !aligned16(q)) return MH_ERR_ARG;
-  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  if (norm_w && (M > 8 || K > 8192 || !aligned16(norm_w))) return MH_ERR_ARG;
-  if (ra.tab && (swi_ff || (N & 1))) return MH_ERR_ARG;
-  if ((swi_ff || ra.tab) && (resid || out_f32)) return MH_ERR_ARG;
-  if (!norm_w && M >= ((swi_ff || ra.tab) ? g_gemv_mfma_pair_min_fp8 : g_gemv_mfma_min_rows_fp8) && (K % 64) == 0 &&
-      (!ra.tab || ((ra.D >> 1) % 16 == 0 && N == 3 * ra.H * ra.D))) {
-    if (dt == MH_BF16) return launch_gemv_mfma<MH_BF16, true>(x, ldx, q, K, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, ra, as_stream(stream));
-    return launch_gemv_mfma<MH_F16, true>(x, ldx, q, K, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, ra, as_stream(stream));
+static int gemv_fp8w_impl(const GemvArgs& a) {
+  if (const int e = gemv_check<WFp8>(a)) return e;
+  if (gemv_mfma_rows<WFp8>(a) && (a.K % 64) == 0 && (!a.ra.tab || ((a.ra.D >> 1) % 16 == 0 && a.N == 3 * a.ra.H * a.ra.D))) {
+    auto mfma = a.dt == MH_BF16 ? launch_gemv_mfma<MH_BF16, true> : launch_gemv_mfma<MH_F16, true>;  // (weight row stride: K)
+    return mfma(a.x, a.ldx, a.W, a.K, (const float*)a.wsc, a.out, a.ldo, a.resid, a.ldr, a.M, a.N, a.K, a.out_f32, a.swi_ff, a.ra, as_stream(a.stream));
   }
-  if (M > 8 || ((swi_ff || ra.tab) && K > 8192)) return MH_ERR_ARG;
-  if (g_gemv_ksplit && M <= 2 && !swi_ff && !norm_w && !ra.tab && N <= 8192 && K >= 2048) {  // small N, 1-2 rows: K split over the block's waves
-    const dim3 gridk((N + 1) / 2), blockk(256);
-    hipStream_t stk = as_stream(stream);
-    if (dt == MH_BF16) {
-      if (M == 1) hipLaunchKernelGGL((gemv_fp8w_ks_k<MH_BF16, 1, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint8_t*)q, scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-      else hipLaunchKernelGGL((gemv_fp8w_ks_k<MH_BF16, 2, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint8_t*)q, scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-    } else {
-      if (M == 1) hipLaunchKernelGGL((gemv_fp8w_ks_k<MH_F16, 1, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint8_t*)q, scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-      else hipLaunchKernelGGL((gemv_fp8w_ks_k<MH_F16, 2, 2>), gridk, blockk, 0, stk, (const uint16_t*)x, ldx, (const uint8_t*)q, scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32);
-    }
-    MH_LAUNCH_CHECK();
-  }
-  const int rows = (swi_ff || ra.tab) ? 2 : (M < 3 ? 1 : (N >= 8192 ? 2 : 1));  // weight rows per wave (>= ~1000 blocks in flight, as in mh_gemv); SwiGLU: one gate/up pair
-  const int cols = swi_ff ? rows / 2 : rows;
-  const dim3 grid((N + 4 * cols - 1) / (4 * cols)), block(256);
-  hipStream_t st = as_stream(stream);
-#define GO1(DT_, MM_, R_, L_, NRM_, LDS_)                                                                                           \
-  do {                                                                                                                              \
-    const size_t lds_ = (LDS_);                                                                                                     \
-    static bool attr_ = false;                                                                                                      \
-    if (lds_ && !attr_) {                                                                                                           \
-      hipFuncSetAttribute((const void*)gemv_fp8w_k<DT_, MM_, R_, L_, NRM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MM_ * 8192 * 2)); \
-      attr_ = true;                                                                                                                 \
-    }                                                                                                                               \
-    hipLaunchKernelGGL((gemv_fp8w_k<DT_, MM_, R_, L_, NRM_>), grid, block, lds_, st, (const uint16_t*)x, ldx, (const uint8_t*)q, scales, \
-                       out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32, swi_ff, (const uint16_t*)norm_w, eps, ra);            \
-  } while (0)
-#define GO(DT_, MM_, R_, L_)                                                                                                       \
-  do {                                                                                                                              \
-    if (norm_w) GO1(DT_, MM_, R_, true, true, (size_t)MM_ * K * 2);                                                                 \
-    else GO1(DT_, MM_, R_, L_, false, L_ ? (size_t)MM_ * GEMV_KC * 2 : 0);                                                          \
-  } while (0)
-#define GOR(DT_, MM_)                                                                        \
-  do {                                                                                       \
-    if (rows == 2) GO(DT_, MM_, 2, true); else GO(DT_, MM_, 1, true);                       \
-  } while (0)
-#define GOS(DT_, MM_)                                                                        \
-  do {                                                                                       \
-    if (rows == 2) GO(DT_, MM_, 2, false); else GO(DT_, MM_, 1, false);                     \
-  } while (0)
-#define GOM(DT_)                                                                                                   \
-  switch (M) {                                                                                                     \
-    case 1: GOS(DT_, 1); break; case 2: GOS(DT_, 2); break; case 3: GOR(DT_, 3); break;                           \
-    case 4: GOR(DT_, 4); break; case 5: GOR(DT_, 5); break; case 6: GOR(DT_, 6); break;                           \
-    case 7: GOR(DT_, 7); break; default: GOR(DT_, 8); break;                                                       \
-  }
-  if (dt == MH_BF16) { GOM(MH_BF16); } else { GOM(MH_F16); }
-#undef GOM
-#undef GOS
-#undef GOR
-#undef GO
-#undef GO1
-  MH_LAUNCH_CHECK();
+  return gemv_wave_launch<WFp8>(a);
 }
 
 extern "C" int mh_gemv_fp8w(const void* x, int64_t ldx, const void* q, const float* scales, void* out, int64_t ldo, const void* resid,
                             int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream) {
-  return gemv_fp8w_impl(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream);
+  return gemv_fp8w_impl({x, ldx, q, 0, scales, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream});
 }
 // mh_gemv_norm with fp8 (e4m3, per-128-block scales) weights: out = rmsnorm(x; norm_w, eps) W^T (norm_w may be NULL: no norm), ff > 0: SwiGLU of the
 // gate|up rows.  With norm_w: M <= 8, K <= 8192; without: M <= 16.
 extern "C" int mh_gemv_fp8w_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const float* scales, void* out,
                                  int64_t ldo, int M, int N, int K, int ff, int dt, void* stream) {
   if (ff < 0) return MH_ERR_ARG;
-  return gemv_fp8w_impl(x, ldx, q, scales, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream);
+  return gemv_fp8w_impl({x, ldx, q, 0, scales, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream});
 }
 
 // q|k|v projection of the decode step with everything around it in one launch: (optional) input_layernorm of x, the projection with 16-bit
@@ -2443,8 +2352,8 @@ extern "C" int mh_gemv_qkv_rope(const void* x, int64_t ldx, const void* norm_w, 
   RopeAppend ra;
   ra.tab = (const float2*)cos_sin; ra.pos = pos; ra.rpos = rope_pos ? rope_pos : pos; ra.kc = (uint16_t*)kcache; ra.vc = (uint16_t*)vcache; ra.H = H; ra.D = D; ra.Smax = Smax;
   const int N = 3 * H * D;
-  if (W) return gemv_impl(x, ldx, W, ldw, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream);
-  return gemv_fp8w_impl(x, ldx, q8, scales, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream);
+  if (W) return gemv_impl({x, ldx, W, ldw, nullptr, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream});
+  return gemv_fp8w_impl({x, ldx, q8, 0, scales, qkv, ldo, nullptr, 0, M, N, K, dt, 0, 0, norm_w, eps, ra, stream});
 }
 
 // ---- MXFP4 weights (OCP MX: e2m1 values, one power-of-two E8M0 scale per 32 consecutive k), bf16/f16 activations -----------------------
@@ -2470,7 +2379,6 @@ __device__ __forceinline__ uint32_t fp4_code(float v, float inv) {  // |v| inv <
                      (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);  // ties: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4
   return c | ((__float_as_uint(v) >> 28) & 8u);
 }
-__device__ __forceinline__ float e8m0_to_f32(uint32_t byte) { return __uint_as_float(byte << 23); }  // byte in [1, 254]; 0 (a masked block) -> 0.0
 
 // one launch: 4 lanes per 32-element block (16-byte loads, block maximum by two shuffles, one 4-byte store of 8 codes per lane)
 template <int DT>
@@ -2495,166 +2403,7 @@ __global__ __launch_bounds__(256) void quant_fp4_b32_k(const uint16_t* __restric
   if (part == 0) sc[(int64_t)n * nb + kb] = (uint8_t)(e + 127);
 }
 
-// eight e2m1 values (a dword) -> four packed 16-bit pairs, one instruction per pair (gfx950 v_cvt_scalef32_pk_*_fp4 with scale 1: the
-// third operand selects the byte, whose low nibble becomes the low half of the pair - the stored order, so no swap); exact in both types
-template <int DT>
-__device__ __forceinline__ void fp4x8_to_pk16(uint32_t p, uint32_t* w) {
-  if constexpr (DT == MH_BF16) {
-    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 0));
-    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 1));
-    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 2));
-    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(p, 1.0f, 3));
-  } else {
-    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 0));
-    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 1));
-    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 2));
-    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(p, 1.0f, 3));
-  }
-}
 
-// y[m, n] = sum_kb 2^e[n, kb] * sum_{k in block} q[n, k] x[m, k] (+ resid): gemv_fp8w_k with fp4 weights.  One wave per ROWS weight
-// rows; a lane's 16-byte load is 32 values = exactly one scale block, a wave step 2048 values.  The codes become packed 16-bit pairs
-// (exact) and meet the activations in dot2 instructions; the block's fp32 sum is scaled once (16 cvt + 16 x MM dot2 + MM fma per row
-// and load).  K % 32 == 0.  1-2 rows (and NORM): the K loop is not chunked and two steps of every row are requested before the first
-// is consumed; LDSX: chunks of GEMV_KC = one step.  (NORM / swi_ff / ra: the fused RMSNorm, SwiGLU and RoPE + append of gemv_k.)
-template <int DT, int MM, int ROWS, bool LDSX, bool NORM = false>
-__global__ __launch_bounds__(256) void gemv_fp4w_k(const uint16_t* __restrict__ x, int64_t ldx, const uint8_t* __restrict__ q,
-                                                   const uint8_t* __restrict__ sc, void* __restrict__ out, int64_t ldo,
-                                                   const uint16_t* __restrict__ resid, int64_t ldr, int N, int K, int out_f32, int swi_ff,
-                                                   const uint16_t* __restrict__ norm_w, float eps, RopeAppend ra) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t xs4[];  // [MM][GEMV_KC] when LDSX (as in gemv_k), [MM][K] when NORM
-  __shared__ float red[NORM ? MM : 1][4];
-  constexpr bool CHUNK = LDSX && !NORM;
-  constexpr int NSTEP = CHUNK ? 1 : 2;
-  const int xstride = NORM ? K : GEMV_KC;
-  const int lane = threadIdx.x & 63;
-  const int NR = swi_ff > 0 ? ROWS / 2 : ROWS;  // output columns per wave
-  const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
-  const int nb = K >> 5;
-  float acc[ROWS][MM];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) acc[r][m] = 0.f;
-  const uint8_t* qrow[ROWS];
-  const uint8_t* srow[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    int n = swi_ff > 0 ? (r < NR ? min(n0 + r, N - 1) : swi_ff + min(n0 + r - NR, N - 1)) : min(n0 + r, N - 1);
-    if (ROWS == 2 && ra.tab) {  // rotary pair (as in gemv_k)
-      const int half = ra.D >> 1, pidx = min(n0 >> 1, (N >> 1) - 1), per_sec = ra.H * half;
-      const int sec = pidx / per_sec, rem = pidx - sec * per_sec, h = rem / half;
-      n = sec * ra.H * ra.D + h * ra.D + (rem - h * half) + r * half;
-    }
-    qrow[r] = q + (int64_t)n * (K >> 1);
-    srow[r] = sc + (int64_t)n * nb;
-  }
-  for (int kc = 0; kc < K; kc += GEMV_KC) {
-    const int klen = CHUNK ? min(GEMV_KC, K - kc) : K;
-    if constexpr (NORM) {
-      stage_rmsnorm<DT, MM>(x, ldx, norm_w, eps, K, xs4, red);
-    } else if constexpr (LDSX) {
-      if (kc) __syncthreads();
-      for (int i = threadIdx.x * 8; i < MM * klen; i += 256 * 8) {
-        const int m = i / klen, k = i - m * klen;
-        *(uint4*)(xs4 + m * GEMV_KC + k) = *(const uint4*)(x + (int64_t)m * ldx + kc + k);
-      }
-      __syncthreads();
-    }
-    if (n0 < N) {
-      for (int k0 = lane * 32; k0 < klen; k0 += 2048 * NSTEP) {
-        uint4 qv[NSTEP][ROWS];
-        uint32_t sb[NSTEP][ROWS];
-#pragma unroll
-        for (int u = 0; u < NSTEP; ++u)
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) {
-            const int kk = k0 + u * 2048;
-            const bool ok = kk < klen;
-            qv[u][r] = ok ? ld_stream16(qrow[r] + ((kc + kk) >> 1)) : make_uint4(0, 0, 0, 0);
-            sb[u][r] = ok ? srow[r][(kc + kk) >> 5] : 0u;
-          }
-#pragma unroll
-        for (int u = 0; u < NSTEP; ++u) {
-          const int kk = k0 + u * 2048;
-          if (kk < klen) {
-            float p[ROWS][MM];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-              for (int m = 0; m < MM; ++m) p[r][m] = 0.f;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {  // 8 values at a time
-              uint32_t w[ROWS][4];
-#pragma unroll
-              for (int r = 0; r < ROWS; ++r) fp4x8_to_pk16<DT>(d == 0 ? qv[u][r].x : d == 1 ? qv[u][r].y : d == 2 ? qv[u][r].z : qv[u][r].w, w[r]);
-#pragma unroll
-              for (int m = 0; m < MM; ++m) {
-                uint4 xa;
-                if constexpr (LDSX || NORM) xa = *(const uint4*)(xs4 + m * xstride + kk + 8 * d);
-                else xa = *(const uint4*)(x + (int64_t)m * ldx + kc + kk + 8 * d);
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                  float a = p[r][m];
-                  a = dot2_acc<DT>(w[r][0], xa.x, a);
-                  a = dot2_acc<DT>(w[r][1], xa.y, a);
-                  a = dot2_acc<DT>(w[r][2], xa.z, a);
-                  a = dot2_acc<DT>(w[r][3], xa.w, a);
-                  p[r][m] = a;
-                }
-              }
-            }
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-              const float s = e8m0_to_f32(sb[u][r]);
-#pragma unroll
-              for (int m = 0; m < MM; ++m) acc[r][m] = fmaf(s, p[r][m], acc[r][m]);
-            }
-          }
-        }
-      }
-    }
-    if constexpr (!CHUNK) break;
-  }
-  if (n0 >= N) return;
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int m = 0; m < MM; ++m) acc[r][m] = wave_sum(acc[r][m]);
-  if constexpr (ROWS == 2) {
-    if (ra.tab) {
-      if (lane == 0) rope_append_store<DT, MM>(ra, n0 >> 1, acc[0], acc[1], (uint16_t*)out, ldo);
-      return;
-    }
-  }
-  if (lane == 0 && swi_ff > 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS / 2; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        const float g_ = ld16<DT>((uint16_t)st16<DT>(acc[r][m])), u_ = ld16<DT>((uint16_t)st16<DT>(acc[r + ROWS / 2][m]));
-        ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(swiglu_fwd1(g_, u_));
-      }
-    }
-    return;
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= N) break;
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        float v = acc[r][m];
-        if (resid) v += ld16<DT>(resid[(int64_t)m * ldr + n]);
-        if (out_f32) ((float*)out)[(int64_t)m * ldo + n] = v;
-        else ((uint16_t*)out)[(int64_t)m * ldo + n] = (uint16_t)st16<DT>(v);
-      }
-    }
-  }
-}
 
 // 3..16 activation rows: gemv_mfma_k with fp4 weights.  A block owns 16 x RG weight rows, its 8 waves split K in steps of 128.  Lane
 // l = (row j = l & 15, kq = l >> 4) loads 16 B = ONE WHOLE scale block (block kq of the step) of its row, but an MFMA's four k-chunks
@@ -2811,79 +2560,26 @@ extern "C" int mh_quant_fp4_b32(const void* w, int64_t ldw, void* q, void* scale
   MH_LAUNCH_CHECK();
 }
 
-// Row thresholds of the MFMA form (g_gemv_mfma_min_rows_fp4 / g_gemv_mfma_pair_min_fp4): 3 rows for a plain projection and 4 for the
-// SwiGLU pair, the fp8 path's values.  Measured at Llama-7B size (profiles/decode_fp4_bench.txt, graph replay, context 613): with these
-// thresholds the fp4 step is 1.78 ms at 1 row (fp8 1.97), 3.01 ms at 5 rows (fp8 3.57) and 3.53 ms at 8 rows (fp8 3.79); the same
-// file holds the 3- and 5-row steps with the MFMA form switched off (mh_gemv_mfma_min_rows(17)).  The weights stream at ~2 TB/s at one
-// row, well below the 16-bit path's 4.7: per byte the wave form issues twice the fp8 form's converts and dot2s, and a 2 KB row is two
-// loads per lane - the step is faster than fp8 but not yet at the byte ratio.
-static int gemv_fp4w_impl(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid,
-                          int64_t ldr, int M, int N, int K, int dt, int out_f32, int swi_ff, const void* norm_w, float eps, const RopeAppend& ra,
-                          void* stream) {
-  if (!x || !q || !scales || !out || M <= 0 || M > 16 || N <= 0 || K <= 0 || (K & 31) || (ldx & 7)) return MH_ERR_ARG;
-  if (!aligned16(x) || !aligned16(q)) return MH_ERR_ARG;
-  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  if (norm_w && (M > 8 || K > 8192 || !aligned16(norm_w))) return MH_ERR_ARG;
-  if (ra.tab && (swi_ff || (N & 1) || M > 8)) return MH_ERR_ARG;
-  if ((swi_ff || ra.tab) && (resid || out_f32)) return MH_ERR_ARG;
-  if (!norm_w && !ra.tab && M >= (swi_ff ? g_gemv_mfma_pair_min_fp4 : g_gemv_mfma_min_rows_fp4) && (K % 64) == 0) {
-    if (dt == MH_BF16) return launch_gemv_fp4w_mfma<MH_BF16>(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, as_stream(stream));
-    return launch_gemv_fp4w_mfma<MH_F16>(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, out_f32, swi_ff, as_stream(stream));
+// (no MFMA form of the RoPE + append projection: it stays on the wave form, so M <= 8)
+static int gemv_fp4w_impl(const GemvArgs& a) {
+  if (const int e = gemv_check<WFp4>(a)) return e;
+  if (!a.ra.tab && gemv_mfma_rows<WFp4>(a) && (a.K % 64) == 0) {
+    auto mfma = a.dt == MH_BF16 ? launch_gemv_fp4w_mfma<MH_BF16> : launch_gemv_fp4w_mfma<MH_F16>;
+    return mfma(a.x, a.ldx, a.W, a.wsc, a.out, a.ldo, a.resid, a.ldr, a.M, a.N, a.K, a.out_f32, a.swi_ff, as_stream(a.stream));
   }
-  if (M > 8 || ((swi_ff || ra.tab) && K > 8192)) return MH_ERR_ARG;
-  const int rows = (swi_ff || ra.tab) ? 2 : (M < 3 ? 1 : (N >= 8192 ? 2 : 1));  // weight rows per wave, as in gemv_fp8w_impl; SwiGLU / RoPE: one pair
-  const int cols = swi_ff ? rows / 2 : rows;
-  const dim3 grid((N + 4 * cols - 1) / (4 * cols)), block(256);
-  hipStream_t st = as_stream(stream);
-#define GO1(DT_, MM_, R_, L_, NRM_, LDS_)                                                                                           \
-  do {                                                                                                                              \
-    const size_t lds_ = (LDS_);                                                                                                     \
-    static bool attr_ = false;                                                                                                      \
-    if (lds_ && !attr_) {                                                                                                           \
-      hipFuncSetAttribute((const void*)gemv_fp4w_k<DT_, MM_, R_, L_, NRM_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MM_ * 8192 * 2)); \
-      attr_ = true;                                                                                                                 \
-    }                                                                                                                               \
-    hipLaunchKernelGGL((gemv_fp4w_k<DT_, MM_, R_, L_, NRM_>), grid, block, lds_, st, (const uint16_t*)x, ldx, (const uint8_t*)q,     \
-                       (const uint8_t*)scales, out, ldo, (const uint16_t*)resid, ldr, N, K, out_f32, swi_ff, (const uint16_t*)norm_w, eps, ra); \
-  } while (0)
-#define GO(DT_, MM_, R_, L_)                                                                                                       \
-  do {                                                                                                                              \
-    if (norm_w) GO1(DT_, MM_, R_, true, true, (size_t)MM_ * K * 2);                                                                 \
-    else GO1(DT_, MM_, R_, L_, false, L_ ? (size_t)MM_ * GEMV_KC * 2 : 0);                                                          \
-  } while (0)
-#define GOR(DT_, MM_)                                                                        \
-  do {                                                                                       \
-    if (rows == 2) GO(DT_, MM_, 2, true); else GO(DT_, MM_, 1, true);                       \
-  } while (0)
-#define GOS(DT_, MM_)                                                                        \
-  do {                                                                                       \
-    if (rows == 2) GO(DT_, MM_, 2, false); else GO(DT_, MM_, 1, false);                     \
-  } while (0)
-#define GOM(DT_)                                                                                                   \
-  switch (M) {                                                                                                     \
-    case 1: GOS(DT_, 1); break; case 2: GOS(DT_, 2); break; case 3: GOR(DT_, 3); break;                           \
-    case 4: GOR(DT_, 4); break; case 5: GOR(DT_, 5); break; case 6: GOR(DT_, 6); break;                           \
-    case 7: GOR(DT_, 7); break; default: GOR(DT_, 8); break;                                                       \
-  }
-  if (dt == MH_BF16) { GOM(MH_BF16); } else { GOM(MH_F16); }
-#undef GOM
-#undef GOS
-#undef GOR
-#undef GO
-#undef GO1
-  MH_LAUNCH_CHECK();
+  return gemv_wave_launch<WFp4>(a);
 }
 
 extern "C" int mh_gemv_fp4w(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid,
                             int64_t ldr, int M, int N, int K, int dt, int out_f32, void* stream) {
-  return gemv_fp4w_impl(x, ldx, q, scales, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream);
+  return gemv_fp4w_impl({x, ldx, q, 0, scales, out, ldo, resid, ldr, M, N, K, dt, out_f32, 0, nullptr, 0.f, RopeAppend{}, stream});
 }
 // mh_gemv_fp8w_norm with fp4 weights: out = rmsnorm(x; norm_w, eps) W^T (norm_w may be NULL: no norm), ff > 0: SwiGLU of the gate|up rows.
 // With norm_w: M <= 8, K <= 8192; without: M <= 16.
 extern "C" int mh_gemv_fp4w_norm(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* out,
                                  int64_t ldo, int M, int N, int K, int ff, int dt, void* stream) {
   if (ff < 0) return MH_ERR_ARG;
-  return gemv_fp4w_impl(x, ldx, q, scales, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream);
+  return gemv_fp4w_impl({x, ldx, q, 0, scales, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream});
 }
 // mh_gemv_qkv_rope with fp4 weights (= mh_rmsnorm_fwd + mh_gemv_fp4w + mh_decode_rope_append, bit for bit): one wave per rotary pair, M <= 8.
 extern "C" int mh_gemv_fp4w_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* qkv,
@@ -2892,5 +2588,5 @@ extern "C" int mh_gemv_fp4w_qkv_rope(const void* x, int64_t ldx, const void* nor
   if (!cos_sin || !pos || !kcache || !vcache || H <= 0 || D <= 0 || (D & 1) || Smax <= 0 || M > 8) return MH_ERR_ARG;
   RopeAppend ra;
   ra.tab = (const float2*)cos_sin; ra.pos = pos; ra.rpos = rope_pos ? rope_pos : pos; ra.kc = (uint16_t*)kcache; ra.vc = (uint16_t*)vcache; ra.H = H; ra.D = D; ra.Smax = Smax;
-  return gemv_fp4w_impl(x, ldx, q, scales, qkv, ldo, nullptr, 0, M, 3 * H * D, K, dt, 0, 0, norm_w, eps, ra, stream);
+  return gemv_fp4w_impl({x, ldx, q, 0, scales, qkv, ldo, nullptr, 0, M, 3 * H * D, K, dt, 0, 0, norm_w, eps, ra, stream});
 }

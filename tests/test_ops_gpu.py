@@ -641,7 +641,9 @@ def test_gemm_256_tile_kernel(ops, dtype, M, N, K, which):
 # ---- KV-cache decode kernels ---------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(1, 4096, 4096), (8, 12288, 4096), (3, 515, 264), (5, 32003, 256), (11, 1024, 11008), (16, 4096, 4096), (4, 22016, 4096),
-                                   (13, 515, 11008), (20, 1000, 2080)])
+                                   (13, 515, 11008), (20, 1000, 2080),
+                                   (1, 515, 2064),   # split-K form: ragged last wave range (520 k per wave, the fourth gets 504), odd N
+                                   (2, 8200, 264)])  # 1-2 rows without LDS staging: N above the split-K limit, K no multiple of 512, ragged last block
 def test_gemv_small_m(ops, dtype, M, N, K):
     """Both GEMV forms (one wave per weight row; MFMA with the weights streamed into the B-operand registers, 3..16 rows) at every M."""
     x, w = rnd(M, K, dtype=dtype), rnd(N, K, dtype=dtype, seed=1, scale=0.5)
