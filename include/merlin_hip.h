@@ -633,6 +633,23 @@ int mh_adamw(void* p, const void* g, float* m, float* v, int64_t n, float lr, fl
 int mh_adamw_clip(void* p, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                   float wd, int step, float gscale, const float* gscale_dev, int dt, void* stream);
 int mh_clip_scale(const float* sumsq, float gscale, float max_norm, float* out2, void* stream);
+/* The same update (gscale * *gscale_dev when gscale_dev is not NULL) with a store of p that keeps what round-to-nearest drops: at lr 5e-5 a
+ * bf16 weight of magnitude >= 2^-6 has a half-spacing above a full Adam step and never moves under mh_adamw.  dt must be MH_BF16
+ * (MH_ERR_DTYPE otherwise: the top 16 bits of an fp32 are a bf16, not an fp16); a null pointer (gscale_dev excepted), n <= 0 or step <= 0
+ * is MH_ERR_ARG.  16-byte accesses when every pointer is 16-byte aligned, element by element otherwise.
+ * mh_adamw_split: lo [n] int16, the low half of an fp32 MASTER whose bits are u = ((uint32)p << 16) + (int32)lo (mod 2^32); lo = 0 means
+ *   master = p.  The update runs on that fp32 value; its new bits u' go back as hi = (u' + 0x8000) >> 16 (the new p: round to nearest, ties
+ *   away from zero) and lo = (int16)(u' - (hi << 16)), in [-32768, 32767].  Exact fp32-master AdamW at 2 bytes per parameter; lo is only
+ *   valid beside the p it was written with.
+ * mh_adamw_sr: stochastic rounding, no extra state.  The element at index j = index0 + i takes the 16-bit field
+ *   r = (z >> 16 (j & 3)) & 0xffff of z = splitmix64(key + (j >> 2)) (mh_fill_normal's hash; one hash serves four elements) and stores
+ *   (u' + r) >> 16, u' the fp32 bits of the new value; a value whose exponent field is 255 is stored truncated.  Exactly 16 bits are dropped,
+ *   so P(round up) is exactly the dropped fraction: unbiased.  index0 >= 0 is the element's position in the caller's whole buffer, which
+ *   makes the result independent of how that buffer is cut into launches. */
+int mh_adamw_split(void* p, void* lo, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                   float wd, int step, float gscale, const float* gscale_dev, int dt, void* stream);
+int mh_adamw_sr(void* p, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                float wd, int step, float gscale, const float* gscale_dev, uint64_t key, int64_t index0, int dt, void* stream);
 /* out[0] += sum(g^2) over n elements (fp32 atomic; zero it first) */
 int mh_sumsq(const void* g, int64_t n, float* out, int dt, void* stream);
 /* Deterministic form (fixed grid, fixed-order two-stage sum; 16-byte loads): out[0] = sum g^2; `partial` = 2048 floats

@@ -253,6 +253,116 @@ __global__ __launch_bounds__(256) void adamw_k(uint16_t* __restrict__ p, const u
   }
 }
 
+// ---- AdamW over a STORE POLICY (bf16 only): the arithmetic of adamw_k on an fp32 value of p, and a policy that says how that value is
+// rebuilt from memory and how the new one goes back.  (adamw_k itself, the round-to-nearest-even store, stays as it is above.)
+//   StoreSplit: an int16 low half `lo` beside every parameter, master bits u = (p << 16) + (int32)lo.  Stored back as
+//               hi = (u' + 0x8000) >> 16, lo = u' - (hi << 16): round to nearest, ties away from zero, lo in [-32768, 32767].  Exact
+//               fp32-master AdamW at 2 extra bytes per parameter.
+//   StoreSr:    no extra state.  Arena element j adds the 16-bit field (j & 3) of splitmix64(key + (j >> 2)) below the kept bits and
+//               truncates: P(round up) is exactly the dropped fraction.  Exponent field 255 (inf / nan) is truncated.
+struct StoreSplit {
+  static constexpr bool HAS_LO = true;
+  uint16_t* lo;
+  __device__ __forceinline__ float load(uint32_t p, uint32_t l) const { return __uint_as_float((p << 16) + (uint32_t)(int32_t)(int16_t)l); }
+  __device__ __forceinline__ uint32_t store(float x, uint32_t, uint32_t& l) const {
+    const uint32_t u = __float_as_uint(x), hi = (u + 0x8000u) >> 16;
+    l = (u - (hi << 16)) & 0xffffu;
+    return hi;
+  }
+  // the 16-bit random fields of 8 consecutive elements from arena index j0 (unused here)
+  __device__ __forceinline__ void fields8(int64_t, uint32_t*) const {}
+  __device__ __forceinline__ uint32_t field(int64_t) const { return 0; }
+};
+struct StoreSr {
+  static constexpr bool HAS_LO = false;
+  uint64_t key;
+  int64_t index0;
+  __device__ __forceinline__ float load(uint32_t p, uint32_t) const { return __uint_as_float(p << 16); }
+  __device__ __forceinline__ uint32_t store(float x, uint32_t r, uint32_t&) const {
+    const uint32_t u = __float_as_uint(x);
+    return ((u & 0x7f800000u) == 0x7f800000u ? u : u + r) >> 16;
+  }
+  __device__ __forceinline__ uint32_t field(int64_t i) const {
+    const uint64_t j = (uint64_t)(index0 + i);
+    return (uint32_t)(splitmix64(key + (j >> 2)) >> (16 * (j & 3))) & 0xffffu;
+  }
+  __device__ __forceinline__ void fields8(int64_t i0, uint32_t* r) const {  // one hash serves four elements: two or three per 8
+    const uint64_t j0 = (uint64_t)(index0 + i0);
+    const int a = (int)(j0 & 3);
+    const uint64_t z0 = splitmix64(key + (j0 >> 2)), z1 = splitmix64(key + (j0 >> 2) + 1);
+    const uint64_t z2 = a ? splitmix64(key + (j0 >> 2) + 2) : 0;  // (wave-uniform: i0 is a multiple of 8)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int q = (a + k) >> 2;
+      const uint64_t z = q == 0 ? z0 : q == 1 ? z1 : z2;
+      r[k] = (uint32_t)(z >> (16 * ((a + k) & 3))) & 0xffffu;
+    }
+  }
+};
+
+// One element's update, every operation rounded on its own: the 16-byte loop and the element-by-element loop must give the same bits (a run cut
+// into two launches equals one launch), so nothing here is left to be contracted one way in one loop and another way in the other.  These
+// are the roundings adamw_k compiles to (separate products and sums; only 1 - lr * wd, `decay`, is a single fma).  m, v: in and out.
+__device__ __forceinline__ float adamw_value(float pi, float gi, float& m, float& v, float lr, float b1, float b2, float eps, float decay,
+                                             float bc1, float bc2) {
+#pragma clang fp contract(off)
+  const float mi = b1 * m + (1.f - b1) * gi;
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  pi = pi * decay;
+  pi -= lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
+  return pi;
+}
+
+// nvec: number of 8-element groups taken with 16-byte accesses (0 when a pointer is not 16-byte aligned); [8 nvec, n) goes element by element
+template <class Store>
+__global__ __launch_bounds__(256) void adamw_store_k(uint16_t* __restrict__ p, const uint16_t* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, int64_t n, int64_t nvec, float lr, float b1, float b2, float eps,
+                                                     float wd, float bc1, float bc2, float gscale, const float* __restrict__ gscale_dev,
+                                                     Store st) {
+  if (gscale_dev) gscale *= *gscale_dev;
+  const float decay = fmaf(-lr, wd, 1.f);
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = tid; i < nvec; i += stride) {
+    const uint4 pw = ((const uint4*)p)[i], gw = ((const uint4*)g)[i];
+    uint4 lw = make_uint4(0, 0, 0, 0);
+    if constexpr (Store::HAS_LO) lw = ((const uint4*)st.lo)[i];
+    const float4 m0 = ((const float4*)m)[2 * i], m1 = ((const float4*)m)[2 * i + 1];
+    const float4 v0 = ((const float4*)v)[2 * i], v1 = ((const float4*)v)[2 * i + 1];
+    const uint32_t pb[4] = {pw.x, pw.y, pw.z, pw.w}, lb[4] = {lw.x, lw.y, lw.z, lw.w};
+    float gf[8], mf[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w}, vf[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    unpack8<MH_BF16>(gw, gf);
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph[8], pl[8];
+    st.fields8(i << 3, r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int sh = 16 * (k & 1);
+      const float pi = adamw_value(st.load((pb[k >> 1] >> sh) & 0xffffu, (lb[k >> 1] >> sh) & 0xffffu), gf[k] * gscale, mf[k], vf[k], lr, b1, b2,
+                                   eps, decay, bc1, bc2);
+      pl[k] = 0;
+      ph[k] = st.store(pi, r[k], pl[k]) & 0xffffu;
+    }
+    ((float4*)m)[2 * i] = make_float4(mf[0], mf[1], mf[2], mf[3]);
+    ((float4*)m)[2 * i + 1] = make_float4(mf[4], mf[5], mf[6], mf[7]);
+    ((float4*)v)[2 * i] = make_float4(vf[0], vf[1], vf[2], vf[3]);
+    ((float4*)v)[2 * i + 1] = make_float4(vf[4], vf[5], vf[6], vf[7]);
+    ((uint4*)p)[i] = make_uint4(ph[0] | (ph[1] << 16), ph[2] | (ph[3] << 16), ph[4] | (ph[5] << 16), ph[6] | (ph[7] << 16));
+    if constexpr (Store::HAS_LO)
+      ((uint4*)st.lo)[i] = make_uint4(pl[0] | (pl[1] << 16), pl[2] | (pl[3] << 16), pl[4] | (pl[5] << 16), pl[6] | (pl[7] << 16));
+  }
+  for (int64_t i = (nvec << 3) + tid; i < n; i += stride) {
+    uint32_t l = 0;
+    if constexpr (Store::HAS_LO) l = st.lo[i];
+    float mi = m[i], vi = v[i];
+    const float pi = adamw_value(st.load(p[i], l), ld16<MH_BF16>(g[i]) * gscale, mi, vi, lr, b1, b2, eps, decay, bc1, bc2);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = (uint16_t)st.store(pi, st.field(i), l);
+    if constexpr (Store::HAS_LO) st.lo[i] = (uint16_t)l;
+  }
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void sumsq_k(const uint16_t* __restrict__ g, int64_t n, float* __restrict__ out) {
   float s = 0.f;
@@ -392,6 +502,31 @@ extern "C" int mh_adamw_clip(void* p, const void* g, float* m, float* v, int64_t
   if (!p || !g || !m || !v || n <= 0 || step <= 0) return MH_ERR_ARG;
   const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
   DISPATCH16(dt, adamw_k, grid_for(n), (uint16_t*)p, (const uint16_t*)g, m, v, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev);
+  MH_LAUNCH_CHECK();
+}
+// 16-byte accesses need every pointer 16-byte aligned (arena runs are: 128-element offsets); any other slice goes element by element
+template <class Store>
+static void adamw_store_go(void* p, const void* g, float* m, float* v, int64_t n, bool vec, float lr, float beta1, float beta2, float eps,
+                           float wd, int step, float gscale, const float* gscale_dev, Store st, void* stream) {
+  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  const int64_t nvec = vec ? n >> 3 : 0;
+  hipLaunchKernelGGL(adamw_store_k<Store>, dim3(grid_for(nvec ? nvec : n)), dim3(256), 0, as_stream(stream), (uint16_t*)p, (const uint16_t*)g,
+                     m, v, n, nvec, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gscale_dev, st);
+}
+extern "C" int mh_adamw_split(void* p, void* lo, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                              float wd, int step, float gscale, const float* gscale_dev, int dt, void* stream) {
+  if (!p || !lo || !g || !m || !v || n <= 0 || step <= 0) return MH_ERR_ARG;
+  if (dt != MH_BF16) return MH_ERR_DTYPE;  // the top 16 bits of an fp32 are a bf16, not an fp16
+  const bool vec = aligned16(p) && aligned16(lo) && aligned16(g) && aligned16(m) && aligned16(v);
+  adamw_store_go(p, g, m, v, n, vec, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, StoreSplit{(uint16_t*)lo}, stream);
+  MH_LAUNCH_CHECK();
+}
+extern "C" int mh_adamw_sr(void* p, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float wd, int step, float gscale, const float* gscale_dev, uint64_t key, int64_t index0, int dt, void* stream) {
+  if (!p || !g || !m || !v || n <= 0 || step <= 0 || index0 < 0) return MH_ERR_ARG;
+  if (dt != MH_BF16) return MH_ERR_DTYPE;
+  const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
+  adamw_store_go(p, g, m, v, n, vec, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, StoreSr{key, index0}, stream);
   MH_LAUNCH_CHECK();
 }
 namespace {

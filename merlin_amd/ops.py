@@ -1450,6 +1450,16 @@ def adamw_clip_(param, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale, gsca
     L.call("mh_adamw_clip", param, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, dt_of(param), _stream())
 
 
+def adamw_split_(param, lo, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0, gscale_dev=None):
+    """AdamW on the fp32 master (param << 16) + lo (lo: int16, same length); param and lo are both rewritten (include/merlin_hip.h)."""
+    L.call("mh_adamw_split", param, lo, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, dt_of(param), _stream())
+
+
+def adamw_sr_(param, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0, gscale_dev=None, key=0, index0=0):
+    """AdamW with a stochastically rounded store of param: element i draws from splitmix64(key + ((index0 + i) >> 2))."""
+    L.call("mh_adamw_sr", param, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, key, index0, dt_of(param), _stream())
+
+
 def clip_scale(sumsq_t, gscale, max_norm, out2):
     L.call("mh_clip_scale", sumsq_t, gscale, max_norm, out2, _stream())
 

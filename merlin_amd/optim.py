@@ -2,7 +2,26 @@
 mmgpt/engine/train/trainer.py:45-74: decoupled weight decay, no decay on biases / norm weights).
 
 One `mh_adamw` launch per run of adjacent parameters sharing (lr scale, weight decay): a handful of launches
-per layer instead of one per tensor.  fp32 moments live in two flat buffers shaped like the arena."""
+per layer instead of one per tensor.  fp32 moments live in two flat buffers shaped like the arena.
+
+How the new value of a parameter goes back into the bf16 arena is `FusedAdamW(rounding=...)`:
+
+  "nearest"     (default) round to nearest even, as torch AdamW on bf16 parameters does (the reference: builder.py:163).  An update below
+                half a bf16 spacing is rounded away.  Emulated on the CPU (tests/test_adamw_rounding_cpu.py): a tensor of ones stepped 400
+                times by 5e-5 (pretrain.sh's peak lr, a full-lr Adam step) is still exactly 1.0 (half a spacing below 1.0 is 1.95e-3); of
+                weights drawn at sigma 0.02, 43 % are bit-identical after one such step (every |w| >= 2^-6 has a half-spacing of
+                6.1e-5 > lr), and 92 % at the first ViT layers' lr under LLRD (0.9^22: 4.9e-6), where the cosine schedule takes every layer
+                in the end.
+  "split"       an int16 low half per parameter (`self.lo`, +2 bytes per parameter: 14.1 GB for the 7B arena, 26 B moved per parameter
+                instead of 22; a full fp32 copy would be +28 GB): (p, lo) together are an fp32 master, the update is exact fp32-master
+                AdamW, and p is that master rounded to nearest.  bf16 only.  `lo` is only valid beside the p it was written with: when the
+                weights changed behind the optimizer (a load, a stock torch step, a repack) the next step() restarts from master := p and
+                counts it in `self.reseeds`.
+  "stochastic"  no extra state: the store rounds up with a probability equal to the dropped fraction (unbiased), drawn from a hash of
+                (seed, step, arena index), so every data-parallel rank computes the same bits from the same gradients.  bf16 only.
+
+Not covered: optimizer-state save and restore (FusedAdamW has none for m and v either).  Resuming with lo = 0 restarts from the stored bf16
+weights."""
 from __future__ import annotations
 
 import math
@@ -11,6 +30,9 @@ import re
 import torch
 
 from . import ops as O
+from .weights import MASK64, splitmix64_scalar
+
+ROUNDINGS = ("nearest", "split", "stochastic")
 
 
 # ---- layer-wise learning-rate decay (mmgpt/utils/llrd_utils.py:4-23), selected by --llrd / --llm_llrd (trainer.py:56-61) ----
@@ -56,8 +78,16 @@ def cosine_with_warmup(step: int, total_steps: int, warmup_ratio: float = 0.0, n
 
 
 class FusedAdamW:
-    def __init__(self, engine, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lr_scale_fn=None):
+    def __init__(self, engine, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lr_scale_fn=None, rounding="nearest", seed=0):
+        """rounding: how p is stored ("nearest", "split", "stochastic": see the module docstring); seed: of the stochastic store.  No state is
+        saved or restored: resuming a "split" run starts from the stored bf16 weights (lo = 0)."""
+        if rounding not in ROUNDINGS:
+            raise ValueError(f"rounding={rounding!r} is not one of {ROUNDINGS}")
         self.engine = engine
+        self.rounding, self.seed = rounding, int(seed)
+        self.lo = None        # "split": int16 low halves of the fp32 masters, shaped like the arena
+        self.reseeds = 0      # "split": how often lo was dropped because the weights changed behind the optimizer
+        self._lo_for = None   # (engine.weight_version, address of the arena's flat) that lo belongs to
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.lr_scale_fn = lr_scale_fn  # name -> multiplier (layer-wise lr decay, llrd_utils.py:4-79)
         self.step_count = 0
@@ -99,9 +129,14 @@ class FusedAdamW:
         global gradient norm like HF Trainer (--max_grad_norm, default 1.0) with the coefficient computed and applied
         on the device; lr_mult is the scheduler's multiplier for this step (cosine_with_warmup)."""
         A = self._build()
+        if self.rounding != "nearest" and A.flat.dtype != torch.bfloat16:
+            raise ValueError(f"rounding={self.rounding!r} needs bfloat16 parameters, got {A.flat.dtype}: the top half of an fp32 is a bf16")
         if A.gflat is None:
             return
         self.step_count += 1
+        if self.rounding == "split":
+            self._ensure_lo(A)
+        key = self.sr_key(self.step_count) if self.rounding == "stochastic" else None
         b1, b2 = self.betas
         clip = None
         if max_grad_norm is not None and max_grad_norm > 0:
@@ -112,11 +147,45 @@ class FusedAdamW:
         for off, num, sc, wd in self._runs:
             args = (A.flat[off: off + num], A.gflat[off: off + num], self.m[off: off + num], self.v[off: off + num],
                     self.lr * sc * lr_mult, b1, b2, self.eps, wd, self.step_count, grad_scale)
-            if clip is None:
+            if self.rounding == "split":
+                O.adamw_split_(args[0], self.lo[off: off + num], *args[1:], clip)
+            elif self.rounding == "stochastic":
+                O.adamw_sr_(*args, clip, key, off)
+            elif clip is None:
                 O.adamw_(*args)
             else:
                 O.adamw_clip_(*args, clip)
         self.engine.weights_changed()  # derived copies (fp8 weights, padded patch-embedding weight) are stale now
+        if self.rounding == "split":
+            self._lo_for = self._weights_id(A)
+
+    def sr_key(self, step: int) -> int:
+        """The stochastic store's hash key of one step."""
+        return splitmix64_scalar((self.seed & MASK64) ^ ((step * 0xD1342543DE82EF95) & MASK64))
+
+    def _weights_id(self, A):
+        return (self.engine.weight_version, A.flat.data_ptr())
+
+    def _ensure_lo(self, A):
+        """lo belongs to the weights this optimizer last wrote: anything else (a load, a stock torch step, a repack) restarts master := p.
+        A needless restart costs at most half a bf16 spacing, once."""
+        if self.lo is None or self.lo.numel() != A.total or self.lo.device != A.flat.device:
+            self.lo = torch.zeros(A.total, dtype=torch.int16, device=A.flat.device)
+        elif self._lo_for != self._weights_id(A):
+            self.lo.zero_()
+            self.reseeds += 1
+
+    def master(self, name):
+        """fp32 master of a parameter under rounding="split", rebuilt from (p, lo): for tests and checkpoint tooling, not the hot path."""
+        if self.rounding != "split":
+            raise ValueError(f"master() needs rounding='split', not {self.rounding!r}")
+        A = self.engine.ensure_arena()
+        p = A.params[name]
+        off = A.offset[name]
+        hi = A.flat[off: off + p.numel()].view(torch.int16).to(torch.int32) << 16
+        if self.lo is not None and self._lo_for == self._weights_id(A):  # (a stale lo is not used: master = p)
+            hi = hi + self.lo[off: off + p.numel()].to(torch.int32)
+        return hi.view(torch.float32).view(p.shape)
 
     def last_grad_norm(self):
         """Total gradient norm seen by the last clipped step (device scalar; what HF logs as grad_norm)."""
