@@ -358,6 +358,15 @@ int mh_gemv_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, 
 int mh_gemv_fp4w_qkv_rope(const void* x, int64_t ldx, const void* norm_w, float eps, const void* q, const void* scales, void* qkv,
                           int64_t ldo, int M, int K, int dt, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos,
                           void* kcache, void* vcache, int H, int D, int Smax, void* stream);
+/* The many-row product on MXFP4 weights (prefill, full-sequence forward; csrc/gemm_fp4w.hip): out[m, n] = sum_kb 2^e[n, kb]
+ * sum_{k in block kb} code[n, k] x[m, k], x [M, K] `dt`, (q, scales) exactly the pair mh_quant_fp4_b32 writes (the byte layout above is the
+ * contract: nothing is repacked).  M >= 1, any N >= 1, K % 32 == 0; x rows 16-byte aligned (ldx % 8 == 0).  Four store forms: out `dt`;
+ * out `dt` + resid `dt`; out fp32 (out_f32); out fp32 += product (out_f32 and accum: the read-modify-write of an fp32 residual stream).
+ * Every other combination is MH_ERR_ARG, as are K % 32 != 0 and null pointers (no launch).  The codes are widened to 16 bits WITH their block
+ * scale (v_cvt_scalef32_pk_*_fp4) and summed in fp32 by the MFMA: code 2^e is exact in bf16 for every scale byte >= 2, in f16 for scale bytes
+ * 104 .. 140 (0.5 2^e >= 2^-24 and 6 2^e <= 65504); outside that window the f16 product uses the weight as that instruction rounds it to f16. */
+int mh_gemm_fp4w(const void* x, int64_t ldx, const void* q, const void* scales, void* out, int64_t ldo, const void* resid, int64_t ldr,
+                 int M, int N, int K, int dt, int out_f32, int accum, void* stream);
 /* qkv [B, 3, H, D] of the new tokens: rotate q and k in place at position rope_pos[b] (int32, device; NULL = pos), copy k and v into
  * kcache / vcache [B, Smax, H*D] at row pos[b]. */
 int mh_decode_rope_append(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kcache, void* vcache, int B,

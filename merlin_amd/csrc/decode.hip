@@ -2357,8 +2357,8 @@ extern "C" int mh_gemv_qkv_rope(const void* x, int64_t ldx, const void* norm_w, 
 }
 
 // ---- MXFP4 weights (OCP MX: e2m1 values, one power-of-two E8M0 scale per 32 consecutive k), bf16/f16 activations -----------------------
-// The next halving of the weight stream after fp8: 0.53 bytes per weight.  Stored format (the contract, also what a later
-// v_mfma_scale_*_f8f6f4 prefill would read): q [N, K/2] bytes, byte j of a row = element 2j in the LOW nibble and 2j + 1 in the high
+// The next halving of the weight stream after fp8: 0.53 bytes per weight.  Stored format (the contract: the prefill's many-row product
+// mh_gemm_fp4w, gemm_fp4w.hip, reads it as it is, and a later v_mfma_scale_*_f8f6f4 product would): q [N, K/2] bytes, byte j of a row = element 2j in the LOW nibble and 2j + 1 in the high
 // one, code s e e m = magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; scales [N, K/32] bytes = e + 127.
 // Scale: the rule of kv8_exp moved to a maximum of 6 - e the smallest integer with amax 2^-e <= 6 (amax = m 2^ex, m in [0.5, 1):
 // e = ex - 3 if m <= 0.75 else ex - 2), clamped to >= -126, 0 for an all-zero block: nothing saturates.  Value: w 2^-e (exact in fp32)

@@ -120,7 +120,9 @@ class Session:
     each span was encoded from).  A call keeps the longest reusable prefix (_reusable_prefix), truncates the cache to it, grows the cache
     when the call needs more rows than it has (to a multiple of 256) and runs only the tail: engine.prefill into this cache when nothing is
     kept, engine.extend otherwise.  `last`: reused_tokens, run_tokens and images_encoded of the last call.  capacity: rows of the cache
-    (default config.max_position_embeddings), allocated at the first call."""
+    (default config.max_position_embeddings), allocated at the first call.  `w_fp4`: the weight format that wrote the cached rows (True:
+    the MXFP4 copies, generate(fp4_prefill=True)); a call with the other format reuses nothing (a full prefill, reused_tokens = 0) -
+    rows of two different models are never mixed."""
 
     def __init__(self, model, capacity=None, fp8_kv=False):
         self.model, self.fp8_kv = model, bool(fp8_kv)
@@ -134,18 +136,23 @@ class Session:
     def reset(self):
         """Forget everything: the next call prefills its whole prompt.  The cache's memory is kept."""
         self.tokens, self.spans, self.images = [], [], []
+        self.w_fp4 = False
         if self.cache is not None:
             self.cache.truncate(0)
 
-    def _prefill(self, input_ids, images, room):
+    def _prefill(self, input_ids, images, room, w_fp4=False):
         """The session's form of engine.prefill(input_ids, None, images, room): -> (logits fp32 [1, V] at the prompt's last position,
-        the session's cache holding the prompt, with `room` free rows behind it)."""
+        the session's cache holding the prompt, with `room` free rows behind it).  w_fp4: the prompt runs on the MXFP4 weight copies;
+        rows that the other weight format wrote are not reused."""
         m = self.model
         eng = m.engine
         ids = [int(t) for t in input_ids[0].tolist()]
         new_spans = _image_spans(ids, getattr(m, "im_start_token", None), getattr(m, "im_end_token", None)) if images is not None else []
         new_images = [im[j] for im in (images or []) for j in range(im.shape[0])]
         keep = _reusable_prefix(self.tokens, self.spans, self.images, ids, new_spans, new_images)
+        if bool(w_fp4) != self.w_fp4:
+            keep = 0
+        self.w_fp4 = bool(w_fp4)
         need = len(ids) + int(room)
         grown = -(-need // 256) * 256  # a call that needs more rows than the session has gets them in whole 256-row steps
         if self.cache is None or (need > self.cache.Smax and keep == 0):  # (nothing to carry over: no copy)
@@ -156,12 +163,12 @@ class Session:
         self.cache.truncate(keep)
         kept = sum(1 for _, e in new_spans if e <= keep)  # images whose spans lie in the kept prefix: not encoded again
         if keep == 0:
-            logits, _ = eng.prefill(input_ids, None, images, 0, kv_fp8=self.fp8_kv, cache=self.cache)
+            logits, _ = eng.prefill(input_ids, None, images, 0, kv_fp8=self.fp8_kv, cache=self.cache, w_fp4=self.w_fp4)
             encoded = len(new_images)
         else:
             tail = new_images[kept:]
             encoded = len(tail)
-            logits = eng.extend(self.cache, input_ids[:, keep:], [torch.stack(tail)] if tail else None, pos=keep)
+            logits = eng.extend(self.cache, input_ids[:, keep:], [torch.stack(tail)] if tail else None, pos=keep, w_fp4=self.w_fp4)
         # (copies: a caller that changes its image tensor in place must not change what the session believes it encoded)
         self.tokens, self.spans, self.images = ids, new_spans, self.images[:kept] + [x.clone() for x in new_images[kept:len(new_spans)]]
         self.last = dict(reused_tokens=keep, run_tokens=len(ids) - keep, images_encoded=encoded)
@@ -404,6 +411,7 @@ class _Call:
     use_graph: bool = True
     fp8_weights: bool = False    # the decode step's weight format: at most one of the two
     fp4_weights: bool = False
+    fp4_prefill: bool = False    # the prompt passes on the MXFP4 copies too (needs fp4_weights)
     fp8_kv: bool = False
     session: Session = None
     bans: dict = None            # _ban_plan; None: the call bans nothing
@@ -419,7 +427,8 @@ class _Call:
 
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
-             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, negative_images=None, **kw):
+             use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, negative_images=None,
+             fp4_prefill=False, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
@@ -427,8 +436,17 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     about half the cache bytes in every mode (greedy, sampling, beam search; with or without use_graph and fp8_weights / fp4_weights).
     fp4_weights=True runs the decode-step projections on MXFP4 copies of the decoder's Linear weights and lm_head (OCP e2m1 values, one
     power-of-two scale per 32 k, engine.quantize_decode_weights_fp4: about 0.53 bytes per weight streamed per token instead of 2; the
-    prompt's prefill keeps the 16-bit weights), in every mode and with either cache format; the alternative to fp8_weights, not an
-    addition to it, and it needs use_cache=True (it applies to the decode step).
+    prompt's prefill keeps the 16-bit weights unless fp4_prefill is set), in every mode and with either cache format; the alternative to
+    fp8_weights, not an addition to it, and it needs use_cache=True (it applies to the decode step).
+    fp4_prefill=True (with fp4_weights=True; alone it is refused) runs every prompt pass of the call on the same MXFP4 copies
+    (ops.gemm_fp4w, engine.prefill / extend w_fp4=True): the prefill of greedy search, sampling, prompt lookup and beam search (also with
+    share_prompt_kv), both sequences of a guided call and a session's prefill or extension.  The call is then ONE model from the first
+    prompt token to the last generated one - the quantised one: the prompt's K/V rows are those the decode step would have written and
+    the first token comes from the quantised lm_head - where the default mixes the 16-bit model's prompt rows with the quantised
+    model's steps.  A session remembers which format wrote its rows; a call with the other format reuses none of them
+    (reused_tokens = 0).  It buys consistency, not time - measured on one MI355X at the 7B geometry (profiles/fp4_prefill_bench.txt): a
+    projection through ops.gemm_fp4w takes 1.3-1.5 times the tuned 16-bit GEMM's time at M = 4096 and 1.3-1.9 times at M = 613 (the down
+    projection is the 1.9), the whole prefill of a 613-token prompt with one image 19.0 ms against 15.0 (x 1.27).
     share_prompt_kv=True (beam search only: num_beams > 1) keeps the prompt's keys and values once per prompt, where the prefill wrote
     them, instead of one copy per beam (engine.BeamKVCache): a beam owns only the rows of its generated tokens, re-ordering the beams
     rewrites an int32 ancestry table (mh_beam_ancestry) and moves no K/V, and the attention loads every prompt key once for all the beams
@@ -466,6 +484,8 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         raise ValueError("fp4_weights and fp8_weights are alternatives: pick one weight format for the decode step")
     if fp4_weights and not use_cache:
         raise ValueError("fp4_weights=True applies to the KV-cache decode step: it needs use_cache=True")
+    if fp4_prefill and not fp4_weights:
+        raise ValueError("fp4_prefill=True runs the prompt on the MXFP4 copies that fp4_weights=True decodes with: it needs fp4_weights=True")
     if share_prompt_kv and num_beams <= 1:
         raise ValueError("share_prompt_kv=True shares the prompt's KV cache among the beams of beam search: it needs num_beams > 1")
     if share_prompt_kv and num_beams > 16:
@@ -517,7 +537,7 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
     call = _Call(model=model, images=images, attention_mask=None if beams else attention_mask,  # (beam search: all ones, as checked)
                  max_len=max_len, eos_ids=eos_ids, pad=pad, stop=_Stopper(max_len, eos_ids, stopping_criteria), sel=sel, streamer=streamer,
-                 use_graph=use_graph, fp8_weights=bool(fp8_weights), fp4_weights=bool(fp4_weights), fp8_kv=bool(fp8_kv), session=session,
+                 use_graph=use_graph, fp8_weights=bool(fp8_weights), fp4_weights=bool(fp4_weights), fp4_prefill=bool(fp4_prefill), fp8_kv=bool(fp8_kv), session=session,
                  bans=_ban_plan(o, eos_ids), guide=guide, stats=stats, lookup=lookup, max_ngram=None if lookup is None else max_ngram,
                  num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping, share_prompt_kv=bool(share_prompt_kv))
     if beams:
@@ -548,12 +568,12 @@ def _select(logits, V, sel, step):
     return O.select_tokens(logits, V, step=step, **sel)
 
 
-def _guided_prefill(eng, guide, input_ids, images, room, fp8_kv, V):
+def _guided_prefill(eng, guide, input_ids, images, room, fp8_kv, V, w_fp4=False):
     """The guided form of engine.prefill: the prompt and the unconditional context prefilled one after the other, their caches paired
     (engine.pair_cache: row 0 conditional, row 1 unconditional, `room` free rows behind the longer one) -> (guided scores fp32 [1, >= V],
     the B = 2 cache)."""
-    lc, cc = eng.prefill(input_ids, None, images, 0, kv_fp8=fp8_kv)
-    lu, cu = eng.prefill(guide["ids"] if guide["ids"] is not None else input_ids[:, -1:], None, guide["images"], 0, kv_fp8=fp8_kv)
+    lc, cc = eng.prefill(input_ids, None, images, 0, kv_fp8=fp8_kv, w_fp4=w_fp4)
+    lu, cu = eng.prefill(guide["ids"] if guide["ids"] is not None else input_ids[:, -1:], None, guide["images"], 0, kv_fp8=fp8_kv, w_fp4=w_fp4)
     return O.guidance_mix(lc, lu, guide["scale"], V, out=lc), eng.pair_cache(cc, cu, room)
 
 
@@ -611,11 +631,11 @@ class _Stepper:
         select the first token; the cache is self.cache."""
         c = self.call
         if c.guide is not None:  # one sequence to the caller; rows (conditional, unconditional) to the decode step
-            logits, self.cache = _guided_prefill(self.eng, c.guide, input_ids, c.images, room, c.fp8_kv, self.V)
+            logits, self.cache = _guided_prefill(self.eng, c.guide, input_ids, c.images, room, c.fp8_kv, self.V, w_fp4=c.fp4_prefill)
         elif c.session is not None:
-            logits, self.cache = c.session._prefill(input_ids, c.images, room)
+            logits, self.cache = c.session._prefill(input_ids, c.images, room, w_fp4=c.fp4_prefill)
         else:
-            logits, self.cache = self.eng.prefill(input_ids, c.attention_mask, c.images, room, kv_fp8=c.fp8_kv)
+            logits, self.cache = self.eng.prefill(input_ids, c.attention_mask, c.images, room, kv_fp8=c.fp8_kv, w_fp4=c.fp4_prefill)
         self.input_ids, self.P, self.logits0 = input_ids, input_ids.shape[1], logits
         if c.bans is not None:
             self.tables = _ban_tables(c.bans, c.eos_ids, self.P, logits.device)

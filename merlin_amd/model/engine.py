@@ -742,6 +742,30 @@ class HipEngine:
         # the row scales (one float per token) are kept: their maximum is the tensor-wide scale of the transposed wgrad operand
         return x, y, ((h1, qkv, o, lse, x2, h2, gu, act, (a1[1], a2[1], a3[1], a4[1]), packed) if keep else None)
 
+    # ---- MXFP4 weights for the prompt (forward only): the prefill's counterpart of the decode step's fp4 GEMVs --------------------------
+    @staticmethod
+    def _stream_add_fp4(x, a, qw):
+        """_stream_add on an MXFP4 weight pair: an fp32 stream is updated IN PLACE (fp32 read-modify-write), a 16-bit one is a new tensor."""
+        if x.dtype == torch.float32:
+            return O.gemm_fp4w(a, qw, out=x, accum=True)
+        return O.gemm_fp4w(a, qw, resid=x)
+
+    def _llama_layer_fwd_fp4(self, W, Q, x, B, S, lens, kv_out=None, unpad=None):
+        """Forward-only decoder layer on the MXFP4 copies (Q: this layer's dict of quantize_decode_weights_fp4()): _llama_layer_fwd with
+        ops.gemm_fp4w for the four projections - q|k|v then ops.rope_qk_, o with the residual form, gate|up then ops.swiglu_fwd, down with
+        the residual form - so the K/V rows it writes are those of the model decode_step(fp4=True) runs.  Norms, RoPE, attention, SwiGLU
+        and the residual stream (fp32 or 16-bit) are the 16-bit layer's.  -> the stream after the layer."""
+        cfg = self.model.config
+        H, D = cfg.num_attention_heads, head_dim_of(cfg)
+        eps = cfg.rms_norm_eps
+        h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
+        qkv = O.rope_qk_(O.gemm_fp4w(h1, Q["wqkv"]), self.rope, S, H, D)
+        o, _, _ = self._attn_fwd(qkv, B, S, H, D, lens, unpad, kv_out)
+        x = self._stream_add_fp4(x, o, Q["wo"])
+        h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
+        act = O.swiglu_fwd(O.gemm_fp4w(h2, Q["wgu"]))
+        return self._stream_add_fp4(x, act, Q["wd"])
+
     def _wgrad_fp8(self, dyT8, x, sx, gout, fresh):
         """gout[N_out, K_in] (+)= dy^T x on the scaled-fp8 MFMA: both operands as transposed e4m3 copies (contraction over the
         tokens, zero-padded to a multiple of 128).  The GRADIENT operand is scaled per output feature (column maxima: a pass
@@ -930,8 +954,10 @@ class HipEngine:
     # public entry points
     # ------------------------------------------------------------------------------------------
     def forward(self, input_ids, attention_mask, labels, images, inputs_embeds=None, want_grad=False, loss_only=False,
-                kv_cache=None, last_only=False, fp8=False):
-        """Returns (loss fp32 scalar tensor | None, logits fp32 [B,S,V] view | None, ctx)."""
+                kv_cache=None, last_only=False, fp8=False, fp4=False):
+        """Returns (loss fp32 scalar tensor | None, logits fp32 [B,S,V] view | None, ctx).
+        fp4=True (forward only): the decoder layers and lm_head run on the MXFP4 copies of quantize_decode_weights_fp4() - the model that
+        decode_step(fp4=True) continues; tower, projector, embeddings and norms are unchanged."""
         m = self.model
         cfg = m.config
         A = self.ensure_arena()
@@ -999,7 +1025,16 @@ class HipEngine:
             raise RuntimeError("prefill runs the 16-bit or fp8-forward path")
         if fp8 and not fp8_train and want_grad:
             raise RuntimeError("model.fp8_forward is the inference form (forward only); set model.fp8_training = True for the fp8 training step")
-        if fp8:
+        if fp4 and fp8:
+            raise RuntimeError("fp4 and fp8 weights are alternatives, not a combination (model.fp4_forward / model.fp8_forward)")
+        if fp4 and want_grad:
+            raise RuntimeError("model.fp4_forward is the inference form (forward only): the MXFP4 copies have no backward")
+        if fp4:
+            F4 = getattr(self, "_fp4", None) or self.quantize_decode_weights_fp4()
+
+            def layer(li, x, kv):
+                return None, self._llama_layer_fwd_fp4(self.llama[li], F4["layers"][li], x, B, S, lens, kv_out=kv, unpad=unpad), None
+        elif fp8:
             if fp8_train:
                 Q8 = [self.fp8_train_weights(li) for li in range(len(self.llama))]
             else:
@@ -1022,6 +1057,8 @@ class HipEngine:
         if last_only:  # prefill of generate(): only each sequence's last valid position feeds the sampler
             last = (lens.to(torch.int64) - 1) if lens is not None else torch.full((B,), S - 1, dtype=torch.int64, device=dev)
             rows = O.gather_rows(hn, torch.arange(B, device=dev) * S + last.clamp_min(0))
+            if fp4:  # (the fp4 copy of lm_head has V rows)
+                return None, O.gemv_fp4w(rows, F4["lm_head"], out_f32=True, n=V), ctx
             return None, O.gemv(rows, wlm, out_f32=True, n=V), ctx
         # fp8 training step: the head's three GEMMs run on the scaled-fp8 MFMA too (BASELINE cfg 5: every Linear) when the geometry
         # allows it (contractions over d, V and T in whole 128-blocks); the logits stay fp32
@@ -1033,6 +1070,9 @@ class HipEngine:
             logits = O.gemm_fp8(hn8, self.fp8_head_weights()["w"], out=torch.empty(T, Vpad, dtype=torch.float32, device=dev), dt16=dt)
             ctx["hn_scales"] = hn8[1] if want_grad else None
             del hn8
+        elif fp4:  # [T, Vpad] fp32; the copy holds the V vocabulary rows, the pad columns read as the zero rows of the 16-bit weight
+            logits = torch.zeros(T, Vpad, dtype=torch.float32, device=dev) if Vpad != V else torch.empty(T, V, dtype=torch.float32, device=dev)
+            O.gemm_fp4w(hn, F4["lm_head"], out=logits[:, :V])
         else:
             logits = O.gemm_nt(hn, wlm, out_f32=True)  # [T, Vpad] fp32
         loss = None
@@ -1220,13 +1260,15 @@ class HipEngine:
         self._rope_table(cache.Smax + max_new, cache.lens.device)  # the prefill may have been given no room to append (its rows stay the prompt's)
         return HipEngine.BeamKVCache(cache, num_beams, max_new)
 
-    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False, cache=None):
+    def prefill(self, input_ids, attention_mask, images, max_new_tokens, inputs_embeds=None, kv_fp8=False, cache=None, w_fp4=False):
         """Full forward over the prompt that also fills a KV cache; returns (logits fp32 [B, V] at each sequence's last
         valid position, cache).  Right-padded prompts (attention_mask) decode from their own length.
         kv_fp8=True: the cache is stored as e4m3 bytes + power-of-two scales (KVCache fp8=True); the prompt's own attention still runs on
         the unquantised keys and values, so these logits do not change.
         cache: an existing KVCache to fill from row 0 instead of a new one (a session's: generation.Session); it keeps its own format and
-        must have B rows and room for the prompt and max_new_tokens."""
+        must have B rows and room for the prompt and max_new_tokens.
+        w_fp4=True: the decoder and lm_head run on the MXFP4 copies (forward(fp4=True)): keys, values and logits of the model that
+        decode_step(fp4=True) continues."""
         self.ensure_arena()
         B, S = (input_ids.shape if input_ids is not None else inputs_embeds.shape[:2])
         A = self.arena
@@ -1238,7 +1280,7 @@ class HipEngine:
             cache.rpos = None
         self._rope_table(max(S + max_new_tokens, cache.Smax), A.flat.device)
         _, logits, ctx = self.forward(input_ids, attention_mask, None, images, inputs_embeds=inputs_embeds, kv_cache=cache,
-                                      last_only=True)
+                                      last_only=True, fp4=w_fp4)
         lens = ctx["lens"]
         if ctx.get("unpad") is not None:
             # general mask (left padding / holes): the cache holds the valid keys only; the next token's rotary position is the
@@ -1249,13 +1291,15 @@ class HipEngine:
             cache.lens.copy_(lens if lens is not None else torch.full((B,), S, dtype=torch.int32, device=A.flat.device))
         return logits, cache
 
-    def extend(self, cache, input_ids, images=None, pos=None):
+    def extend(self, cache, input_ids, images=None, pos=None, w_fp4=False):
         """n = input_ids.shape[1] new positions of ONE sequence on a plain KVCache that already holds P = cache.lens[0] tokens; returns
         logits fp32 [1, V] at the last new position and advances the cache by n.  The prefill's path on the tail alone: embedding and
         image splice of the tail (tower and projector only for `images`, the images whose spans lie in the tail), per layer the prefill's
         GEMMs with the RoPE epilogue reading the table from row P on (rotary positions P .. P + n - 1), the rotated keys and the values
         appended to cache rows [P, P + n) (fp8 cache: quantised by mh_kv8_fill on views offset by P), then mh_attn_extend over the cache
-        AFTER the append - the new keys are read as stored, like decode_step and verify_step read them.  Always the 16-bit weights.
+        AFTER the append - the new keys are read as stored, like decode_step and verify_step read them.  The 16-bit weights, or with
+        w_fp4=True the MXFP4 copies of quantize_decode_weights_fp4() (ops.gemm_fp4w per projection, the last row's logits by
+        ops.gemv_fp4w): the weight format must be the one that wrote the cached rows.
         pos: P when the caller knows it on the host (a session does); None reads cache.lens back."""
         m = self.model
         cfg = m.config
@@ -1287,28 +1331,32 @@ class HipEngine:
         x = splice(ids.view(-1), src.view(-1) if src is not None else None, emb, feats)
         del feats
         lens1 = cache.lens + 1  # what the first new query sees: the cached rows and its own key
-        hn = self._extend_layers(cache, x, rope, n, P, O.attn_extend, lens1, n, H, D)
-        logits = O.gemv(hn[n - 1:n], self._lm_head_w(), out_f32=True, n=V)
+        hn = self._extend_layers(cache, x, rope, n, P, O.attn_extend, lens1, n, H, D, w_fp4=w_fp4)
+        if w_fp4:
+            logits = O.gemv_fp4w(hn[n - 1:n], self._fp4["lm_head"], out_f32=True, n=V)
+        else:
+            logits = O.gemv(hn[n - 1:n], self._lm_head_w(), out_f32=True, n=V)
         cache.advance(n)
         return logits
 
-    def _extend_layers(self, cache, x, rope, n, P, attn, *attn_args):
+    def _extend_layers(self, cache, x, rope, n, P, attn, *attn_args, w_fp4=False):
         """The layer loop of extend and extend_branches over the n embedded rows x of one sequence: the prefill's GEMMs with `rope` as the
         RoPE epilogue's table (row t: the position of row t), the rotated keys and the values appended to cache rows [P, P + n), then
         attn (ops.attn_extend or ops.attn_extend_branches, with attn_args behind q and the layer's tensors) over the cache AFTER the
-        append.  -> the normalised final hidden rows [n, d]."""
+        append.  w_fp4=True: the projections of _llama_layer_fwd_fp4 on the MXFP4 copies.  -> the normalised final hidden rows [n, d]."""
         cfg = self.model.config
         H, D, eps = cfg.num_attention_heads, head_dim_of(cfg), cfg.rms_norm_eps
+        F4 = (getattr(self, "_fp4", None) or self.quantize_decode_weights_fp4())["layers"] if w_fp4 else None
         for li, W in enumerate(self.llama):
             h1, _ = self._stream_norm(x, W.ln1, eps, want_x16=False)
-            qkv = O.gemm_nt_rope(h1, W.wqkv, rope, n, H, D)
+            qkv = O.rope_qk_(O.gemm_fp4w(h1, F4[li]["wqkv"]), rope, n, H, D) if w_fp4 else O.gemm_nt_rope(h1, W.wqkv, rope, n, H, D)
             q, k, v = self._qkv(qkv)
             cache.append_rows(li, k, v, n, P, H, D)
             o = cache.attend(attn, li, q, *attn_args)
-            x = self._stream_add(x, o, W.wo)
+            x = self._stream_add_fp4(x, o, F4[li]["wo"]) if w_fp4 else self._stream_add(x, o, W.wo)
             h2, _ = self._stream_norm(x, W.ln2, eps, want_x16=False)
-            _, act = O.gemm_swiglu_fwd(h2, W.wgu)
-            x = self._stream_add(x, act, W.wd)
+            act = O.swiglu_fwd(O.gemm_fp4w(h2, F4[li]["wgu"])) if w_fp4 else O.gemm_swiglu_fwd(h2, W.wgu)[1]
+            x = self._stream_add_fp4(x, act, F4[li]["wd"]) if w_fp4 else self._stream_add(x, act, W.wd)
         return self._stream_norm(x, self.arena.view("model.norm.weight"), eps, want_x16=False)[0]
 
     HEAD_CHUNK = 256  # rows of fp32 logits held at a time by the scoring pass (256 x V floats: 33 MB at V = 32003)

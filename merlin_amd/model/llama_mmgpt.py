@@ -225,6 +225,9 @@ class MMGPTLlamaForCausalLM(nn.Module):
         # opt-in fp8 paths (BASELINE cfg 5's fp8 MFMA weight path): model.fp8_training = True -> forward + backward GEMMs of the decoder
         # on the scaled-fp8 MFMA; model.fp8_forward = True -> the inference form (forward only, weights quantised once)
         fp8 = "train" if getattr(self, "fp8_training", False) else bool(getattr(self, "fp8_forward", False))
+        # model.fp4_forward = True -> the decoder and lm_head on the MXFP4 copies generate(fp4_weights=True) decodes with (forward only):
+        # full-sequence logits and loss of the quantised model
+        fp4 = bool(getattr(self, "fp4_forward", False))
         if getattr(self.engine, "parity_fp32", False) and inputs_embeds is None:
             # fp32-store parity forward (merlin_amd/parity.py): measures the kernels against BASELINE's 1e-3, forward only
             if want_grad:
@@ -237,7 +240,7 @@ class MMGPTLlamaForCausalLM(nn.Module):
             return CausalLMOutputWithPast(loss=loss, logits=logits) if return_dict else ((loss, logits) if loss is not None else (logits,))
         with torch.no_grad():
             loss, logits, ectx = self.engine.forward(input_ids, attention_mask, labels, images, inputs_embeds=inputs_embeds,
-                                                     want_grad=want_grad, fp8=fp8)
+                                                     want_grad=want_grad, fp8=fp8, fp4=fp4)
         if want_grad:
             if self._anchor is None or self._anchor.device != loss.device:
                 self._anchor = torch.zeros(1, device=loss.device, requires_grad=True)
@@ -267,6 +270,8 @@ class MMGPTLlamaForCausalLM(nn.Module):
         engine's prefill + KV-cache decode step (merlin_amd/generation.py).  Extras: use_cache=False (full recompute per token,
         the cross-check), use_graph (decode step as one HIP graph), fp8_weights (fp8 weight copies for the decode GEMVs),
         fp4_weights (MXFP4 copies instead: e2m1 values + one power-of-two scale per 32 k, about a quarter of the 16-bit bytes; needs use_cache),
+        fp4_prefill (with fp4_weights: every prompt pass of the call - prefill, session extension, both guidance sequences - runs on the
+        MXFP4 copies too, so the whole call is ONE model, the quantised one; costs prefill time, see generation.generate),
         fp8_kv (KV cache stored as e4m3 bytes + power-of-two scales: about half the cache bytes; needs use_cache),
         share_prompt_kv (beam search only: the prompt's K/V once per prompt instead of once per beam, beams re-ordered through a table),
         seed (counter-based sampling stream; default drawn from torch's global generator),

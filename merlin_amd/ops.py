@@ -286,6 +286,40 @@ def gemv_fp4w(x, qw, out=None, resid=None, out_f32=False, n=None):
     return out
 
 
+def gemm_fp4w(x, qw, out=None, resid=None, out_f32=False, accum=False, n=None):
+    """out[M, N] = x[M, K] @ dequant(q, scales)^T for any number of rows in ONE launch (prefill, full-sequence forward); qw = (q, scales)
+    from quant_fp4_b32, read as stored.  Store forms: 16-bit (+ 16-bit resid), fp32 (out_f32, or an fp32 `out`), fp32 read-modify-write
+    (accum: out += product, out given and fp32).  Anything the launcher would refuse is a ValueError and nothing is launched."""
+    q, sc = qw
+    if x.dim() != 2 or q.dim() != 2 or sc.dim() != 2 or q.dtype != torch.uint8 or sc.dtype != torch.uint8:
+        raise ValueError("gemm_fp4w takes x [M, K] and the (q, scales) uint8 pair of quant_fp4_b32")
+    M, K = x.shape
+    N = q.shape[0] if n is None else n
+    if K % 32 or q.shape[1] * 2 != K or sc.shape[1] * 32 != K:
+        raise ValueError(f"gemm_fp4w: K = {K} must be a multiple of the 32-element scale block and match the weight's {q.shape[1] * 2}")
+    if M < 1 or not 1 <= N <= q.shape[0] or x.dtype not in (torch.bfloat16, torch.float16) or not (q.is_contiguous() and sc.is_contiguous()):
+        raise ValueError(f"gemm_fp4w: M = {M}, N = {N} of {q.shape[0]} weight rows, x {x.dtype}")
+    out_f32 = bool(out_f32) or (out is not None and out.dtype == torch.float32)
+    if accum and not out_f32:
+        raise ValueError("gemm_fp4w: accum is the fp32 read-modify-write (out_f32); a 16-bit sum takes resid")
+    if accum and out is None:
+        raise ValueError("gemm_fp4w: accum adds to `out`, which must be given")
+    if resid is not None and (accum or out_f32):
+        raise ValueError("gemm_fp4w: resid goes with the 16-bit store only (not with accum or out_f32)")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    if out.dtype != (torch.float32 if out_f32 else x.dtype) or out.shape[0] < M or out.shape[1] < N:
+        raise ValueError(f"gemm_fp4w: out {tuple(out.shape)} {out.dtype} does not hold [{M}, {N}] {'fp32' if out_f32 else x.dtype}")
+    if resid is not None and (resid.dtype != x.dtype or resid.shape[0] < M or resid.shape[1] < N):
+        raise ValueError(f"gemm_fp4w: resid {tuple(resid.shape)} {resid.dtype} does not hold [{M}, {N}] {x.dtype}")
+    if _rowmajor(x) % 8 or x.data_ptr() % 16:
+        raise ValueError("gemm_fp4w: x rows must be 16-byte aligned")
+    with _timed("gemm_fp4w", 2.0 * M * N * K, 2.0 * M * K + 0.53125 * N * K + float(out.element_size()) * M * N):
+        L.call("mh_gemm_fp4w", x, _rowmajor(x), q, sc, out, _rowmajor(out), resid, _rowmajor(resid) if resid is not None else 0, M, N, K,
+               dt_of(x), int(out_f32), int(bool(accum)), _stream())
+    return out
+
+
 def gemv_fp4w_norm(x, norm_w, eps, qw, swiglu=False, out=None):
     """gemv_norm with MXFP4 weights (qw = (q, scales) from quant_fp4_b32).  1-2 rows: norm, projection (and SwiGLU) in one launch;
     3-16 rows: separate norm, SwiGLU still fused; more rows: separate launches."""
