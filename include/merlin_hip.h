@@ -373,10 +373,8 @@ int mh_decode_rope_append(void* qkv, const float* cos_sin, const int32_t* pos, c
                           int H, int D, int Smax, int dt, void* stream);
 /* out[b, h*D..] = softmax(q[b,h] . K[b, 0..lens[b]) / sqrt(D)) V[b, 0..lens[b]);  q row stride ldq; D in {64, 128}.
  * Split-KV: with ws != NULL (B*H*mh_attn_decode_splits(B,H,Smax)*(D+2) floats) several blocks share one (b, h) and a second
- * launch merges their partial softmaxes; ws == NULL runs one block per (b, h).  mh_attn_decode_fused_merge(1): the last block of a
- * (b, h) to finish merges instead (ticket counters inside the library: one decode stream at a time; A-B arm, default off). */
+ * launch merges their partial softmaxes; ws == NULL runs one block per (b, h). */
 int mh_attn_decode_splits(int B, int H, int Smax);
-void mh_attn_decode_fused_merge(int on);
 int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens,
                    int B, int H, int D, int Smax, float* ws, int dt, void* stream);
 /* fp8 KV cache of the decode step (half the cache bytes per token): K and V rows as OCP e4m3 bytes k8 / v8 [B, Smax, H*D] with one fp32
@@ -390,8 +388,7 @@ int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* v
  * mh_decode_rope_append_kv8: mh_decode_rope_append with the quantiser behind it - qkv is rotated in place bit-identically, the rotated
  *   16-bit k row and the v row as it lies in qkv are quantised into row pos[b].
  * mh_attn_decode_kv8: mh_attn_decode on that cache - keys [0, min(lens[b], Smax)), the same workspace and split plan
- *   (mh_attn_decode_splits; ws == NULL: one block per (b, h)), fp32 scores, softmax and accumulation, each scale applied once per key.
- *   The split partials are always merged by the second launch: mh_attn_decode_fused_merge does not apply. */
+ *   (mh_attn_decode_splits; ws == NULL: one block per (b, h)), fp32 scores, softmax and accumulation, each scale applied once per key. */
 int mh_kv8_fill(const void* x, int64_t ldx, void* c8, float* scales, int B, int S, int H, int D, int Smax, int dt, void* stream);
 int mh_decode_rope_append_kv8(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* k8, void* v8, float* kscale,
                               float* vscale, int B, int H, int D, int Smax, int dt, void* stream);

@@ -32,6 +32,7 @@
 //                       kernel of mh_attn_extend with a two-part horizon - the prompt's keys and the query's own continuation's.
 // A decode step of a layer is 6 launches; each costs ~4 us of fixed time on top of its streaming, which is why the neighbours are folded in.
 #include <climits>
+#include <type_traits>
 
 #include "mh_common.h"
 
@@ -855,215 +856,120 @@ __global__ __launch_bounds__(256) void rope_append_k(uint16_t* __restrict__ qkv,
   rope_append_lane<DT, KV8>(qkv, tab, kc_, vc_, ks, vs, b, b, h, v, pos[b], rpos[b], H, D, Smax);
 }
 
-__device__ __forceinline__ void st_agent(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_agent(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// ticket counters of the split-KV merge, one per (b, h): zero at load, left zero by every launch (one decode stream at a time)
-__device__ unsigned g_decode_tickets[16384];
+// ---- one query per (sequence or beam, head): ONE KERNEL over a cache-format policy and a row-source policy --------------------------------
+// A format policy holds what differs between the KV-cache formats and nothing else (the W* policies' convention, above):
+//   ES, Raw    bytes per cache element, and a lane's 8-element piece of a key / value row as it is loaded
+//   load / zero / to_f32<DT>   the streamed piece, the piece of a key beyond the range, and its 8 values
+//   SCALED     one fp32 scale per (row, head, key) multiplies the score and the probability: s_j = (q . k8_j) ks_j scale,
+//              o += (p_j vs_j) v8_j - one multiply per key, none per element, and - the scales being powers of two - the arithmetic of the
+//              16-bit form on the dequantised cache
+//   UNR_DENSE  key rows requested per thread before any is used, dense rows (the cache is streamed, so what limits the rate is bytes in flight)
+struct KV16 {  // bf16 / f16 rows
+  static constexpr int ES = 2, UNR_DENSE = 4;  // (4: not measured against other depths)
+  static constexpr bool SCALED = false;
+  using Raw = uint4;
+  static __device__ __forceinline__ Raw load(const void* p) { return ld_stream16(p); }
+  static __device__ __forceinline__ Raw zero() { return make_uint4(0, 0, 0, 0); }
+  template <int DT>
+  static __device__ __forceinline__ void to_f32(const Raw& r, float* f) { unpack8<DT>(r, f); }
+};
+struct KVFp8 {  // e4m3 bytes and fp32 scales (fp8 KV cache, above)
+  static constexpr int ES = 1, UNR_DENSE = 8;  // (a lane's piece is 8 bytes, so twice the rows for the same bytes in flight; not measured against 4)
+  static constexpr bool SCALED = true;
+  using Raw = uint2;
+  static __device__ __forceinline__ Raw load(const void* p) { return ld_stream8(p); }
+  static __device__ __forceinline__ Raw zero() { return make_uint2(0, 0); }
+  template <int DT>
+  static __device__ __forceinline__ void to_f32(const Raw& r, float* f) {
+    fp8x4_to_f32(r.x, f);
+    fp8x4_to_f32(r.y, f + 4);
+  }
+};
+template <bool KV8>
+using KVFmt = std::conditional_t<KV8, KVFp8, KV16>;
 
-// q [B, ldq] (head h at h*D); kc, vc [B, Smax, H*D]; out [B, H*D]; keys [0, len[b]).  D in {64, 128}.
-// Split-KV ("flash decoding"): with B*H blocks only (32 at batch 1) the cache streams at a few % of HBM speed, so
-// `splits` blocks share one (b, h), each takes `chunk` keys and leaves (unnormalised o[D], max, sum) in `ws`;
-// attn_decode_combine_k merges them as a second launch (cnt == NULL, the default) - or the last of the blocks to finish does
-// (cnt != NULL: mh_attn_decode_fused_merge(1), an A/B arm that measured no faster).  splits == 1 writes the normalised result directly.
-template <int DT, int D>
-__global__ __launch_bounds__(256) void attn_decode_k(const uint16_t* __restrict__ q, int64_t ldq, const uint16_t* __restrict__ kc,
-                                                     const uint16_t* __restrict__ vc, uint16_t* __restrict__ out,
-                                                     const int32_t* __restrict__ lens, int H, int Smax, float scale_log2,
-                                                     int splits, int chunk, float* __restrict__ ws, unsigned* __restrict__ cnt) {
+// A row-source policy says which cache row holds key j of query row m - row0() + row(j), where row0() is folded into the block's base
+// pointers once - how many rows are requested ahead, and what a launch leaves.
+// Either way the cache is [rows, S, H*D] with scales [rows, H, S], the keys are [0, min(lens[m], S)), and split sp leaves its partial in
+// slot `slot0 + sp` of the `wsplits`-wide ws row (m*H + h).
+struct DenseRows {  // mh_attn_decode: sequence m's keys lie in cache row m (S = Smax).  One split writes the normalised result itself
+  static constexpr bool DIRECT = true;
+  template <class Fmt>
+  static constexpr int UNR = Fmt::UNR_DENSE;
+  int m;
+  __device__ __forceinline__ DenseRows(const int32_t*, int, int m_, int, int) : m(m_) {}
+  __device__ __forceinline__ int row0() const { return m; }
+  __device__ __forceinline__ int row(int, bool) const { return 0; }
+};
+struct AncestryRows {  // the suffix part of mh_attn_decode_beams: key j of beam row m lies in suffix row anc[m, j] (S = G).  Always partials
+  static constexpr bool DIRECT = false;
+  template <class Fmt>
+  static constexpr int UNR = 4;  // (both formats; not measured against other depths)
+  const int32_t* anc;
+  int last;
+  __device__ __forceinline__ AncestryRows(const int32_t* anc_, int rows, int m, int G, int key0) : anc(anc_ + (int64_t)m * G + key0), last(rows - 1) {}
+  __device__ __forceinline__ int row0() const { return 0; }
+  __device__ __forceinline__ int row(int j, bool ok) const { return ok ? min(max(anc[j], 0), last) : 0; }
+};
+
+// q [M, ldq] (head h at h*D); kc, vc [rows, S, H*D] (ks, vs [rows, H, S]: Fmt::SCALED); out [M, H*D]; D in {64, 128}.
+// Split-KV ("flash decoding"): with M*H blocks only (32 at batch 1) the cache streams at a few % of HBM speed, so `splits` blocks share
+// one (m, h), each takes `chunk` keys and leaves (unnormalised o[D], max, sum) in `ws`; attn_decode_combine_k merges them as a second
+// launch.  Dense rows with splits == 1 write the normalised result directly.
+template <class Fmt, class Rows, int DT, int D>
+__global__ __launch_bounds__(256) void attn_decode_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
+                                                     const void* __restrict__ vc_, const float* __restrict__ ks,
+                                                     const float* __restrict__ vs, uint16_t* __restrict__ out,
+                                                     const int32_t* __restrict__ lens, const int32_t* __restrict__ anc, int rows, int H, int S,
+                                                     float scale_log2, int splits, int chunk, float* __restrict__ ws, int slot0,
+                                                     int wsplits) {
   extern __shared__ float sc[];  // [chunk] scores, then [G][D] partial outputs
   __shared__ float red[8];
+  typedef typename Fmt::Raw Raw;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sp = blockIdx.x % splits;
-  const int h = (blockIdx.x / splits) % H, b = blockIdx.x / (splits * H);
+  const int h = (blockIdx.x / splits) % H, m = blockIdx.x / (splits * H);
   const int key0 = sp * chunk;
-  const int len = max(0, min(min(lens[b], Smax) - key0, chunk));  // keys [key0, key0 + len) of this split
-  kc += (int64_t)key0 * H * D;
-  vc += (int64_t)key0 * H * D;
+  const int len = max(0, min(min(lens[m], S) - key0, chunk));  // keys [key0, key0 + len) of this split
   const int64_t HD = (int64_t)H * D;
-  // pass 1: D/8 lanes per key (one 16-byte piece each: a key row is one coalesced 256-byte read), 256*8/D keys per
-  // block iteration; the partial dot products are summed across the lane group by shuffles
-  constexpr int OCT1 = D / 8, KPI = 256 / OCT1;
-  const int kpart = tid % OCT1, ksub = tid / OCT1;
-  float q8[8];
-  unpack8<DT>(*(const uint4*)(q + (int64_t)b * ldq + (int64_t)h * D + kpart * 8), q8);
-  float mx = -1e30f;
-  // (UNR key rows requested per thread before any is used: the cache is streamed, so what limits the rate is bytes in flight)
-  constexpr int UNR = 4;
-  for (int j0 = 0; j0 < len; j0 += KPI * UNR) {
-    uint4 kraw[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * KPI + ksub;
-      kraw[u] = (j < len) ? ld_stream16(kc + ((int64_t)b * Smax + j) * HD + (int64_t)h * D + kpart * 8) : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * KPI + ksub;
-      float kv[8];
-      unpack8<DT>(kraw[u], kv);
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s = fmaf(q8[e], kv[e], s);
-#pragma unroll
-      for (int o2 = OCT1 / 2; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2, 64);
-      s *= scale_log2;
-      if (j < len) {
-        if (kpart == 0) sc[j] = s;
-        mx = fmaxf(mx, s);
-      }
-    }
-  }
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int j = tid; j < len; j += 256) {
-    const float pj = fast_exp2(sc[j] - mx);
-    sc[j] = pj;
-    sum += pj;
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  sum = (red[4] + red[5]) + (red[6] + red[7]);
-  // pass 2: thread = (key slice g of 256*8/D, channel octet c); 8 channels per thread
-  constexpr int OCT = D / 8;       // octets per value row
-  constexpr int G = 256 / OCT;     // key slices
+  const Rows src(anc, rows, m, S, key0);
+  // thread = (key slice gsl of G = 256*8/D, channel octet c) in both passes: a row is one coalesced read of D/8 lanes, 8 values each
+  constexpr int OCT = D / 8, G = 256 / OCT, UNR = Rows::template UNR<Fmt>;
   const int c = tid % OCT, gsl = tid / OCT;
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int j0 = gsl; j0 < len; j0 += G * UNR) {
-    uint4 vraw[UNR];
-    float pj[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * G;
-      const bool ok = j < len;
-      vraw[u] = ok ? ld_stream16(vc + ((int64_t)b * Smax + j) * HD + (int64_t)h * D + c * 8) : make_uint4(0, 0, 0, 0);
-      pj[u] = ok ? sc[j] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      float vv[8];
-      unpack8<DT>(vraw[u], vv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = fmaf(pj[u], vv[e], o[e]);
-    }
-  }
-  __syncthreads();  // everyone is done reading the scores: reuse the buffer for the slice partials
-  float* part = sc;  // [G][D]
-#pragma unroll
-  for (int e = 0; e < 8; ++e) part[gsl * D + c * 8 + e] = o[e];
-  __syncthreads();
-  if (tid < D) {
-    float a = 0.f;
-    for (int g2 = 0; g2 < G; ++g2) a += part[g2 * D + tid];
-    if (splits == 1) {
-      out[(int64_t)b * HD + (int64_t)h * D + tid] = (uint16_t)st16<DT>(len > 0 ? a / sum : 0.f);
-    } else {
-      float* w = ws + ((int64_t)(b * H + h) * splits + sp) * (D + 2);
-      if (cnt) {  // device-coherent stores: the merging block may sit on another XCD (its L2 is not this one's)
-        st_agent(w + tid, a);
-        if (tid == 0) { st_agent(w + D, mx); st_agent(w + D + 1, sum); }
-      } else {
-        w[tid] = a;
-        if (tid == 0) { w[D] = mx; w[D + 1] = sum; }
-      }
-    }
-  }
-  if (splits == 1 || !cnt) return;
-  // The last of the `splits` blocks of this (b, h) to get here merges the partial softmaxes: no second launch (at batch 1 the merge
-  // kernel is 5.6 us of dependent round trips per layer - and so is this tail: no gain).  Ticket counter per (b, h), reset by its last taker.
-  // (no __threadfence: at agent scope it writes back and invalidates the whole L2 - measured 150 us per layer.  The partials are
-  //  written and read with device-coherent accesses, so all the release needs is that this block's stores have completed)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned t = __hip_atomic_fetch_add(cnt + (b * H + h), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = (t == (unsigned)splits - 1u);
-    if (last) __hip_atomic_store(cnt + (b * H + h), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    red[0] = last ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (red[0] == 0.f) return;
-  asm volatile("" ::: "memory");
-  if (tid < D) {
-    const float* w = ws + (int64_t)(b * H + h) * splits * (D + 2);
-    float v[32], sm_[32], sl_[32];
-#pragma unroll
-    for (int s2 = 0; s2 < 32; ++s2) {  // every partial is requested before any is used
-      v[s2] = s2 < splits ? ld_agent(w + s2 * (D + 2) + tid) : 0.f;
-      sm_[s2] = s2 < splits ? ld_agent(w + s2 * (D + 2) + D) : -1e30f;
-      sl_[s2] = s2 < splits ? ld_agent(w + s2 * (D + 2) + D + 1) : 0.f;
-    }
-    float M = -1e30f;
-#pragma unroll
-    for (int s2 = 0; s2 < 32; ++s2) M = fmaxf(M, sm_[s2]);
-    float num = 0.f, den = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < 32; ++s2) {
-      if (s2 < splits) {
-        const float f = fast_exp2(sm_[s2] - M);
-        num += v[s2] * f;
-        den += sl_[s2] * f;
-      }
-    }
-    out[(int64_t)b * HD + (int64_t)h * D + tid] = (uint16_t)st16<DT>(den > 0.f ? num / den : 0.f);
-  }
-}
-
-// attn_decode_k on the fp8 KV cache (k8, v8 e4m3 bytes [B, Smax, H*D]; ks, vs fp32 scales [B, H, Smax]): the same launch plan, LDS use and
-// partial layout (attn_decode_combine_k merges the splits), half the bytes per key.  A key's scale is requested with its row;
-// s_j = (q . k8_j) ks_j scale, o += (p_j vs_j) v8_j: one multiply per key, none per element, and - the scales being powers of two - the
-// arithmetic of the 16-bit kernel on the dequantised cache.  A lane's piece of a row is 8 bytes, so twice the rows are in flight per thread.
-template <int DT, int D>
-__global__ __launch_bounds__(256) void attn_decode_kv8_k(const uint16_t* __restrict__ q, int64_t ldq, const uint8_t* __restrict__ k8,
-                                                         const uint8_t* __restrict__ v8, const float* __restrict__ ks,
-                                                         const float* __restrict__ vs, uint16_t* __restrict__ out,
-                                                         const int32_t* __restrict__ lens, int H, int Smax, float scale_log2, int splits,
-                                                         int chunk, float* __restrict__ ws) {
-  extern __shared__ float sc[];  // [chunk] scores, then [G][D] partial outputs
-  __shared__ float red[8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int sp = blockIdx.x % splits;
-  const int h = (blockIdx.x / splits) % H, b = blockIdx.x / (splits * H);
-  const int key0 = sp * chunk;
-  const int len = max(0, min(min(lens[b], Smax) - key0, chunk));  // keys [key0, key0 + len) of this split
-  const int64_t HD = (int64_t)H * D;
-  k8 += ((int64_t)b * Smax + key0) * HD + (int64_t)h * D;
-  v8 += ((int64_t)b * Smax + key0) * HD + (int64_t)h * D;
-  ks += ((int64_t)b * H + h) * Smax + key0;
-  vs += ((int64_t)b * H + h) * Smax + key0;
-  constexpr int OCT = D / 8, G = 256 / OCT;  // lanes per row (8 values each), rows per block iteration
-  const int c = tid % OCT, gsl = tid / OCT;
-  constexpr int UNR = 8;
+  // key j of this split in cache row row0() + r: its piece for this thread, and its scale
+  const int64_t piece0 = ((((int64_t)src.row0() * S + key0) * HD) + (int64_t)h * D + c * 8) * Fmt::ES;
+  const int64_t scale0 = ((int64_t)src.row0() * H + h) * S + key0;
+  const uint8_t* kc = (const uint8_t*)kc_ + piece0;
+  const uint8_t* vc = (const uint8_t*)vc_ + piece0;
+  auto piece = [&](const uint8_t* base, int r, int j) { return base + ((int64_t)r * S + j) * HD * Fmt::ES; };
+  auto scale = [&](const float* base, int r, int j) { return base[((int64_t)r * H) * S + scale0 + j]; };
+  // pass 1: the partial dot products are summed across a key's lane group by shuffles
   float q8[8];
-  unpack8<DT>(*(const uint4*)(q + (int64_t)b * ldq + (int64_t)h * D + c * 8), q8);
+  unpack8<DT>(*(const uint4*)(q + (int64_t)m * ldq + (int64_t)h * D + c * 8), q8);
   float mx = -1e30f;
   for (int j0 = 0; j0 < len; j0 += G * UNR) {
-    uint2 kraw[UNR];
+    Raw kraw[UNR];
     float ksc[UNR];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int j = j0 + u * G + gsl;
       const bool ok = j < len;
-      kraw[u] = ok ? ld_stream8(k8 + (int64_t)j * HD + c * 8) : make_uint2(0, 0);
-      ksc[u] = ok ? ks[j] : 0.f;
+      const int r = src.row(j, ok);
+      kraw[u] = ok ? Fmt::load(piece(kc, r, j)) : Fmt::zero();
+      if constexpr (Fmt::SCALED) ksc[u] = ok ? scale(ks, r, j) : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int j = j0 + u * G + gsl;
       float kv[8];
-      fp8x4_to_f32(kraw[u].x, kv);
-      fp8x4_to_f32(kraw[u].y, kv + 4);
+      Fmt::template to_f32<DT>(kraw[u], kv);
       float s = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; ++e) s = fmaf(q8[e], kv[e], s);
 #pragma unroll
       for (int o2 = OCT / 2; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2, 64);
-      s = s * ksc[u] * scale_log2;
+      if constexpr (Fmt::SCALED) s = s * ksc[u] * scale_log2;
+      else s *= scale_log2;
       if (j < len) {
         if (c == 0) sc[j] = s;
         mx = fmaxf(mx, s);
@@ -1084,24 +990,26 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_k(const uint16_t* __restr
   if (lane == 0) red[4 + wave] = sum;
   __syncthreads();
   sum = (red[4] + red[5]) + (red[6] + red[7]);
+  // pass 2: 8 channels per thread over the keys of its slice
   float o[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) o[e] = 0.f;
   for (int j0 = gsl; j0 < len; j0 += G * UNR) {
-    uint2 vraw[UNR];
+    Raw vraw[UNR];
     float pj[UNR];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int j = j0 + u * G;
       const bool ok = j < len;
-      vraw[u] = ok ? ld_stream8(v8 + (int64_t)j * HD + c * 8) : make_uint2(0, 0);
-      pj[u] = ok ? sc[j] * vs[j] : 0.f;
+      const int r = src.row(j, ok);
+      vraw[u] = ok ? Fmt::load(piece(vc, r, j)) : Fmt::zero();
+      if constexpr (Fmt::SCALED) pj[u] = ok ? sc[j] * scale(vs, r, j) : 0.f;
+      else pj[u] = ok ? sc[j] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       float vv[8];
-      fp8x4_to_f32(vraw[u].x, vv);
-      fp8x4_to_f32(vraw[u].y, vv + 4);
+      Fmt::template to_f32<DT>(vraw[u], vv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = fmaf(pj[u], vv[e], o[e]);
     }
@@ -1114,10 +1022,10 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_k(const uint16_t* __restr
   if (tid < D) {
     float a = 0.f;
     for (int g2 = 0; g2 < G; ++g2) a += part[g2 * D + tid];
-    if (splits == 1) {
-      out[(int64_t)b * HD + (int64_t)h * D + tid] = (uint16_t)st16<DT>(len > 0 ? a / sum : 0.f);
+    if (Rows::DIRECT && splits == 1) {
+      out[(int64_t)m * HD + (int64_t)h * D + tid] = (uint16_t)st16<DT>(len > 0 ? a / sum : 0.f);
     } else {
-      float* w = ws + ((int64_t)(b * H + h) * splits + sp) * (D + 2);
+      float* w = ws + ((int64_t)(m * H + h) * wsplits + slot0 + sp) * (D + 2);
       w[tid] = a;
       if (tid == 0) { w[D] = mx; w[D + 1] = sum; }
     }
@@ -1397,137 +1305,6 @@ __global__ __launch_bounds__(256) void beam_ancestry_k(const int32_t* __restrict
   if (threadIdx.x == 0 && n < G) anc_out[(int64_t)m * G + n] = m;
 }
 
-// The suffix part of mh_attn_decode_beams: attn_decode_k / attn_decode_kv8_k (block per (beam row m, head, key split), the same two
-// passes, LDS use and partial layout) with one indirection - key g of row m is read from suffix row anc[m, g] (its fp8 scale from
-// [anc[m, g], h, g]).  Keys [0, min(slens[m], G)).  Always leaves partials: slot `slot0 + split` of the ws row (m*H + h), wsplits wide.
-template <int DT, int D, bool KV8>
-__global__ __launch_bounds__(256) void attn_decode_beams_suffix_k(const uint16_t* __restrict__ q, int64_t ldq, const void* __restrict__ kc_,
-                                                                  const void* __restrict__ vc_, const float* __restrict__ ks,
-                                                                  const float* __restrict__ vs, const int32_t* __restrict__ anc,
-                                                                  const int32_t* __restrict__ slens, int rows, int H, int G,
-                                                                  float scale_log2, int splits, int chunk, float* __restrict__ ws,
-                                                                  int slot0, int wsplits) {
-  extern __shared__ float sc[];  // [chunk] scores, then [NS][D] partial outputs
-  __shared__ float red[8];
-  constexpr int ES = KV8 ? 1 : 2;  // bytes per cache element
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int sp = blockIdx.x % splits;
-  const int h = (blockIdx.x / splits) % H, m = blockIdx.x / (splits * H);
-  const int key0 = sp * chunk;
-  const int len = max(0, min(min(slens[m], G) - key0, chunk));  // keys [key0, key0 + len) of this split
-  const int64_t HD = (int64_t)H * D;
-  const uint8_t* kc = (const uint8_t*)kc_;
-  const uint8_t* vc = (const uint8_t*)vc_;
-  anc += (int64_t)m * G + key0;
-  constexpr int OCT = D / 8, NS = 256 / OCT;  // lanes per row (8 values each), rows per block iteration
-  const int c = tid % OCT, gsl = tid / OCT;
-  constexpr int UNR = 4;
-  float q8[8];
-  unpack8<DT>(*(const uint4*)(q + (int64_t)m * ldq + (int64_t)h * D + c * 8), q8);
-  float mx = -1e30f;
-  for (int j0 = 0; j0 < len; j0 += NS * UNR) {
-    uint4 kraw[UNR];
-    float ksc[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * NS + gsl;
-      const bool ok = j < len;
-      const int r = ok ? min(max(anc[j], 0), rows - 1) : 0;
-      const uint8_t* src = kc + ((((int64_t)r * G + key0 + j) * HD) + (int64_t)h * D + c * 8) * ES;
-      if constexpr (KV8) {
-        const uint2 w = ok ? ld_stream8(src) : make_uint2(0, 0);
-        kraw[u] = make_uint4(w.x, w.y, 0, 0);
-        ksc[u] = ok ? ks[((int64_t)r * H + h) * G + key0 + j] : 0.f;
-      } else {
-        kraw[u] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
-        ksc[u] = 1.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * NS + gsl;
-      float kv[8];
-      if constexpr (KV8) {
-        fp8x4_to_f32(kraw[u].x, kv);
-        fp8x4_to_f32(kraw[u].y, kv + 4);
-      } else {
-        unpack8<DT>(kraw[u], kv);
-      }
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s = fmaf(q8[e], kv[e], s);
-#pragma unroll
-      for (int o2 = OCT / 2; o2 > 0; o2 >>= 1) s += __shfl_xor(s, o2, 64);
-      if constexpr (KV8) s = s * ksc[u] * scale_log2;
-      else s *= scale_log2;
-      if (j < len) {
-        if (c == 0) sc[j] = s;
-        mx = fmaxf(mx, s);
-      }
-    }
-  }
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  float sum = 0.f;
-  for (int j = tid; j < len; j += 256) {
-    const float pj = fast_exp2(sc[j] - mx);
-    sc[j] = pj;
-    sum += pj;
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) red[4 + wave] = sum;
-  __syncthreads();
-  sum = (red[4] + red[5]) + (red[6] + red[7]);
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = 0.f;
-  for (int j0 = gsl; j0 < len; j0 += NS * UNR) {
-    uint4 vraw[UNR];
-    float pj[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int j = j0 + u * NS;
-      const bool ok = j < len;
-      const int r = ok ? min(max(anc[j], 0), rows - 1) : 0;
-      const uint8_t* src = vc + ((((int64_t)r * G + key0 + j) * HD) + (int64_t)h * D + c * 8) * ES;
-      if constexpr (KV8) {
-        const uint2 w = ok ? ld_stream8(src) : make_uint2(0, 0);
-        vraw[u] = make_uint4(w.x, w.y, 0, 0);
-        pj[u] = ok ? sc[j] * vs[((int64_t)r * H + h) * G + key0 + j] : 0.f;
-      } else {
-        vraw[u] = ok ? ld_stream16(src) : make_uint4(0, 0, 0, 0);
-        pj[u] = ok ? sc[j] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      float vv[8];
-      if constexpr (KV8) {
-        fp8x4_to_f32(vraw[u].x, vv);
-        fp8x4_to_f32(vraw[u].y, vv + 4);
-      } else {
-        unpack8<DT>(vraw[u], vv);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = fmaf(pj[u], vv[e], o[e]);
-    }
-  }
-  __syncthreads();  // everyone is done reading the scores: reuse the buffer for the slice partials
-  float* part = sc;  // [NS][D]
-#pragma unroll
-  for (int e = 0; e < 8; ++e) part[gsl * D + c * 8 + e] = o[e];
-  __syncthreads();
-  if (tid < D) {
-    float a = 0.f;
-    for (int g2 = 0; g2 < NS; ++g2) a += part[g2 * D + tid];
-    float* w = ws + ((int64_t)(m * H + h) * wsplits + slot0 + sp) * (D + 2);
-    w[tid] = a;
-    if (tid == 0) { w[D] = mx; w[D + 1] = sum; }
-  }
-}
-
 // Prompt-lookup drafter (transformers PromptLookupCandidateGenerator.get_candidates, no logits processor): one block per row of ids
 // [rows, ld].  For n = min(max_ngram, len - 1) .. 1: the EARLIEST window ids[i .. i + n) equal to the last n tokens whose continuation
 // ids[i + n .. min(i + n + k, len, max_length)) is not empty; the first n that has one wins.  out [rows, k], out_count [rows] (0: none).
@@ -1696,21 +1473,27 @@ extern "C" int mh_gemv_norm(const void* x, int64_t ldx, const void* norm_w, floa
   return gemv_impl({x, ldx, W, ldw, nullptr, out, ldo, nullptr, 0, M, ff > 0 ? ff : N, K, dt, 0, ff, norm_w, eps, RopeAppend{}, stream});
 }
 
+// the one-token append of either cache format (ks, vs: the fp8 cache's scales); dt is MH_BF16 or MH_F16, checked by the fronts
+template <bool KV8>
+static int launch_rope_append(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kc, void* vc, float* ks,
+                              float* vs, int B, int H, int D, int Smax, int dt, void* stream) {
+  const int64_t total = (int64_t)B * H * (D / 16);
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (dt == MH_BF16)
+    hipLaunchKernelGGL((rope_append_k<MH_BF16, KV8>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       kc, vc, ks, vs, B, H, D, Smax);
+  else
+    hipLaunchKernelGGL((rope_append_k<MH_F16, KV8>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
+                       kc, vc, ks, vs, B, H, D, Smax);
+  MH_LAUNCH_CHECK();
+}
 
 extern "C" int mh_decode_rope_append(void* qkv, const float* cos_sin, const int32_t* pos, const int32_t* rope_pos, void* kcache, void* vcache,
                                      int B, int H, int D, int Smax, int dt, void* stream) {
   if (!rope_pos) rope_pos = pos;
   if (!qkv || !cos_sin || !pos || !kcache || !vcache || B <= 0 || H <= 0 || (D & 15) || Smax <= 0) return MH_ERR_ARG;
   if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  const int64_t total = (int64_t)B * H * (D / 16);
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dt == MH_BF16)
-    hipLaunchKernelGGL((rope_append_k<MH_BF16, false>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       kcache, vcache, (float*)nullptr, (float*)nullptr, B, H, D, Smax);
-  else
-    hipLaunchKernelGGL((rope_append_k<MH_F16, false>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       kcache, vcache, (float*)nullptr, (float*)nullptr, B, H, D, Smax);
-  MH_LAUNCH_CHECK();
+  return launch_rope_append<false>(qkv, cos_sin, pos, rope_pos, kcache, vcache, nullptr, nullptr, B, H, D, Smax, dt, stream);
 }
 
 // mh_decode_rope_append on the fp8 KV cache: qkv rotated in place exactly as above; the rotated k row and the v row are quantised (one
@@ -1722,15 +1505,7 @@ extern "C" int mh_decode_rope_append_kv8(void* qkv, const float* cos_sin, const 
   if (!aligned16(qkv) || (((uintptr_t)k8 | (uintptr_t)v8) & 7u)) return MH_ERR_ARG;  // 16-byte row pieces in, 8-byte e4m3 stores out
   if (D != 128 && D != 64) return MH_ERR_SHAPE;
   if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  const int64_t total = (int64_t)B * H * (D / 16);
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dt == MH_BF16)
-    hipLaunchKernelGGL((rope_append_k<MH_BF16, true>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       k8, v8, kscale, vscale, B, H, D, Smax);
-  else
-    hipLaunchKernelGGL((rope_append_k<MH_F16, true>), grid, block, 0, as_stream(stream), (uint16_t*)qkv, (const float2*)cos_sin, pos, rope_pos,
-                       k8, v8, kscale, vscale, B, H, D, Smax);
-  MH_LAUNCH_CHECK();
+  return launch_rope_append<true>(qkv, cos_sin, pos, rope_pos, k8, v8, kscale, vscale, B, H, D, Smax, dt, stream);
 }
 
 // prefill of the fp8 KV cache: x [B*S, H, D] (row stride ldx elements; the k or the v section of the fused q|k|v buffer) -> c8 rows
@@ -1751,8 +1526,6 @@ extern "C" int mh_kv8_fill(const void* x, int64_t ldx, void* c8, float* scales, 
   MH_LAUNCH_CHECK();
 }
 
-static int g_decode_fused_merge = 0;  // 1: split-KV merge by the last block of a (b, h) instead of a second launch (A-B arm: measured 0.3-1 % slower, profiles/r03_decode_nt_ab.txt)
-extern "C" void mh_attn_decode_fused_merge(int on) { g_decode_fused_merge = on ? 1 : 0; }
 extern "C" int mh_attn_decode_splits(int B, int H, int Smax) {
   int s = (1024 + B * H - 1) / (B * H);
   const int by_len = (Smax + 127) / 128;  // >= 128 keys per split
@@ -1761,75 +1534,55 @@ extern "C" int mh_attn_decode_splits(int B, int H, int Smax) {
   return s < 1 ? 1 : s;
 }
 
-extern "C" int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens,
-                              int B, int H, int D, int Smax, float* ws, int dt, void* stream) {
-  if (!q || !kcache || !vcache || !out || !lens || B <= 0 || H <= 0 || Smax <= 0 || (ldq & 7)) return MH_ERR_ARG;
-  if (D != 128 && D != 64) return MH_ERR_SHAPE;
-  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+template <class Fmt, int DT, int D>
+static void launch_attn_decode(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                               const int32_t* lens, int B, int H, int Smax, int splits, int chunk, size_t lds, float* ws, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)attn_decode_k<Fmt, DenseRows, DT, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    attr = true;
+  }
   const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+  hipLaunchKernelGGL((attn_decode_k<Fmt, DenseRows, DT, D>), dim3(B * H * splits), dim3(256), lds, st, (const uint16_t*)q, ldq, kc, vc, ks, vs,
+                     (uint16_t*)out, lens, (const int32_t*)nullptr, B, H, Smax, scale_log2, splits, chunk, ws, 0, splits);
+  if (splits > 1)
+    hipLaunchKernelGGL((attn_decode_combine_k<DT, D>), dim3(B * H), dim3(D), 0, st, (const float*)ws, (uint16_t*)out, H, splits);
+}
+
+// the split plan (mh_attn_decode_splits; ws == NULL: one block per (b, h)), a block's LDS and the launches of mh_attn_decode / _kv8, which
+// check their own arguments: D is 64 or 128 and dt MH_BF16 or MH_F16 here
+template <bool KV8>
+static int attn_decode_impl(const void* q, int64_t ldq, const void* kc, const void* vc, const float* ks, const float* vs, void* out,
+                            const int32_t* lens, int B, int H, int D, int Smax, float* ws, int dt, void* stream) {
   const int splits = ws ? mh_attn_decode_splits(B, H, Smax) : 1;
   const int chunk = (Smax + splits - 1) / splits;
   const int G = 256 / (D / 8);
   const size_t lds = sizeof(float) * (size_t)((chunk > G * D) ? chunk : G * D);
   if (lds > 150 * 1024) return MH_ERR_SHAPE;  // <= 38400 keys per split
-  const dim3 grid(B * H * splits), block(256);
   hipStream_t st = as_stream(stream);
-  unsigned* cnt = nullptr;
-  if (splits > 1 && g_decode_fused_merge && B * H <= 16384) {
-    static unsigned* tickets = nullptr;
-    if (!tickets && hipGetSymbolAddress((void**)&tickets, HIP_SYMBOL(g_decode_tickets)) != hipSuccess) tickets = nullptr;
-    cnt = tickets;
-  }
-#define GO(DT_, D_)                                                                                                     \
-  do {                                                                                                                   \
-    static bool attr = false;                                                                                           \
-    if (!attr) {                                                                                                         \
-      hipFuncSetAttribute((const void*)attn_decode_k<DT_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-      attr = true;                                                                                                       \
-    }                                                                                                                    \
-    hipLaunchKernelGGL((attn_decode_k<DT_, D_>), grid, block, lds, st, (const uint16_t*)q, ldq, (const uint16_t*)kcache, \
-                       (const uint16_t*)vcache, (uint16_t*)out, lens, H, Smax, scale_log2, splits, chunk, ws, cnt);      \
-    if (splits > 1 && !cnt)                                                                                              \
-      hipLaunchKernelGGL((attn_decode_combine_k<DT_, D_>), dim3(B * H), dim3(D_), 0, st, (const float*)ws, (uint16_t*)out, H, splits); \
-  } while (0)
+#define GO(DT_, D_) launch_attn_decode<KVFmt<KV8>, DT_, D_>(q, ldq, kc, vc, ks, vs, out, lens, B, H, Smax, splits, chunk, lds, ws, st)
   if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
   else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
 #undef GO
   MH_LAUNCH_CHECK();
 }
 
-// mh_attn_decode on the fp8 KV cache (k8, v8 + kscale, vscale): same semantics, workspace and split plan (mh_attn_decode_splits; ws == NULL:
-// one block per (b, h)); the split partials are always merged by the second launch (mh_attn_decode_fused_merge does not apply).
+extern "C" int mh_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, void* out, const int32_t* lens,
+                              int B, int H, int D, int Smax, float* ws, int dt, void* stream) {
+  if (!q || !kcache || !vcache || !out || !lens || B <= 0 || H <= 0 || Smax <= 0 || (ldq & 7)) return MH_ERR_ARG;
+  if (D != 128 && D != 64) return MH_ERR_SHAPE;
+  if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
+  return attn_decode_impl<false>(q, ldq, kcache, vcache, nullptr, nullptr, out, lens, B, H, D, Smax, ws, dt, stream);
+}
+
+// mh_attn_decode on the fp8 KV cache (k8, v8 + kscale, vscale): same semantics, workspace and split plan
 extern "C" int mh_attn_decode_kv8(const void* q, int64_t ldq, const void* k8, const void* v8, const float* kscale, const float* vscale, void* out,
                                   const int32_t* lens, int B, int H, int D, int Smax, float* ws, int dt, void* stream) {
   if (!q || !k8 || !v8 || !kscale || !vscale || !out || !lens || B <= 0 || H <= 0 || Smax <= 0 || (ldq & 7)) return MH_ERR_ARG;
   if (((uintptr_t)k8 | (uintptr_t)v8) & 7u) return MH_ERR_ARG;  // the cache is read 8 bytes at a time
   if (D != 128 && D != 64) return MH_ERR_SHAPE;
   if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-  const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
-  const int splits = ws ? mh_attn_decode_splits(B, H, Smax) : 1;
-  const int chunk = (Smax + splits - 1) / splits;
-  const int G = 256 / (D / 8);
-  const size_t lds = sizeof(float) * (size_t)((chunk > G * D) ? chunk : G * D);
-  if (lds > 150 * 1024) return MH_ERR_SHAPE;  // <= 38400 keys per split
-  const dim3 grid(B * H * splits), block(256);
-  hipStream_t st = as_stream(stream);
-#define GO(DT_, D_)                                                                                                          \
-  do {                                                                                                                        \
-    static bool attr = false;                                                                                                \
-    if (!attr) {                                                                                                              \
-      hipFuncSetAttribute((const void*)attn_decode_kv8_k<DT_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);  \
-      attr = true;                                                                                                            \
-    }                                                                                                                         \
-    hipLaunchKernelGGL((attn_decode_kv8_k<DT_, D_>), grid, block, lds, st, (const uint16_t*)q, ldq, (const uint8_t*)k8, (const uint8_t*)v8, \
-                       kscale, vscale, (uint16_t*)out, lens, H, Smax, scale_log2, splits, chunk, ws);                        \
-    if (splits > 1)                                                                                                           \
-      hipLaunchKernelGGL((attn_decode_combine_k<DT_, D_>), dim3(B * H), dim3(D_), 0, st, (const float*)ws, (uint16_t*)out, H, splits); \
-  } while (0)
-  if (dt == MH_BF16) { if (D == 128) GO(MH_BF16, 128); else GO(MH_BF16, 64); }
-  else { if (D == 128) GO(MH_F16, 128); else GO(MH_F16, 64); }
-#undef GO
-  MH_LAUNCH_CHECK();
+  return attn_decode_impl<true>(q, ldq, k8, v8, kscale, vscale, out, lens, B, H, D, Smax, ws, dt, stream);
 }
 
 // ---- T new tokens per sequence (the verify step of prompt-lookup decoding) --------------------------------------------------------------
@@ -2246,8 +1999,8 @@ static void launch_attn_beams(const void* q, int64_t ldq, const void* pk, const 
   const size_t slds = sizeof(float) * (size_t)(schunk > NS * D ? schunk : NS * D);
   hipLaunchKernelGGL((attn_decode_multi_k<DT, D, TQ, KV8, true>), dim3(Bp * H * psplits), dim3(256), plds, st, (const uint16_t*)q, ldq, pk, pv,
                      pks, pvs, (uint16_t*)out, pre_lens, nb, H, Pmax, scale_log2, psplits, pchunk, ws, wsplits);
-  hipLaunchKernelGGL((attn_decode_beams_suffix_k<DT, D, KV8>), dim3(rows * H * ssplits), dim3(256), slds, st, (const uint16_t*)q, ldq, sk, sv,
-                     sks, svs, anc, slens, rows, H, G, scale_log2, ssplits, schunk, ws, psplits, wsplits);
+  hipLaunchKernelGGL((attn_decode_k<KVFmt<KV8>, AncestryRows, DT, D>), dim3(rows * H * ssplits), dim3(256), slds, st, (const uint16_t*)q, ldq, sk,
+                     sv, sks, svs, (uint16_t*)nullptr, slens, anc, rows, H, G, scale_log2, ssplits, schunk, ws, psplits, wsplits);
   hipLaunchKernelGGL((attn_decode_combine_k<DT, D>), dim3(rows * H), dim3(D), 0, st, (const float*)ws, (uint16_t*)out, H, wsplits);
 }
 
@@ -2269,7 +2022,8 @@ static int attn_beams_impl(const void* q, int64_t ldq, const void* pk, const voi
   {  // the suffix kernel's LDS beyond the default 64 KiB (G above 65 536)
     static bool attr = false;
     if (!attr && (int64_t)schunk * 4 > 64 * 1024) {
-#define GO(DT_, D_) hipFuncSetAttribute((const void*)attn_decode_beams_suffix_k<DT_, D_, KV8>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_MULTI_LDS_MAX)
+#define GO(DT_, D_) \
+  hipFuncSetAttribute((const void*)attn_decode_k<KVFmt<KV8>, AncestryRows, DT_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_MULTI_LDS_MAX)
       GO(MH_BF16, 128); GO(MH_BF16, 64); GO(MH_F16, 128); GO(MH_F16, 64);
 #undef GO
       attr = true;

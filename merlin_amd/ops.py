@@ -647,11 +647,6 @@ def ban_tokens(logits, V=None, ids=None, len0=0, len_step=0, ld_ids=None, ngram=
     return logits
 
 
-def attn_decode_fused_merge(on: bool):
-    """A/B switch: split-KV partials merged by a second launch (default) or by the last block of a (b, h) to finish."""
-    L.lib().mh_attn_decode_fused_merge(1 if on else 0)
-
-
 _splitk_ws = {}
 SPLITK_WS_MIN = 256 * 65536  # floats: one round of 256 tiles of fp32 partials (the most mh_gemm_splitk_max ever asks for)
 

@@ -3,7 +3,7 @@
 Prefill: every family, bf16 and fp16, at the smallest shapes at which each form's structure is present - the three forward forms (o through
 _hold_heads, bit equality of the forms, lse per element), the seven-product backward in the three fused-kv modes and the five-product
 backward where it applies.  Cache kernels: one-hot and sink keys placed by key index - inside the first split, the last split, one key of a
-middle split, prefix only, suffix only - for mh_attn_decode (merge launch, fused merge, one block), _multi, extend, extend_branches, _beams
+middle split, prefix only, suffix only - for mh_attn_decode (merge launch, one block), _multi, extend, extend_branches, _beams
 and their fp8-cache forms, against N.attention_decode on the dequantised cache.
 
 Outputs and gradients keep the project's rule: limit = N.limit(c_model), c_model from the rounding model on the same inputs.  lse is held to
@@ -184,7 +184,7 @@ def _grow(splits_of, Smax, want=3, cap=1 << 16):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("kind,shift", KINDS)
 def test_decode_with_placed_heavy_keys_per_element(ops, dtype, kind, shift):
-    """mh_attn_decode / _kv8 (split-KV by a merge launch, by the fused merge, one block) on the smallest shape of its own test, Smax raised to
+    """mh_attn_decode / _kv8 (split-KV by a merge launch, one block) on the smallest shape of its own test, Smax raised to
     three splits.  Sequence 0 fills the cache; sequence 1 ends one key into the last split, so "last split" is a split of ONE key."""
     from merlin_amd import _lib as L
 
@@ -203,14 +203,8 @@ def test_decode_with_placed_heavy_keys_per_element(ops, dtype, kind, shift):
         ref, Bc, mod = _refs([(q[b].view(H, D), k64[b, :lens[b]], v64[b, :lens[b]]) for b in range(B)], dtype)
         lens_t = torch.tensor(lens, dtype=torch.int32, device=dev())
         name = f"{kind} {tag} Smax={Smax} splits={splits}"
-        try:
-            for fused in (False, True):
-                ops.attn_decode_fused_merge(fused)
-                how = "fused merge" if fused else "merge launch"
-                hold(f"attention decode 16-bit {how} {name}", dtype, ops.attn_decode(q, k16, v16, lens_t, H, D).view(B, H, D), ref, Bc, mod)
-                hold(f"attention decode kv8 {how} {name}", dtype, ops.attn_decode_kv8(q, k8, v8, ks, vs, lens_t, H, D).view(B, H, D), ref, Bc, mod)
-        finally:
-            ops.attn_decode_fused_merge(False)
+        hold(f"attention decode 16-bit merge launch {name}", dtype, ops.attn_decode(q, k16, v16, lens_t, H, D).view(B, H, D), ref, Bc, mod)
+        hold(f"attention decode kv8 merge launch {name}", dtype, ops.attn_decode_kv8(q, k8, v8, ks, vs, lens_t, H, D).view(B, H, D), ref, Bc, mod)
         hold(f"attention decode 16-bit one block {name}", dtype, ops.attn_decode(q, k16, v16, lens_t, H, D, split_kv=False).view(B, H, D), ref, Bc, mod)
         hold(f"attention decode kv8 one block {name}", dtype, ops.attn_decode_kv8(q, k8, v8, ks, vs, lens_t, H, D, split_kv=False).view(B, H, D), ref, Bc, mod)
 

@@ -171,9 +171,13 @@ def test_beam_ancestry_kernel_alone(O):
 # [c, c + 1], c the prefix chunk of mh_attn_decode_beams_splits - a split exactly full, and one with a single key
 # G = 600: the suffix part's key splits (3 of 200 keys) - all of them full (gen = 599); one full, one with a single key and one empty
 # (gen = 200); the same at D = 128 with two prompts, so that the rows of the second prompt's beams lie behind the first's
+# gen as a list, one per beam: 63 / 64 / 65 suffix keys at D = 128 and 127 / 128 / 129 at D = 64 - one unrolled iteration of the suffix
+# kernel (256 * 8 / D key slices x 4 rows in flight) less one key, exactly, and plus one - in one suffix split and in the first of two
 BEAM_ATTN_CASES = [(1, 1, 2, 128, 40, [1], 4, 0), (2, 5, 4, 64, 700, [1, 690], 16, 15), (1, 3, 2, 128, 300, [299], 8, 3),
                    (1, 16, 2, 128, 600, [590], 8, 7), (1, 9, 2, 64, 300, [290], 8, 0), (2, 5, 4, 64, 700, "straddle", 16, 5),
-                   (1, 5, 2, 64, 300, [290], 600, 599), (1, 5, 2, 64, 300, [290], 600, 200), (2, 3, 2, 128, 40, [3, 40], 600, 200)]
+                   (1, 5, 2, 64, 300, [290], 600, 599), (1, 5, 2, 64, 300, [290], 600, 200), (2, 3, 2, 128, 40, [3, 40], 600, 200),
+                   (1, 3, 2, 128, 40, [40], 130, [62, 63, 64]), (1, 3, 2, 128, 40, [40], 260, [62, 63, 64]),
+                   (1, 3, 2, 64, 40, [40], 130, [126, 127, 128]), (1, 3, 2, 64, 40, [40], 258, [126, 127, 128])]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -184,22 +188,25 @@ def test_attn_decode_beams_per_element(O, dtype, Bp, nb, H, D, Pmax, pre_lens, G
     the 16-bit kernel on the exactly cast dequantised cache.  Every suffix slot no beam references and every prefix row at or beyond
     pre_lens holds NaN (fp8: 0x7F bytes and NaN scales): one row too many, or the wrong beam's row, fails loudly."""
     psplits, ssplits = O.attn_decode_beams_splits(Bp, nb, H, Pmax, G)
-    assert psplits >= 1 and ssplits == (3 if G == 600 else 1) and psplits + ssplits <= 32  # (ceil(G / 256) suffix splits, 4 at the most)
+    assert psplits >= 1 and ssplits == min((G + 255) // 256, 4) and psplits + ssplits <= 32  # (ceil(G / 256) suffix splits, 4 at the most)
     if pre_lens == "straddle":
         c = (Pmax + psplits - 1) // psplits
         assert psplits > 2 and c + 1 <= Pmax
         pre_lens = [c, c + 1]
-    d, n, sl = H * D, Bp * nb, gen + 1
+    d, n = H * D, Bp * nb
+    gens = gen if isinstance(gen, list) else [gen] * n  # the suffix keys of beam m are g <= gens[m]
+    assert len(gens) == n
     q = rnd_rows(n * H, D, dtype, seed=5, lo=0.5, hi=2.0).view(n, d).to(dev())
     g = torch.Generator().manual_seed(17)
     anc = torch.randint(0, nb, (Bp, nb, G), generator=g) + nb * torch.arange(Bp)[:, None, None]
     anc = anc.view(n, G).to(torch.int32)
-    anc[:, gen] = torch.arange(n, dtype=torch.int32)  # the new key is the beam's own
-    if nb > 1 and gen > 0:
+    anc[torch.arange(n), torch.tensor(gens)] = torch.arange(n, dtype=torch.int32)  # the new key is the beam's own
+    if nb > 1 and min(gens) > 0:
         anc[1::nb, 0] = anc[0::nb, 0]                 # two beams of every prompt share an ancestor row
         assert int(anc[1, 0]) == int(anc[0, 0])
     used = torch.zeros(n, G, dtype=torch.bool)
-    used[anc[:, :sl].long(), torch.arange(sl)[None, :]] = True
+    for m in range(n):
+        used[anc[m, :gens[m] + 1].long(), torch.arange(gens[m] + 1)] = True
     valid = torch.arange(Pmax)[None, :] < torch.tensor(pre_lens)[:, None]
     fmt = {}
     for name, rows, S, keep, seeds in (("pre", Bp, Pmax, valid, (3, 4)), ("suf", n, G, used, (8, 9))):
@@ -215,7 +222,7 @@ def test_attn_decode_beams_per_element(O, dtype, Bp, nb, H, D, Pmax, pre_lens, G
             fmt[name + kv] = (c8.to(dev()), cs.to(dev()), x16.to(dev()), x64.to(dev()))
     rows = []
     for m in range(n):
-        p = m // nb
+        p, sl = m // nb, gens[m] + 1
         pick = anc[m, :sl].long().to(dev())
         k64 = torch.cat([fmt["prek"][3][p, :pre_lens[p]], fmt["sufk"][3][pick, torch.arange(sl, device=dev())]])
         v64 = torch.cat([fmt["prev"][3][p, :pre_lens[p]], fmt["sufv"][3][pick, torch.arange(sl, device=dev())]])
@@ -224,7 +231,7 @@ def test_attn_decode_beams_per_element(O, dtype, Bp, nb, H, D, Pmax, pre_lens, G
         rows.append(N.attention_decode(qm, k64, v64, k64.shape[0]) + (N.attention_decode(qm, k64, v64, k64.shape[0], model=dtype),))
     ref, Bc, mod = (torch.stack([r[i] for r in rows]) for i in range(3))
     pl = torch.tensor(pre_lens, dtype=torch.int32, device=dev())
-    slens = torch.full((n,), sl, dtype=torch.int32, device=dev())
+    slens = torch.tensor([g_ + 1 for g_ in gens], dtype=torch.int32, device=dev())
     anc_d = anc.to(dev())
     tag = f"Bp={Bp} nb={nb} D={D} Pmax={Pmax} pre_lens={pre_lens} G={G} gen={gen} splits={psplits}+{ssplits}"
     o = O.attn_decode_beams_kv8(q, fmt["prek"][0], fmt["prev"][0], fmt["prek"][1], fmt["prev"][1], pl, fmt["sufk"][0], fmt["sufv"][0],

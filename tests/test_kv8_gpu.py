@@ -125,7 +125,11 @@ def _chunk(B, H, Smax):
 
 
 # SHAPES, and (6 splits of 117 keys) lengths that are whole chunks of the split plan / whole chunks plus one key
-ATTN_CASES = SHAPES + [(2, 4, 64, 700, "chunk"), (2, 4, 64, 700, "chunk+1")]
+# lengths around one unrolled iteration of the one-query kernel (256 * 8 / D key slices x 4 rows in flight with the 16-bit cache, x 8 with
+# the fp8 cache: 64 and 128 keys at D = 128, 128 and 256 at D = 64), and fewer keys than key slices (16 at D = 128, 32 at D = 64)
+ATTN_CASES = SHAPES + [(2, 4, 64, 700, "chunk"), (2, 4, 64, 700, "chunk+1"),
+                       (3, 2, 128, 130, [63, 64, 65]), (3, 2, 128, 130, [127, 128, 129]), (3, 2, 64, 260, [127, 128, 129]),
+                       (3, 2, 64, 260, [255, 256, 257]), (3, 2, 128, 40, [1, 5, 15]), (3, 2, 64, 40, [1, 5, 31])]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -154,8 +158,9 @@ def test_attn_decode_kv8_per_element(ops, dtype, B, H, D, Smax, lens):
     for split in (True, False):
         o = ops.attn_decode_kv8(q, k8, v8, ks, vs, lens_t, H, D, split_kv=split)
         hold(f"attention decode kv8 {'split-KV' if split else 'one block'} {tag}", dtype, o.view(B, H, D), ref, Bc, mod)
-    o16 = ops.attn_decode(q, k16.view(B, Smax, d), v16.view(B, Smax, d), lens_t, H, D)
-    hold(f"attention decode 16-bit on the dequantised cache {tag}", dtype, o16.view(B, H, D), ref, Bc, mod)
+    for split in (True, False):
+        o16 = ops.attn_decode(q, k16.view(B, Smax, d), v16.view(B, Smax, d), lens_t, H, D, split_kv=split)
+        hold(f"attention decode 16-bit on the dequantised cache {'split-KV' if split else 'one block'} {tag}", dtype, o16.view(B, H, D), ref, Bc, mod)
 
 
 # ---- engine and generate() -----------------------------------------------------------------------------------------------------------------
