@@ -656,6 +656,33 @@ int mh_adamw_split(void* p, void* lo, const void* g, float* m, float* v, int64_t
                    float wd, int step, float gscale, const float* gscale_dev, int dt, void* stream);
 int mh_adamw_sr(void* p, const void* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                 float wd, int step, float gscale, const float* gscale_dev, uint64_t key, int64_t index0, int dt, void* stream);
+/* The same update on COMPACT moments: 3 + 1/128 bytes of optimizer state per parameter instead of 8, and 12 bytes moved per parameter
+ * instead of 22.  The storage format (blocks are 128 consecutive elements of the caller's whole buffer, block b = [128 b, 128 b + 128);
+ * a launch starts on a block boundary and its last block may be partial):
+ *   m:  one OCP e4m3 byte per element, m8 [n], and one scale byte per block, mscale [ceil(n / 128)] = e + 127, under mh_kv8_fill's rule:
+ *       e is the smallest integer with max|m'| * 2^-e <= 448 over the block's valid elements, e >= -126, e = 0 for an all-zero block.
+ *       Nothing saturates and code * 2^e is exact in fp32 (for max|m'| <= 448 * 2^119; beyond, a successor can be 2^128).  The byte is chosen by stochastic rounding of y = |m'| * 2^-e: lo the largest
+ *       e4m3 magnitude <= y, hi its successor on the e4m3 grid, t = (y - lo) / (hi - lo); hi is stored when r_m < 65536 t, else lo, with
+ *       the sign bit of m'.  P(up) = ceil(65536 t) / 65536, in [t, t + 2^-16).
+ *   v:  bf16, v16 [n], stored as (u + r_v) >> 16 on the fp32 bits u of v' (mh_adamw_sr's store: P(up) is exactly the dropped fraction).
+ *       Round to nearest would not do: one step changes v by at most 1 - beta2 relative, below bf16's half spacing, and v would never decay.
+ *   random fields: element j = index0 + i takes the 32-bit half (j & 1) of splitmix64(state_key + (j >> 1)) (one hash serves two elements);
+ *       r_v is that half's low 16 bits, r_m its high 16.  Results do not depend on how the buffer is cut into launches.
+ * Both decodes are exact; the update runs on the decoded fp32 moments exactly as above, p (and lo) are computed from the UNROUNDED m', v', and
+ * m', v' are then stored: given the same decoded moments, p' and lo' are bit-identical to mh_adamw / mh_adamw_clip / mh_adamw_split /
+ * mh_adamw_sr.
+ * mh_adamw_compact: p_mode 0 = round to nearest (mh_adamw), 1 = split master (lo as in mh_adamw_split; NULL otherwise), 2 = stochastic
+ *   (p_key, index0 as mh_adamw_sr's key, index0).  dt must be MH_BF16 (MH_ERR_DTYPE); a null pointer (gscale_dev, and lo outside mode 1,
+ *   excepted), n <= 0, step <= 0, a p_mode outside 0..2 or an index0 that is negative or no multiple of 128 is MH_ERR_ARG, and nothing is
+ *   launched.  m8, v16, p, g (lo) point at the block's first element, mscale at its scale byte.  Wide accesses when p, g, v16 (lo) are
+ *   16-byte and m8 8-byte aligned, element by element otherwise.  Elements beyond n and scale bytes beyond ceil(n / 128) are not written.
+ * mh_adamw_states_pack / _unpack: fp32 moments -> the compact form (the same store rule) and back (exact): tests, tooling, FusedAdamW.moments(). */
+int mh_adamw_compact(void* p, void* lo, const void* g, void* m8, void* mscale, void* v16, int64_t n, float lr, float beta1, float beta2,
+                     float eps, float wd, int step, float gscale, const float* gscale_dev, int p_mode, uint64_t p_key, uint64_t state_key,
+                     int64_t index0, int dt, void* stream);
+int mh_adamw_states_pack(const float* m32, const float* v32, void* m8, void* mscale, void* v16, int64_t n, uint64_t state_key, int64_t index0,
+                         void* stream);
+int mh_adamw_states_unpack(const void* m8, const void* mscale, const void* v16, float* m32, float* v32, int64_t n, void* stream);
 /* out[0] += sum(g^2) over n elements (fp32 atomic; zero it first) */
 int mh_sumsq(const void* g, int64_t n, float* out, int dt, void* stream);
 /* Deterministic form (fixed grid, fixed-order two-stage sum; 16-byte loads): out[0] = sum g^2; `partial` = 2048 floats

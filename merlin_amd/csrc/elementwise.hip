@@ -363,6 +363,196 @@ __global__ __launch_bounds__(256) void adamw_store_k(uint16_t* __restrict__ p, c
   }
 }
 
+// ---- AdamW on COMPACT moments (bf16 only): m as e4m3 bytes with one power-of-two scale byte per 128-element block, v as bf16, both stored
+// with stochastic rounding (the format and its random fields: include/merlin_hip.h, mh_adamw_compact).  A second policy axis beside Store:
+// the moments are decoded to fp32 (exact), adamw_value and the Store policy run on them as in adamw_store_k, and the unrounded m', v' are
+// then stored in the compact form.  16 lanes of 8 elements own one block; its maximum is a 16-lane shuffle reduction.
+struct StoreNearest {  // adamw_k's store (round to nearest even) as a policy
+  static constexpr bool HAS_LO = false;
+  __device__ __forceinline__ float load(uint32_t p, uint32_t) const { return __uint_as_float(p << 16); }
+  __device__ __forceinline__ uint32_t store(float x, uint32_t, uint32_t&) const { return f32_to_bf16_bits(x); }
+  __device__ __forceinline__ void fields8(int64_t, uint32_t*) const {}
+};
+
+// 8 consecutive 16-bit / 8-bit elements of one lane as packed words: one wide access, or (a misaligned buffer, the lanes of a partial last
+// block) the first cnt elements one by one, the rest zero / untouched
+__device__ __forceinline__ uint4 ld8_u16(const uint16_t* q, int cnt, bool wide) {
+  if (wide) return *(const uint4*)q;
+  uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < cnt) w[k >> 1] |= (uint32_t)q[k] << (16 * (k & 1));
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void st8_u16(uint16_t* q, const uint32_t* h, int cnt, bool wide) {  // h: 8 values, 16 bits each
+  if (wide) {
+    *(uint4*)q = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < cnt) q[k] = (uint16_t)h[k];
+}
+__device__ __forceinline__ uint2 ld8_u8(const uint8_t* q, int cnt, bool wide) {
+  if (wide) return *(const uint2*)q;
+  uint32_t w[2] = {0, 0};
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < cnt) w[k >> 2] |= (uint32_t)q[k] << (8 * (k & 3));
+  return make_uint2(w[0], w[1]);
+}
+__device__ __forceinline__ void st8_u8(uint8_t* q, uint2 w, int cnt, bool wide) {
+  if (wide) {
+    *(uint2*)q = w;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < cnt) q[k] = (uint8_t)((k < 4 ? w.x : w.y) >> (8 * (k & 3)));
+}
+
+// the block's scale exponent, by the rule of the fp8 KV cache (decode.hip, kv8_exp; restated here because mh_common.h is part of the GEMM
+// sources' stamp): the smallest e with amax * 2^-e <= 448 (amax = m * 2^ex, m in [0.5, 1): e = ex - 9 if m <= 0.875 else ex - 8), e >= -126,
+// 0 for an all-zero block
+__device__ __forceinline__ int compact_exp(float amax) {  // amax >= 0, finite
+  const uint32_t bits = __float_as_uint(amax);
+  const int ef = (int)(bits >> 23);
+  if (ef == 0) return bits ? -126 : 0;  // an fp32 subnormal maximum: e < -126 clamps
+  return max(ef - 126 - ((bits & 0x7fffffu) <= 0x600000u ? 9 : 8), -126);
+}
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }  // e in [-126, 127]
+
+// 8 e4m3 bytes x the block's scale byte (e + 127; 2^e as fp32 bits) -> fp32, exact
+__device__ __forceinline__ void compact_m_decode8(uint2 codes, uint32_t scale_byte, float* m) {
+  typedef float f2_ __attribute__((ext_vector_type(2)));
+  const float sc = __uint_as_float(scale_byte << 23);
+  const f2_ a = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes.x, true);
+  const f2_ c = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)codes.y, true);
+  m[0] = a[0] * sc; m[1] = a[1] * sc; m[2] = b[0] * sc; m[3] = b[1] * sc;
+  m[4] = c[0] * sc; m[5] = c[1] * sc; m[6] = d[0] * sc; m[7] = d[1] * sc;
+}
+// e4m3 magnitude byte of y in [0, 448], rounded up to the next grid point when r < 65536 t, t = (y - lo) / (hi - lo).  Normal range
+// (y >= 2^-6): the byte is the fp32 exponent and top three mantissa bits rebased, t the 20 dropped bits; below, the grid is k * 2^-9.
+__device__ __forceinline__ uint32_t e4m3_sr(float y, uint32_t r) {
+  const uint32_t u = __float_as_uint(y);
+  const float s = y * 512.f, k = floorf(s);
+  const uint32_t normal = (u >> 20) - (120u << 3) + ((r << 4) < (u & 0xfffffu) ? 1u : 0u);
+  const uint32_t sub = (uint32_t)k + ((float)r < (s - k) * 65536.f ? 1u : 0u);
+  return y >= 0.015625f ? normal : sub;
+}
+// The compact store of one lane's 8 new moments (the first cnt are real) at arena index j0 (a multiple of 8) of a 128-element block held by
+// 16 adjacent lanes: -> the e4m3 bytes, the bf16 halves and the block's scale byte.  One splitmix64 serves two elements.
+__device__ __forceinline__ void compact_store8(const float* m, const float* v, int cnt, uint64_t key, uint64_t j0, uint2& codes, uint32_t* vh,
+                                               uint32_t& scale_byte) {
+  float amax = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < cnt) amax = fmaxf(amax, fabsf(m[k]));
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 16));
+  const int e = compact_exp(amax);
+  const float inv = pow2f(-e);  // e <= 120 for any fp32 maximum: 2^-e is a normal number
+  scale_byte = (uint32_t)(e + 127);
+  uint32_t c[8];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint64_t z = splitmix64(key + (j0 >> 1) + (uint64_t)q);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = 2 * q + h;
+      const uint32_t half = (uint32_t)(z >> (32 * h)), mu = __float_as_uint(m[k]), vu = __float_as_uint(v[k]);
+      c[k] = e4m3_sr(fabsf(m[k]) * inv, half >> 16) | ((mu >> 24) & 0x80u);
+      vh[k] = ((vu & 0x7f800000u) == 0x7f800000u ? vu : vu + (half & 0xffffu)) >> 16;
+    }
+  }
+  codes = make_uint2(c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24));
+}
+
+// n elements = ceil(n / 128) blocks, every block's 16 lanes in the loop together (the last block's tail lanes hold cnt < 8 elements, down
+// to none: they take part in the maximum with nothing and store nothing).  wide: every pointer is aligned for the 16- and 8-byte accesses.
+template <class Store>
+__global__ __launch_bounds__(256) void adamw_compact_k(uint16_t* __restrict__ p, const uint16_t* __restrict__ g, uint8_t* __restrict__ m8,
+                                                       uint8_t* __restrict__ mscale, uint16_t* __restrict__ v16, int64_t n, bool wide, float lr,
+                                                       float b1, float b2, float eps, float wd, float bc1, float bc2, float gscale,
+                                                       const float* __restrict__ gscale_dev, Store st, uint64_t state_key, int64_t index0) {
+  if (gscale_dev) gscale *= *gscale_dev;
+  const float decay = fmaf(-lr, wd, 1.f);
+  const int64_t ngroup = ((n + 127) >> 7) << 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ngroup; i += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = i << 3, left = n - i0;
+    const int cnt = left >= 8 ? 8 : left > 0 ? (int)left : 0;
+    const bool w = wide && cnt == 8;
+    const uint4 pw = ld8_u16(p + i0, cnt, w), gw = ld8_u16(g + i0, cnt, w), vw = ld8_u16(v16 + i0, cnt, w);
+    uint4 lw = make_uint4(0, 0, 0, 0);
+    if constexpr (Store::HAS_LO) lw = ld8_u16(st.lo + i0, cnt, w);
+    const uint2 mw = ld8_u8(m8 + i0, cnt, w);
+    const uint32_t pb[4] = {pw.x, pw.y, pw.z, pw.w}, lb[4] = {lw.x, lw.y, lw.z, lw.w};
+    float gf[8], mf[8], vf[8];
+    unpack8<MH_BF16>(gw, gf);
+    unpack8<MH_BF16>(vw, vf);
+    compact_m_decode8(mw, mscale[i >> 4], mf);
+    uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph[8], pl[8];
+    st.fields8(i0, r);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int sh = 16 * (k & 1);
+      const float pi = adamw_value(st.load((pb[k >> 1] >> sh) & 0xffffu, (lb[k >> 1] >> sh) & 0xffffu), gf[k] * gscale, mf[k], vf[k], lr, b1, b2,
+                                   eps, decay, bc1, bc2);
+      pl[k] = 0;
+      ph[k] = st.store(pi, r[k], pl[k]) & 0xffffu;
+    }
+    uint2 codes;
+    uint32_t vh[8], sb;
+    compact_store8(mf, vf, cnt, state_key, (uint64_t)(index0 + i0), codes, vh, sb);
+    st8_u16(p + i0, ph, cnt, w);
+    if constexpr (Store::HAS_LO) st8_u16(st.lo + i0, pl, cnt, w);
+    st8_u8(m8 + i0, codes, cnt, w);
+    st8_u16(v16 + i0, vh, cnt, w);
+    if ((i & 15) == 0) mscale[i >> 4] = (uint8_t)sb;
+  }
+}
+
+// fp32 moments -> the compact form (the store of adamw_compact_k on given values) and back (exact)
+__global__ __launch_bounds__(256) void adamw_states_pack_k(const float* __restrict__ m32, const float* __restrict__ v32, uint8_t* __restrict__ m8,
+                                                           uint8_t* __restrict__ mscale, uint16_t* __restrict__ v16, int64_t n, bool wide,
+                                                           uint64_t state_key, int64_t index0) {
+  const int64_t ngroup = ((n + 127) >> 7) << 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ngroup; i += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = i << 3, left = n - i0;
+    const int cnt = left >= 8 ? 8 : left > 0 ? (int)left : 0;
+    const bool w = wide && cnt == 8;
+    float mf[8], vf[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      mf[k] = k < cnt ? m32[i0 + k] : 0.f;
+      vf[k] = k < cnt ? v32[i0 + k] : 0.f;
+    }
+    uint2 codes;
+    uint32_t vh[8], sb;
+    compact_store8(mf, vf, cnt, state_key, (uint64_t)(index0 + i0), codes, vh, sb);
+    st8_u8(m8 + i0, codes, cnt, w);
+    st8_u16(v16 + i0, vh, cnt, w);
+    if ((i & 15) == 0) mscale[i >> 4] = (uint8_t)sb;
+  }
+}
+__global__ __launch_bounds__(256) void adamw_states_unpack_k(const uint8_t* __restrict__ m8, const uint8_t* __restrict__ mscale,
+                                                             const uint16_t* __restrict__ v16, float* __restrict__ m32, float* __restrict__ v32,
+                                                             int64_t n) {
+  const int64_t ngroup = (n + 7) >> 3;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ngroup; i += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = i << 3, left = n - i0;
+    const int cnt = left >= 8 ? 8 : (int)left;
+    float mf[8];
+    compact_m_decode8(ld8_u8(m8 + i0, cnt, false), mscale[i >> 4], mf);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (k < cnt) {
+        m32[i0 + k] = mf[k];
+        v32[i0 + k] = bf16_bits_to_f32(v16[i0 + k]);
+      }
+  }
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void sumsq_k(const uint16_t* __restrict__ g, int64_t n, float* __restrict__ out) {
   float s = 0.f;
@@ -527,6 +717,44 @@ extern "C" int mh_adamw_sr(void* p, const void* g, float* m, float* v, int64_t n
   if (dt != MH_BF16) return MH_ERR_DTYPE;
   const bool vec = aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
   adamw_store_go(p, g, m, v, n, vec, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, StoreSr{key, index0}, stream);
+  MH_LAUNCH_CHECK();
+}
+template <class Store>
+static void adamw_compact_go(void* p, const void* g, void* m8, void* mscale, void* v16, int64_t n, bool wide, float lr, float beta1, float beta2,
+                             float eps, float wd, int step, float gscale, const float* gscale_dev, Store st, uint64_t state_key, int64_t index0,
+                             void* stream) {
+  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adamw_compact_k<Store>, dim3(grid_for(((n + 127) >> 7) << 4)), dim3(256), 0, as_stream(stream), (uint16_t*)p,
+                     (const uint16_t*)g, (uint8_t*)m8, (uint8_t*)mscale, (uint16_t*)v16, n, wide, lr, beta1, beta2, eps, wd, bc1, bc2, gscale,
+                     gscale_dev, st, state_key, index0);
+}
+static inline bool aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }
+extern "C" int mh_adamw_compact(void* p, void* lo, const void* g, void* m8, void* mscale, void* v16, int64_t n, float lr, float beta1, float beta2,
+                                float eps, float wd, int step, float gscale, const float* gscale_dev, int p_mode, uint64_t p_key,
+                                uint64_t state_key, int64_t index0, int dt, void* stream) {
+  if (!p || !g || !m8 || !mscale || !v16 || n <= 0 || step <= 0 || index0 < 0 || (index0 & 127) || p_mode < 0 || p_mode > 2) return MH_ERR_ARG;
+  if (p_mode == 1 && !lo) return MH_ERR_ARG;
+  if (dt != MH_BF16) return MH_ERR_DTYPE;
+  const bool wide = aligned16(p) && aligned16(g) && aligned16(v16) && aligned8(m8) && (p_mode != 1 || aligned16(lo));
+  auto go = [&](auto st) {
+    adamw_compact_go(p, g, m8, mscale, v16, n, wide, lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, st, state_key, index0, stream);
+  };
+  if (p_mode == 0) go(StoreNearest{});
+  else if (p_mode == 1) go(StoreSplit{(uint16_t*)lo});
+  else go(StoreSr{p_key, index0});
+  MH_LAUNCH_CHECK();
+}
+extern "C" int mh_adamw_states_pack(const float* m32, const float* v32, void* m8, void* mscale, void* v16, int64_t n, uint64_t state_key,
+                                    int64_t index0, void* stream) {
+  if (!m32 || !v32 || !m8 || !mscale || !v16 || n <= 0 || index0 < 0 || (index0 & 127)) return MH_ERR_ARG;
+  hipLaunchKernelGGL(adamw_states_pack_k, dim3(grid_for(((n + 127) >> 7) << 4)), dim3(256), 0, as_stream(stream), m32, v32, (uint8_t*)m8,
+                     (uint8_t*)mscale, (uint16_t*)v16, n, aligned8(m8) && aligned16(v16), state_key, index0);
+  MH_LAUNCH_CHECK();
+}
+extern "C" int mh_adamw_states_unpack(const void* m8, const void* mscale, const void* v16, float* m32, float* v32, int64_t n, void* stream) {
+  if (!m8 || !mscale || !v16 || !m32 || !v32 || n <= 0) return MH_ERR_ARG;
+  hipLaunchKernelGGL(adamw_states_unpack_k, dim3(grid_for((n + 7) >> 3)), dim3(256), 0, as_stream(stream), (const uint8_t*)m8,
+                     (const uint8_t*)mscale, (const uint16_t*)v16, m32, v32, n);
   MH_LAUNCH_CHECK();
 }
 namespace {

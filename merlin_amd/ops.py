@@ -1489,6 +1489,32 @@ def adamw_sr_(param, grad, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0, gs
     L.call("mh_adamw_sr", param, grad, m, v, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, key, index0, dt_of(param), _stream())
 
 
+P_MODES = {"nearest": 0, "split": 1, "stochastic": 2}  # mh_adamw_compact's p_mode
+
+
+def adamw_compact_(param, lo, grad, m8, mscale, v16, lr, beta1, beta2, eps, wd, step, gscale=1.0, gscale_dev=None, p_mode=0, p_key=0, state_key=0,
+                   index0=0):
+    """AdamW on compact moments (include/merlin_hip.h): m8 e4m3 bytes [n] with one scale byte per 128 elements in mscale, v16 bf16 [n], all
+    rewritten with stochastic rounding drawn from (state_key, index0 + i); param (and lo, p_mode 1) as adamw_ / adamw_split_ / adamw_sr_ store
+    it.  index0 is a multiple of 128 and the slices start on that block."""
+    L.call("mh_adamw_compact", param, lo, grad, m8, mscale, v16, param.numel(), lr, beta1, beta2, eps, wd, step, gscale, gscale_dev, p_mode, p_key,
+           state_key, index0, dt_of(param), _stream())
+
+
+def adamw_states_pack(m32, v32, m8, mscale, v16, state_key=0, index0=0):
+    """fp32 moments -> the compact form, by the store rule of adamw_compact_."""
+    L.call("mh_adamw_states_pack", m32, v32, m8, mscale, v16, m32.numel(), state_key, index0, _stream())
+
+
+def adamw_states_unpack(m8, mscale, v16, m32=None, v32=None):
+    """Compact moments -> fp32 (m, v), exact."""
+    n = m8.numel()
+    m32 = torch.empty(n, dtype=torch.float32, device=m8.device) if m32 is None else m32
+    v32 = torch.empty(n, dtype=torch.float32, device=m8.device) if v32 is None else v32
+    L.call("mh_adamw_states_unpack", m8, mscale, v16, m32, v32, n, _stream())
+    return m32, v32
+
+
 def clip_scale(sumsq_t, gscale, max_norm, out2):
     L.call("mh_clip_scale", sumsq_t, gscale, max_norm, out2, _stream())
 

@@ -20,6 +20,18 @@ How the new value of a parameter goes back into the bf16 arena is `FusedAdamW(ro
   "stochastic"  no extra state: the store rounds up with a probability equal to the dropped fraction (unbiased), drawn from a hash of
                 (seed, step, arena index), so every data-parallel rank computes the same bits from the same gradients.  bf16 only.
 
+How the moments are kept is `FusedAdamW(states=...)`, independent of `rounding`:
+
+  "fp32"        (default) m and v as two fp32 vectors shaped like the arena: 8 bytes per parameter (56 GB for the 7B arena), 22 bytes moved
+                per parameter and step.
+  "compact"     m as OCP e4m3 bytes with one power-of-two scale byte per 128-element block, v as bf16, both written with stochastic
+                rounding from a hash of (seed, step, arena index): 3 + 1/128 bytes per parameter (21 GB), 12 bytes moved.  The format is
+                include/merlin_hip.h's (mh_adamw_compact).  v is not rounded to nearest because one step changes it by at most
+                1 - beta2 relative, below half a bf16 spacing: it would never decay.  The update itself runs on the decoded fp32 moments
+                and the unrounded new ones, so only the stored moments carry the format's noise; simulated on synthetic gradient streams
+                (tests/adamw_compact_ref.py) a step deviates by about 8 % relative RMS from fp32 moments and 400 accumulated steps by about
+                1.5 %.  bf16 only.
+
 Not covered: optimizer-state save and restore (FusedAdamW has none for m and v either).  Resuming with lo = 0 restarts from the stored bf16
 weights."""
 from __future__ import annotations
@@ -33,6 +45,8 @@ from . import ops as O
 from .weights import MASK64, splitmix64_scalar
 
 ROUNDINGS = ("nearest", "split", "stochastic")
+STATES = ("fp32", "compact")
+BLOCK = 128  # elements per scale byte of the compact m; arena offsets are multiples of it (arena.ALIGN)
 
 
 # ---- layer-wise learning-rate decay (mmgpt/utils/llrd_utils.py:4-23), selected by --llrd / --llm_llrd (trainer.py:56-61) ----
@@ -78,20 +92,25 @@ def cosine_with_warmup(step: int, total_steps: int, warmup_ratio: float = 0.0, n
 
 
 class FusedAdamW:
-    def __init__(self, engine, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lr_scale_fn=None, rounding="nearest", seed=0):
-        """rounding: how p is stored ("nearest", "split", "stochastic": see the module docstring); seed: of the stochastic store.  No state is
-        saved or restored: resuming a "split" run starts from the stored bf16 weights (lo = 0)."""
+    def __init__(self, engine, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, lr_scale_fn=None, rounding="nearest", seed=0,
+                 states="fp32"):
+        """rounding: how p is stored ("nearest", "split", "stochastic"); states: how m and v are kept ("fp32", "compact"): see the module
+        docstring for both; seed: of the stochastic stores.  No state is saved or restored: resuming a "split" run starts from the stored
+        bf16 weights (lo = 0), and m, v start from zero."""
         if rounding not in ROUNDINGS:
             raise ValueError(f"rounding={rounding!r} is not one of {ROUNDINGS}")
+        if states not in STATES:
+            raise ValueError(f"states={states!r} is not one of {STATES}")
         self.engine = engine
-        self.rounding, self.seed = rounding, int(seed)
+        self.rounding, self.states, self.seed = rounding, states, int(seed)
         self.lo = None        # "split": int16 low halves of the fp32 masters, shaped like the arena
         self.reseeds = 0      # "split": how often lo was dropped because the weights changed behind the optimizer
         self._lo_for = None   # (engine.weight_version, address of the arena's flat) that lo belongs to
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.lr_scale_fn = lr_scale_fn  # name -> multiplier (layer-wise lr decay, llrd_utils.py:4-79)
         self.step_count = 0
-        self.m = self.v = None
+        self.m = self.v = None                        # states="fp32"
+        self.m8 = self.mscale = self.v16 = None       # states="compact": e4m3 bytes, one scale byte per BLOCK elements, bf16
         self._runs = None
         self._flat_id = None
         self._clip = None
@@ -99,10 +118,17 @@ class FusedAdamW:
 
     def _build(self):
         A = self.engine.ensure_arena()
+        if self.states == "compact" and A.flat.dtype != torch.bfloat16:
+            raise ValueError(f"states='compact' needs bfloat16 parameters, got {A.flat.dtype}: mh_adamw_compact is bf16 only")
         sig = (A.flat.data_ptr(), tuple(p.requires_grad for p in A.params.values()))  # freeze / unfreeze rebuilds the runs
         if self._flat_id == sig and self._runs is not None:
             return A
-        if self.m is None or self.m.numel() != A.total or self.m.device != A.flat.device:
+        if self.states == "compact":
+            if self.m8 is None or self.m8.numel() != A.total or self.m8.device != A.flat.device:
+                self.m8 = torch.zeros(A.total, dtype=torch.uint8, device=A.flat.device)
+                self.mscale = torch.full((A.total // BLOCK,), 127, dtype=torch.uint8, device=A.flat.device)  # an all-zero block: e = 0
+                self.v16 = torch.zeros(A.total, dtype=torch.bfloat16, device=A.flat.device)
+        elif self.m is None or self.m.numel() != A.total or self.m.device != A.flat.device:
             self.m = torch.zeros(A.total, dtype=torch.float32, device=A.flat.device)
             self.v = torch.zeros(A.total, dtype=torch.float32, device=A.flat.device)
         hp = per_param_hparams(A.params.items(), 1.0, self.weight_decay, self.lr_scale_fn)  # lr as a multiplier of self.lr
@@ -137,6 +163,7 @@ class FusedAdamW:
         if self.rounding == "split":
             self._ensure_lo(A)
         key = self.sr_key(self.step_count) if self.rounding == "stochastic" else None
+        skey = self.state_key(self.step_count) if self.states == "compact" else None
         b1, b2 = self.betas
         clip = None
         if max_grad_norm is not None and max_grad_norm > 0:
@@ -145,6 +172,11 @@ class FusedAdamW:
             O.clip_scale(self.grad_norm_sq(), grad_scale, max_grad_norm, self._clip)
             clip = self._clip
         for off, num, sc, wd in self._runs:
+            if self.states == "compact":
+                O.adamw_compact_(A.flat[off: off + num], self.lo[off: off + num] if self.rounding == "split" else None, A.gflat[off: off + num],
+                                 self.m8[off: off + num], self.mscale[off // BLOCK:], self.v16[off: off + num], self.lr * sc * lr_mult, b1, b2,
+                                 self.eps, wd, self.step_count, grad_scale, clip, O.P_MODES[self.rounding], key or 0, skey, off)
+                continue
             args = (A.flat[off: off + num], A.gflat[off: off + num], self.m[off: off + num], self.v[off: off + num],
                     self.lr * sc * lr_mult, b1, b2, self.eps, wd, self.step_count, grad_scale)
             if self.rounding == "split":
@@ -162,6 +194,25 @@ class FusedAdamW:
     def sr_key(self, step: int) -> int:
         """The stochastic store's hash key of one step."""
         return splitmix64_scalar((self.seed & MASK64) ^ ((step * 0xD1342543DE82EF95) & MASK64))
+
+    def state_key(self, step: int) -> int:
+        """The compact moments' hash key of one step (another stream than sr_key's)."""
+        return splitmix64_scalar((self.seed & MASK64) ^ ((step * 0xA0761D6478BD642F) & MASK64))
+
+    def state_bytes(self) -> int:
+        """Bytes held in moment buffers (0 before the first step builds them)."""
+        return sum(t.numel() * t.element_size() for t in (self.m, self.v, self.m8, self.mscale, self.v16) if t is not None)
+
+    def moments(self, name):
+        """fp32 (m, v) of one parameter, shaped like it: views of the fp32 buffers, or decoded copies of the compact ones (exact).  For tests
+        and checkpoint tooling, not the hot path."""
+        A = self._build()
+        p, off = A.params[name], A.offset[name]
+        if self.states == "compact":
+            m, v = O.adamw_states_unpack(self.m8[off: off + p.numel()], self.mscale[off // BLOCK:], self.v16[off: off + p.numel()])
+        else:
+            m, v = self.m[off: off + p.numel()], self.v[off: off + p.numel()]
+        return m.view(p.shape), v.view(p.shape)
 
     def _weights_id(self, A):
         return (self.engine.weight_version, A.flat.data_ptr())
