@@ -267,7 +267,11 @@ int mh_attn_fwd2(const void* q, int64_t ldq, const void* k, int64_t ldk, const v
  * (profiles/r03_attn_fwd_pingpong.txt, profiles/r04_attn_fwd_wave64.txt). */
 void mh_attn_fwd_pingpong(int on);
 /* Backward: dq/dk/dv are [B*S, H, D] views with their own row strides; no workspace and no operand re-layout passes
- * (transposed operands come from LDS transpose-reads); rope_cos_sin != NULL applies the inverse RoPE to dq, dk.  `delta`: ZERO-INITIALISED fp32 scratch of 2*B*H*S_pad floats. */
+ * (transposed operands come from LDS transpose-reads); rope_cos_sin != NULL applies the inverse RoPE to dq, dk.  `delta`: fp32 scratch of 2*B*H*S_pad floats, S_pad = S rounded up
+ * to 64 ([2][B, H, S_pad]: -delta, then -lse / scale).  The kernels write rows < S only and read the pad rows [S, S_pad) of a partial last
+ * tile as accumulator start values of MASKED query rows (dS = P x (dP - delta) with P = 0): those rows must be ZERO AT EVERY CALL - a
+ * non-finite value there gives 0 x inf = NaN in dK.  A buffer zeroed once may be reused by calls of the same S; one that an earlier call
+ * of a larger S (same S_pad) wrote must be zeroed again on [S, S_pad).  Rows < S need no initial value. */
 int mh_attn_bwd2(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* o, int64_t ldo,
                  const void* dout, int64_t lddo, const float* lse, float* delta, void* dq, int64_t lddq, void* dk, int64_t lddk,
                  void* dv, int64_t lddv, const int32_t* seqlens, int B, int S, int H, int D, int causal, const float* rope_cos_sin, int dt, void* stream);

@@ -1158,15 +1158,18 @@ def attn_fwd2(q, k, v, B, S, H, D, causal, seqlens=None, out=None, lse=None):
 _delta_cache = {}
 
 
-def _delta_ws(B, H, S_pad, device):
-    """[2, B, H, S_pad] fp32 scratch of the attention backward, reused across calls (same stream => ordered).  Zeroed once:
-    the kernels only ever write rows < S, so the pad rows stay zero."""
-    key = (device, B, H, S_pad)
+def _delta_ws(B, H, S, device):
+    """[2, B, H, S_pad] fp32 scratch of the attention backward (S_pad = S rounded up to 64), reused across calls (same stream => ordered).
+    The kernels write rows < S and READ the pad rows [S, S_pad) of a partial last tile, which must be zero at every call
+    (include/merlin_hip.h, mh_attn_bwd2): a masked row's dS is P x (dP - delta) = 0 x delta, NaN where a stale delta is not finite.
+    So the buffer is zeroed once and the cache is keyed on S, not on S_pad: two lengths with the same S_pad never share one, and
+    under any key the pad rows are never written."""
+    key = (device, B, H, S)
     ws = _delta_cache.get(key)
     if ws is None:
         if len(_delta_cache) > 8:
             _delta_cache.clear()
-        ws = _delta_cache[key] = torch.zeros(2, B, H, S_pad, dtype=torch.float32, device=device)
+        ws = _delta_cache[key] = torch.zeros(2, B, H, round_up(S, 64), dtype=torch.float32, device=device)
     return ws
 
 
@@ -1224,7 +1227,7 @@ def attn_bwd2(q, k, v, o, do, lse, B, S, H, D, causal, seqlens=None, dq=None, dk
     dq = torch.empty(B * S, H * D, dtype=q.dtype, device=q.device) if dq is None else dq
     dk = torch.empty(B * S, H * D, dtype=q.dtype, device=q.device) if dk is None else dk
     dv = torch.empty(B * S, H * D, dtype=q.dtype, device=q.device) if dv is None else dv
-    delta = _delta_ws(B, H, round_up(S, 64), q.device)  # [delta | lse*log2e]
+    delta = _delta_ws(B, H, S, q.device)  # [delta | lse*log2e]
     use_spill = ATTN_BWD_SPILL if spill is None else spill
     # (the dS spill lives in attn_bwd3_kv_k = fused-kv mode 2; in modes 0 / 1 the library would run the seven-product kernels and ignore ds_ws)
     use_spill = use_spill and causal and D == 128 and S % 128 == 0 and seqlens is None and int(L.lib().mh_attn_bwd_fused_kv_mode()) == 2

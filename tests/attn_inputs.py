@@ -109,17 +109,29 @@ def _staircase(S, D, dtype, causal, n, g, step):
     return q, k
 
 
+MAX_OVERLAP = 0.4
+
+
 def _onehot(S, D, dtype, heavy, g):
     """Every distinct heavy key j gets a random unit direction g_j: k_j = a g_j, every other key small noise, q_i = a g_heavy(i) + noise with
-    scale a^2 = 54 nats (one shared key) or 56 (many: their directions overlap by up to ~0.4)."""
+    scale a^2 = 54 nats (one shared key) or 57 (many: their directions overlap by up to MAX_OVERLAP, which leaves 57 x 0.6 = 34 nats of
+    lead before the noise).  In 64 dimensions random directions of a few hundred keys overlap by up to ~0.5: a heavy direction whose
+    |cosine| with an EARLIER heavy key's exceeds MAX_OVERLAP is drawn again.  The redraws come after every other draw, so a set of
+    directions that needs none gives the inputs it always gave."""
     keys = torch.unique(heavy)
     s_heavy = 54.0 if keys.numel() == 1 else 57.0
     a = math.sqrt(s_heavy * math.sqrt(D))
     dirs = torch.randn(S, D, generator=g).double()
     dirs = dirs / dirs.norm(dim=1, keepdim=True)
     k = 0.3 * torch.randn(S, D, generator=g).double()
+    q_noise = 0.05 * torch.randn(S, D, generator=g).double()
+    kl = keys.tolist()
+    for i, j in enumerate(kl[1:], 1):
+        while float((dirs[kl[:i]] @ dirs[j]).abs().max()) > MAX_OVERLAP:
+            d = torch.randn(D, generator=g).double()
+            dirs[j] = d / d.norm()
     k[keys] = a * dirs[keys]
-    q = a * dirs[heavy] + 0.05 * torch.randn(S, D, generator=g).double()
+    q = a * dirs[heavy] + q_noise
     return q, k
 
 
@@ -273,7 +285,10 @@ def cache_family(kind, n, H, D, dtype, heavy, seed, shift=0, kv8=True, nq=None):
 
 # (B, S, H, D, causal, lens) of the prefill tests: the five-product backward applies and attn_fwd3 gets a full 256-query block plus a partial
 # one; causal with ragged lengths and partial tiles; the non-causal D = 64 form with ragged lengths
-PREFILL_SHAPES = [(1, 384, 1, 128, True, None), (2, 300, 2, 128, True, [300, 177]), (2, 200, 2, 64, False, [200, 130])]
+# ... and the other two (head dim, mask) combinations the library compiles: non-causal D = 128 (a full 256-query block plus a partial one for
+# attn_fwd3 / attn_fwd4; ragged with partial tiles) and causal D = 64 (ragged; whole tiles with two key blocks)
+PREFILL_SHAPES = [(1, 384, 1, 128, True, None), (2, 300, 2, 128, True, [300, 177]), (2, 200, 2, 64, False, [200, 130]),
+                  (1, 384, 1, 128, False, None), (2, 300, 2, 128, False, [300, 177]), (2, 200, 2, 64, True, [200, 130]), (1, 256, 1, 64, True, None)]
 
 
 def families(causal):

@@ -18,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(__file__))
 import attn_inputs as AI  # noqa: E402
 import numerics as N  # noqa: E402
-from test_componentwise_gpu import _attention_refs, _heads, _hold_heads  # noqa: E402
+from test_componentwise_gpu import _attention_refs, _heads, _hold_heads, _mask_tag  # noqa: E402
 from test_kv8_cpu import kv8_dequantize, kv8_quantize  # noqa: E402
 from test_kv8_gpu import hold  # noqa: E402
 
@@ -62,7 +62,7 @@ def run_prefill(ops, name, dtype, B, S, H, D, causal, lens):
     v, do = AI.randn16(B * S, H * D, dtype, 21).to(dev()), AI.randn16(B * S, H * D, dtype, 22).to(dev())
     lens_t = torch.tensor(lens, dtype=torch.int32, device=dev()) if lens else None
     refs, mods = _attention_refs(q, k, v, do, B, S, H, D, causal, lens, dtype)
-    tag = f"{name} S={S} D={D}{' ragged' if lens else ''}"
+    tag = f"{name} S={S} D={D}{_mask_tag(D, causal)}{' ragged' if lens else ''}"
     fwd = {}
     try:
         for form in ((0, 1, 2) if D == 128 else (0,)):

@@ -68,11 +68,20 @@ def _hold_heads(name, dtype, got, refs, mods, nm, B, S, H, D):
     return hold(name, dtype, torch.stack(_heads(got, B, S, H, D)), ref, Bc, mod)
 
 
+def _mask_tag(D, causal):
+    """The mask in a printed name, where it is not the model's own for this head dim (causal at D = 128, none at D = 64)."""
+    return "" if causal == (D == 128) else (" causal" if causal else " non-causal")
+
+
 ATTN_CASES = [
     # the causal D = 128 shapes of test_attention_fwd_bwd (with its ragged lengths), the non-causal D = 64 tower shape, the benchmark lengths
     (1, 128, 1, 128, True, None), (2, 613, 2, 128, True, None), (2, 300, 2, 128, True, [300, 177]), (2, 40, 2, 128, True, [29, 40]),
     (1, 1024, 1, 128, True, None), (3, 577, 2, 64, False, None), (1, 17, 2, 64, False, None), (2, 577, 2, 64, False, [577, 300]),
-    (1, 4096, 2, 128, True, None), (1, 8192, 1, 128, True, None), (1, 4096, 1, 128, True, [4001])]
+    (1, 4096, 2, 128, True, None), (1, 8192, 1, 128, True, None), (1, 4096, 1, 128, True, [4001]),
+    # the other two (head dim, mask) combinations the library dispatches: D = 128 without a mask (a tower with 128-wide heads), D = 64 causal
+    # (a decoder with 64-wide heads) - ragged, one row past a 128- / 256-row block, fewer rows than one tile
+    (2, 300, 2, 128, False, [300, 177]), (1, 257, 2, 128, False, None), (2, 200, 2, 64, True, [200, 130]), (1, 129, 2, 64, True, None),
+    (1, 17, 2, 64, True, None)]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -83,7 +92,7 @@ def test_attention_forward_and_backward_per_element(ops, dtype, B, S, H, D, caus
     do = rnd(B * S, H * D, dtype=dtype, seed=9)
     lens_t = torch.tensor(lens, dtype=torch.int32, device=dev()) if lens else None
     refs, mods = _attention_refs(q, k, v, do, B, S, H, D, causal, lens, dtype)
-    tag = f"S={S} D={D}{' ragged' if lens else ''}"
+    tag = f"S={S} D={D}{_mask_tag(D, causal)}{' ragged' if lens else ''}"
     o, lse = ops.attn_fwd2(q, k, v, B, S, H, D, causal, seqlens=lens_t)
     _hold_heads(f"attention o {tag}", dtype, o, refs, mods, "o", B, S, H, D)
     if D == 128:  # all three forward forms (mh_attn_fwd_pingpong 0 / 1 / 2)

@@ -284,7 +284,8 @@ def test_gemm_persistent_and_raster_group_arms_are_bit_identical(ops, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("B,S,H,D,causal,lens", [(2, 613, 2, 128, True, None), (3, 577, 2, 64, False, None), (1, 1024, 1, 128, True, None), (2, 300, 2, 128, True, [300, 177])])
+@pytest.mark.parametrize("B,S,H,D,causal,lens", [(2, 613, 2, 128, True, None), (3, 577, 2, 64, False, None), (1, 1024, 1, 128, True, None), (2, 300, 2, 128, True, [300, 177]),
+                                                    (2, 300, 2, 128, False, [300, 177]), (2, 200, 2, 64, True, [200, 130])])
 def test_attn_wide_stores_arm_is_bit_identical(ops, dtype, B, S, H, D, causal, lens):
     qkv = rnd(B * S, 3 * H * D, dtype=dtype)
     q, k, v = (qkv[:, i * H * D:(i + 1) * H * D] for i in range(3))

@@ -6,6 +6,7 @@ Tolerances (stated, per dtype): logits  max|d| / max|ref|  <= 1e-3 (fp16: BASELI
 tiny, medium and released-geometry models in the DEFAULT configuration = fp32 residual streams) / 1.5e-2 (bf16); loss rel-err <= 1e-3 / 5e-3; every parameter-gradient tensor: cosine >= 0.999
 (fp16) / 0.995 (bf16) and norm ratio within 1% / 3%.  BASELINE.json's "1e-3 rel fp16" is the fp16 row.
 """
+import dataclasses
 import os
 
 import numpy as np
@@ -42,15 +43,13 @@ def _to_dev(batch):
                 images=[im.cuda() for im in batch["images"]])
 
 
-@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("name", ["tiny_1img", "tiny_2img", "tiny_padbatch", "tiny_textonly", "tiny_conv2"])
-def test_tiny_forward_backward_parity(name, dtype):
-    from oracle import cases as C
+def _forward_backward_parity(cfg, batch, dtype, golden):
+    """Logits and loss against `golden` (a mapping with "logits" and "loss"; None: the CPU oracle's own, run here), every parameter gradient
+    against the CPU oracle's."""
     from oracle import ref_cpu as R
 
     tol = TOL[dtype]
-    cfg, batch = C.get_case(name)
-    g = np.load(os.path.join(GOLD, name + ".npz"))
+    g = golden
     model = _build(cfg, dtype)
     # weights on the device are the generator's bits
     P = R.make_params(cfg, seed=0, requires_grad=True)
@@ -59,6 +58,9 @@ def test_tiny_forward_backward_parity(name, dtype):
     for k in ("model.layers.1.mlp.up_proj.weight", "model.norm.weight", "lm_head.weight",
               "model.vision_tower.vision_tower.vision_model.encoder.layers.0.self_attn.q_proj.bias"):
         assert torch.equal(sd[k].detach().float().cpu(), P[k].detach()), k
+    loss_ref, logits_ref = R.forward(P, cfg, batch["input_ids"], batch["attention_mask"], batch["labels"], batch["images"])
+    if g is None:
+        g = {"logits": logits_ref.detach().numpy(), "loss": float(loss_ref)}
     out = model(**_to_dev(batch))
     logits = out.logits.float().cpu().numpy()
     mask = batch["attention_mask"].numpy()
@@ -69,7 +71,6 @@ def test_tiny_forward_backward_parity(name, dtype):
     # padded query rows: the flash path returns finite values (zeros from attention)
     assert np.isfinite(logits).all()
     out.loss.backward()
-    loss_ref, _ = R.forward(P, cfg, batch["input_ids"], batch["attention_mask"], batch["labels"], batch["images"])
     loss_ref.backward()
     bad = []
     for k, p in model.named_parameters():
@@ -90,6 +91,34 @@ def test_tiny_forward_backward_parity(name, dtype):
         if cos < tol["cos"] or abs(ratio - 1) > tol["norm"]:
             bad.append((k, cos, ratio))
     assert not bad, bad[:8]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("name", ["tiny_1img", "tiny_2img", "tiny_padbatch", "tiny_textonly", "tiny_conv2"])
+def test_tiny_forward_backward_parity(name, dtype):
+    from oracle import cases as C
+
+    cfg, batch = C.get_case(name)
+    _forward_backward_parity(cfg, batch, dtype, np.load(os.path.join(GOLD, name + ".npz")))
+
+
+def swapped_head_dims_cfg():
+    """The tiny config with the head dims of its two towers swapped: decoder 256 / 4 = 64 (the CAUSAL D = 64 attention kernels), tower
+    128 / 1 = 128 (the NON-causal D = 128 ones).  Same widths, so the weights, the batches and TOL are those of the tiny cases; there is no
+    golden file of the real reference for it, so the CPU oracle is run live."""
+    from oracle import cases as C
+
+    cfg = dataclasses.replace(C.tiny_cfg(), num_attention_heads=4, v_num_attention_heads=1)
+    assert cfg.hidden_size // cfg.num_attention_heads == 64 and cfg.v_hidden_size // cfg.v_num_attention_heads == 128
+    return cfg
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("name", ["tiny_1img", "tiny_padbatch"])
+def test_swapped_head_dims_forward_backward_parity(name, dtype):
+    from oracle import cases as C
+
+    _forward_backward_parity(swapped_head_dims_cfg(), C.get_case(name)[1], dtype, None)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
@@ -499,10 +528,24 @@ def test_kv_cache_decode_matches_full_recompute_and_oracle(name, dtype):
     the logits that pick every new token must agree (tolerance of the dtype), for a single prompt with an image and for
     a right-padded batch whose rows continue from their own lengths."""
     from oracle import cases as C
+
+    cfg, batch = C.get_case(name)
+    _kv_cache_decode_parity(name, cfg, batch, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("name", ["tiny_1img", "tiny_padbatch"])
+def test_swapped_head_dims_kv_cache_decode_matches_full_recompute_and_oracle(name, dtype):
+    """The same through the decoder's D = 64 and the tower's D = 128 kernels: prefill, decode steps, graph replay against eager."""
+    from oracle import cases as C
+
+    _kv_cache_decode_parity(name + " swapped head dims", swapped_head_dims_cfg(), C.get_case(name)[1], dtype)
+
+
+def _kv_cache_decode_parity(name, cfg, batch, dtype):
     from oracle import ref_cpu as R
 
     tol = TOL[dtype]["logits"] * 2
-    cfg, batch = C.get_case(name)
     model = _build(cfg, dtype)
     dev_b = _to_dev(batch)
     ids, am, images = dev_b["input_ids"], dev_b["attention_mask"], dev_b["images"]

@@ -334,7 +334,8 @@ def test_attention_bwd_five_product_form(ops, dtype, B, S, H):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("B,S,H,D,causal", [(1, 577, 2, 64, False), (2, 300, 2, 128, True), (1, 613, 1, 128, True), (1, 70, 2, 128, True), (1, 17, 2, 64, False)])
+@pytest.mark.parametrize("B,S,H,D,causal", [(1, 577, 2, 64, False), (2, 300, 2, 128, True), (1, 613, 1, 128, True), (1, 70, 2, 128, True), (1, 17, 2, 64, False),
+                                               (1, 300, 2, 128, False), (1, 70, 2, 64, True)])
 def test_attention_never_reads_rows_past_the_batch(ops, dtype, B, S, H, D, causal):
     """The K|V / Q|dO tile copies go through buffer descriptors (csrc/attn_tiles.h stage_rows_buf): rows past the end of a batch element
     - the tail of a sequence's last, partial tile - must read as zeros whatever lies behind them in memory.  q, k, v, dO here are views of a
@@ -918,7 +919,7 @@ def test_gemm_with_fused_rope_is_bit_identical_to_gemm_then_rope(ops, dtype, B, 
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("B,S,H,D,causal", [(2, 200, 2, 128, True), (1, 577, 4, 64, False), (2, 256, 3, 128, True)])
+@pytest.mark.parametrize("B,S,H,D,causal", [(2, 200, 2, 128, True), (1, 577, 4, 64, False), (2, 256, 3, 128, True), (2, 200, 2, 64, True), (1, 200, 2, 128, False)])
 def test_attention_bwd_with_fused_inverse_rope(ops, dtype, B, S, H, D, causal):
     """dq, dk rotated back inside the backward kernels' epilogues (fp32, before the single rounding) against the
     separate path: attention backward, then the stand-alone inverse RoPE on the stored 16-bit gradients."""
