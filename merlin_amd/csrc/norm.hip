@@ -651,7 +651,14 @@ extern "C" int mh_rmsnorm_fwd_q8(const void* x, const void* w, void* y, void* q,
   if (!x || !w || !y || !q || !scales || rows <= 0 || d <= 0 || (d & 7) || !aligned16(x) || !aligned16(w) || !aligned16(y) || (((uintptr_t)q) & 7u)) return MH_ERR_ARG;
   const dim3 grid((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
   if (dt != MH_BF16 && dt != MH_F16) return MH_ERR_DTYPE;
-#define Q8_GO(DT_, NCH_)                                                                                                                \
+  if (rows <= 64 && d <= 8192) {
+    // mh_rmsnorm_fwd gives these shapes to rmsnorm_fwd_row_k, whose block-wide sum of squares is formed in another order than the
+    // wave-per-row sum below: rstd can differ in its last bit and with it an element of y (and the row's scale).  The fused kernel is
+    // bit-identical to rmsnorm_fwd_k only, so a few rows take the unfused sequence itself.
+    const int rc = mh_rmsnorm_fwd(x, w, y, nullptr, rows, d, eps, dt, stream);
+    return rc != MH_OK ? rc : mh_quant_fp8_rows(y, d, q, d, scales, rows, d, dt, stream);
+  }
+#define Q8_GO(DT_, NCH_)                                                                                                               \
   hipLaunchKernelGGL((rmsnorm_fwd_q8_k<DT_, NCH_>), grid, block, 0, as_stream(stream), (const uint16_t*)x, (const uint16_t*)w, (uint16_t*)y, \
                      (uint8_t*)q, scales, rows, d, eps)
   if (dt == MH_BF16) { if (d == 4096) Q8_GO(MH_BF16, 8); else Q8_GO(MH_BF16, 0); }
@@ -711,7 +718,7 @@ extern "C" int mh_layernorm_f32_to_f32(const float* x, const void* w, const void
 
 extern "C" int mh_rmsnorm_bwd(const void* x, const void* w, const void* dy, void* dx, float* dw_partial, int rows,
                               int d, float eps, int dt, int accumulate_dx, void* stream) {
-  if (!x || !w || !dy || !dx || !dw_partial || rows <= 0 || (d & 7)) return MH_ERR_ARG;
+  if (!x || !w || !dy || !dx || !dw_partial || rows <= 0 || d <= 0 || (d & 7)) return MH_ERR_ARG;
   if (dt == MH_BF16) return launch_norm_bwd<MH_BF16, false>(x, w, dy, dx, dw_partial, nullptr, rows, d, eps, accumulate_dx, as_stream(stream));
   if (dt == MH_F16) return launch_norm_bwd<MH_F16, false>(x, w, dy, dx, dw_partial, nullptr, rows, d, eps, accumulate_dx, as_stream(stream));
   return MH_ERR_DTYPE;
@@ -719,7 +726,7 @@ extern "C" int mh_rmsnorm_bwd(const void* x, const void* w, const void* dy, void
 
 extern "C" int mh_layernorm_bwd(const void* x, const void* w, const void* dy, void* dx, float* dw_partial,
                                 float* db_partial, int rows, int d, float eps, int dt, int accumulate_dx, void* stream) {
-  if (!x || !w || !dy || !dx || !dw_partial || !db_partial || rows <= 0 || (d & 7)) return MH_ERR_ARG;
+  if (!x || !w || !dy || !dx || !dw_partial || !db_partial || rows <= 0 || d <= 0 || (d & 7)) return MH_ERR_ARG;
   if (dt == MH_BF16) return launch_norm_bwd<MH_BF16, true>(x, w, dy, dx, dw_partial, db_partial, rows, d, eps, accumulate_dx, as_stream(stream));
   if (dt == MH_F16) return launch_norm_bwd<MH_F16, true>(x, w, dy, dx, dw_partial, db_partial, rows, d, eps, accumulate_dx, as_stream(stream));
   return MH_ERR_DTYPE;

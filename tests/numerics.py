@@ -121,6 +121,42 @@ is a wrong reference or weight, which scores in the thousands (tests/test_attent
     placed sink: attention extend branches 0.773        0.656        0.762        0.685
     placed sink: attention decode beams    0.844        0.495        2.170        0.489
 
+The norm kernels' dispatch arms and row partitions (tests/norm_inputs.py with its edge rows; tests/test_norm_arms_gpu.py), measured on an MI355X
+on 2026-10-20, worst over the shapes of each check (every limit is the floor of 2, except 7.272 for the bf16 summed column-sum partials, whose
+model - torch's fp32 column sum - scores 3.636).  "partials summed" = the raw fp32 partial rows summed in fp64, held to eps = 2^-24; rstd is in
+fp32 ulps from fp64 against a bound of 4:
+
+    operation                                         bf16 model  bf16 kernel   fp16 model  fp16 kernel
+    ------------------------------------------------  ----------  -----------   ----------  -----------
+    colsum                                                 0.435        0.435        0.231        0.231
+    colsum accumulate                                      0.439        0.439        0.173        0.173
+    colsum partials summed, fp32 bound                     3.636        0.739        0.525        0.093
+    layernorm_bwd db                                       0.457        0.457        0.487        0.487
+    layernorm_bwd db accumulate                            0.446        0.446        0.477        0.477
+    layernorm_bwd db partials summed, fp32 bound           0.038        0.001        0.136        0.002
+    layernorm_bwd dw                                       0.470        0.470        0.473        0.473
+    layernorm_bwd dw accumulate                            0.490        0.490        0.469        0.469
+    layernorm_bwd dw partials summed, fp32 bound           0.274        0.096        0.336        0.097
+    layernorm_bwd dx                                       0.447        0.447        0.428        0.428
+    layernorm_bwd dx accumulate                            0.464        0.464        0.494        0.494
+    layernorm_f32_to_f32 y (fp32)                          0.425        0.571        0.387        0.559
+    layernorm_fwd y                                        0.497        0.497        0.500        0.500
+    norm_fwd_f32in ln y                                    0.498        0.498        0.498        0.498
+    norm_fwd_f32in rms y                                   0.994        0.994        0.992        0.992
+    rmsnorm_bwd dw                                         0.493        0.493        0.476        0.476
+    rmsnorm_bwd dw accumulate                              0.484        0.484        0.471        0.471
+    rmsnorm_bwd dw partials summed, fp32 bound             0.287        0.095        0.123        0.104
+    rmsnorm_bwd dx                                         0.498        0.498        0.496        0.496
+    rmsnorm_bwd dx accumulate                              0.495        0.495        0.498        0.498
+    rmsnorm_fwd rstd (fp32 ulps, bound 4)                  1.310        2.505        0.816        1.504
+    rmsnorm_fwd y                                          0.996        0.996        0.998        0.998
+    rmsnorm_fwd_q8 y                                       0.996        0.996        0.996        0.996
+
+Their mutants (tests/test_numerics_cpu.py, on the same inputs): a dw without the row's last 8-element chunk, a block that skips its last row, a
+reduce that skips a partial row score 85 to 1000 against 2 in the 16-bit dw / db at 9 rows and 1e4 to 7e5 under the fp32 bound at 4097 rows (a 16-bit
+dw cannot see one row of 4097); a LayerNorm variance taken as E[x^2] - mu^2 in fp32 is invisible in a 16-bit y (c = 0.5, the model's own) and is
+rejected in the fp32 y of mh_layernorm_f32_to_f32 (c = 8 to 12 against 2).
+
 The scaled-fp8 GEMMs are held to |got - want| <= ulp_out(want) + C_ACC 2^-24 sum|ab| instead (see the fp8 section below).  Worst observed
 (|got - want| - ulp) / (2^-24 sum|ab|) on an MI355X, against C_ACC = 512: the 4-wave kernel ~140 (K = 256, fp32 store); the 8-wave kernel over
 the shapes, weight forms and epilogues of tests/test_fp8_componentwise_gpu.py 167 (bf16 store), 185 (fp16 store), 175 (fp32 store), 71 / 104
@@ -609,6 +645,42 @@ def reduce_rows(partial, old=None, *, model=None):
     if old is not None:
         s, Bc = s + old.to(wt), Bc + old.to(wt).abs()
     return (s, Bc) if model is None else r16(s, None if model == torch.float32 else model)
+
+
+def colsum(x, old=None, *, model=None):
+    """mh_colsum_partial + mh_reduce_partials: out[d] = sum_r x[r, d] (+ old), x 16-bit (any row stride).  -> (ref64, B = sum |x| + |old|) like
+    `reduce_rows`, or the model: every term is exact in fp32, the sum is fp32, ONE rounding at the store (model=torch.float32: none)."""
+    return reduce_rows(x, old, model=model)
+
+
+def norm_f32in(x32, w, b, eps, *, y_dtype, model=None):
+    """mh_norm_fwd_f32in (y_dtype = w's 16-bit type) and mh_layernorm_f32_to_f32 (y_dtype = fp32): the fp32 stream's reader.  x32 fp32 [rows, d],
+    b None: RMSNorm, else LayerNorm.  -> dict y, B_y, x16; x16 = x32 rounded to nearest-even in w's type, which the kernel must reproduce
+    exactly (torch.equal).  model=w's dtype: the same in fp32, y rounded once to y_dtype (not at all when that is fp32).
+    The input is not a 16-bit value here and y may be stored in fp32, so the fp32 arithmetic itself is what B_y measures, in units of
+    eps(y_dtype): F = 4 (rstd |w| mean|x| + |xh w| / 2) + |xh w| + |b|, times 2^-24 / eps(y_dtype).  Its terms: the row sums are trees (a
+    lane's d / 64 terms, then a 64-lane butterfly; torch's pairwise sum in the model), so only their last levels round at the size of the
+    result - 4 roundings of mean|x| allowed for the mean with its divide, not the sqrt(K) of `gemm`'s sequential K loop - and an error of
+    the mean moves every y of the row by rstd |w| times itself (LayerNorm only); the variance is such a sum of non-negative terms and rstd
+    carries half its relative error into xh w; the last multiply-add rounds |xh w| and |b| once each.  A 16-bit LayerNorm y keeps
+    `layernorm`'s own B_y = |xh w| + |b| on top (the two may cancel), a 16-bit RMSNorm y none, as in `rmsnorm`."""
+    wt = torch.float64 if model is None else torch.float32
+    X, W = x32.to(wt), w.to(wt)
+    mu = X.mean(1, keepdim=True) if b is not None else torch.zeros_like(X[:, :1])
+    rstd = torch.rsqrt(((X - mu) ** 2).mean(1, keepdim=True) + eps)
+    xh = (X - mu) * rstd
+    y = xh * W if b is None else xh * W + b.to(wt)
+    x16 = x32.to(w.dtype)
+    if model is not None:
+        return {"y": r16(y, None if y_dtype == torch.float32 else y_dtype), "x16": x16}
+    k = 4.0
+    F = (k / 2 + 1) * (xh * W).abs()
+    if b is not None:
+        F = F + k * rstd * W.abs() * X.abs().mean(1, keepdim=True) + b.to(wt).abs()
+    By = F * (EPS16[torch.float32] / EPS16[y_dtype])
+    if b is not None and y_dtype != torch.float32:
+        By = By + (xh * W).abs() + b.to(wt).abs()
+    return {"y": y, "B_y": By, "x16": x16}
 
 
 # ---- elementwise: single roundings of a short expression, B = 0 ----------------------------------------------------------------------------

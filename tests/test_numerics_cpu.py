@@ -182,6 +182,109 @@ def test_elementwise_and_rope_models_accepted_and_mutants_rejected(dtype):
     reject("rope inverse on the last row", dtype, bad, ref, 0.0, lim)
 
 
+# ---- the norm kernels' dispatch arms and row partition, on the inputs of tests/test_norm_arms_gpu.py ----------------------------------------
+def c_of(got, ref, B, od):
+    try:
+        return N.componentwise(got, ref, B, N.EPS16[od], N.TINY[od])[0]
+    except AssertionError:
+        return float("inf")
+
+
+def above(name, dtype, c, lim):
+    print(f"mutant {name:50s} {str(dtype)[6:]:9s} c = {c:10.1f}  limit = {lim:.3f}")
+    assert c > lim, (name, dtype, c, lim)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("ln", [False, True], ids=["rms", "ln"])
+@pytest.mark.parametrize("rows,d", [(9, 520), (9, 1032), (9, 2056), (4097, 128)])
+def test_norm_backward_partition_mutants_rejected(dtype, ln, rows, d):
+    """What the GPU test holds dx, dw (db) and the raw partials to rejects: a dw without the row's last 8-element chunk, a block that skips its
+    last row, a reduce that skips one partial row.  16-bit dw where the GPU test has few rows; at 4097 rows one row is below a bf16 rounding of
+    the whole column (B_dw sums 4097 terms), and it is the fp32 bound on the summed partials that sees it."""
+    import norm_inputs as NI
+
+    F32 = torch.float32
+    I = NI.norm_inputs(rows, d, dtype, ln)
+    fn = (lambda **kw: N.layernorm(I["x"], I["w"], I["b"], NI.EPS, I["dy"], **kw)) if ln else (lambda **kw: N.rmsnorm(I["x"], I["w"], NI.EPS, I["dy"], **kw))
+    ref, mod = fn(), fn(model=dtype)
+    names = ("dw", "db") if ln else ("dw",)
+    lim16 = {nm: N.limit(c_of(N.r16(mod[nm], dtype), ref[nm], ref["B_" + nm], dtype)) for nm in names}
+    lim32 = {nm: N.limit(c_of(mod[nm], ref[nm], ref["B_" + nm], F32)) for nm in names}
+    limx = N.limit(c_of(mod["dx"], ref["dx"], ref["B_dx"], dtype))
+    print(f"model  backward {rows}x{d} {'ln' if ln else 'rms'} {str(dtype)[6:]}: limits dx {limx:.3f} 16-bit {lim16} fp32 {lim32}")
+    big = rows >= 4097
+    od = F32 if big else dtype
+    lim = lim32 if big else lim16
+    # the terms of dw (db) per row, and the partition the launcher makes of them
+    X, DY = I["x"].double(), I["dy"].double()
+    mu = X.mean(1, keepdim=True) if ln else 0.0
+    xh = (X - mu) * torch.rsqrt(((X - mu) ** 2).mean(1, keepdim=True) + NI.EPS)
+    terms = {"dw": DY * xh, "db": DY}
+    nblk, rpb, ranges = NI.block_ranges(rows)
+    for nm in names:
+        T = terms[nm]
+        partial = torch.stack([T[r0:r1].sum(0) for r0, r1 in ranges])
+        assert c_of(partial.sum(0).to(od), ref[nm], ref["B_" + nm], od) <= 1.0  # the partition itself is the reference
+        cut = ref[nm].clone()
+        cut[-8:] = 0
+        above(f"{nm} without the last 8-element chunk {rows}x{d}", dtype, c_of(cut.to(od), ref[nm], ref["B_" + nm], od), lim[nm])
+        r0, r1 = ranges[0]
+        above(f"{nm}: block 0 skips its last row {rows}x{d}", dtype, c_of((ref[nm] - T[r1 - 1]).to(od), ref[nm], ref["B_" + nm], od), lim[nm])
+        last_full = max(b for b, (r0, r1) in enumerate(ranges) if r1 > r0)
+        for b in (0, last_full):
+            above(f"{nm}: reduce skips partial row {b} {rows}x{d}", dtype, c_of((ref[nm] - partial[b]).to(od), ref[nm], ref["B_" + nm], od), lim[nm])
+    # the skipped row's dx is never written: whatever the buffer held (zeros here) is not the row's dx
+    dx = ref["dx"].clone()
+    dx[ranges[0][1] - 1] = 0
+    above(f"dx: block 0 skips its last row {rows}x{d}", dtype, c_of(dx.to(dtype), ref["dx"], ref["B_dx"], dtype), limx)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("d", [520, 1024, 4096])
+def test_layernorm_one_pass_variance_rejected_on_the_shifted_row(dtype, d):
+    """LayerNorm whose variance is E[x^2] - mu^2 in fp32: on a row of 30 + randn that difference keeps about 2^-24 x 900 of a variance of 1.
+    A 16-bit y cannot show it (printed); the fp32 y of mh_layernorm_f32_to_f32 does, under numerics.norm_f32in's B_y."""
+    import norm_inputs as NI
+
+    F32 = torch.float32
+    I = NI.f32_inputs(6, d, dtype, True)
+    x, w, b = I["x32"], I["w"], I["b"]
+    mu = x.mean(1, keepdim=True)
+    var = (x * x).mean(1, keepdim=True) - mu * mu
+    y_mut = (x - mu) * torch.rsqrt(var + torch.tensor(NI.EPS)) * w.float() + b.float()
+    assert y_mut.dtype == F32
+    for yd in (F32, dtype):
+        ref, mod = N.norm_f32in(x, w, b, NI.EPS, y_dtype=yd), N.norm_f32in(x, w, b, NI.EPS, y_dtype=yd, model=dtype)
+        assert torch.equal(ref["x16"], x.to(dtype))
+        cm = c_of(mod["y"], ref["y"], ref["B_y"], yd)
+        c = c_of(y_mut if yd == F32 else y_mut.to(yd), ref["y"], ref["B_y"], yd)
+        if yd == F32:
+            above(f"layernorm variance E[x^2] - mu^2, fp32 y d={d}", dtype, c, N.limit(cm))
+        else:
+            print(f"       (the same mutant in a 16-bit y d={d} {str(dtype)[6:]}: c = {c:.3f}, model {cm:.3f}: not visible)")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_colsum_and_f32in_models_accepted(dtype):
+    import norm_inputs as NI
+
+    for rows, d, ld, off in ((3, 8, 8, 0), (4097, 264, 272, 0), (4097, 260, 260, 0), (4097, 264, 272, 1)):
+        buf, old = NI.colsum_inputs(rows, d, ld, dtype, offset=off)
+        x = NI.colsum_view(buf, rows, d, ld, off)
+        for o in (None, old):
+            ref, B = N.colsum(x, o)
+            accept(f"colsum {rows}x{d} ld {ld}{' accumulate' if o is not None else ''}", dtype, N.colsum(x, o, model=dtype), ref, B, cap=1.01)
+    for ln in (False, True):
+        for d in (8, 520, 1024, 4096):
+            I = NI.f32_inputs(6, d, dtype, ln)
+            for yd in (dtype, torch.float32) if ln else (dtype,):
+                ref, mod = N.norm_f32in(I["x32"], I["w"], I["b"], NI.EPS, y_dtype=yd), N.norm_f32in(I["x32"], I["w"], I["b"], NI.EPS, y_dtype=yd, model=dtype)
+                c = c_of(mod["y"], ref["y"], ref["B_y"], yd)
+                print(f"model  norm_f32in {'ln' if ln else 'rms'} d={d} y {str(yd)[6:]:9s} {str(dtype)[6:]:9s} c = {c:8.3f}")
+                assert c <= 1.01, (ln, d, yd, c)
+
+
 # ---- loss ----------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("V", [103, 32003])
