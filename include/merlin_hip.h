@@ -517,6 +517,26 @@ int mh_select_tokens_warp(const float* logits, int64_t ldl, int rows, int V, int
 int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int len0, int len_step, int ngram,
                   const int64_t* words, const int32_t* word_off, int n_words, const int64_t* always, int n_always, const int64_t* begin,
                   int n_begin, int begin_index, const int64_t* eos, int n_eos, int min_total, void* stream);
+/* Device-resident forms of the two launches above, for a chain of steps captured into ONE replayable graph (the draft chain of assisted
+ * decoding, engine.capture_draft_graph): the step number and the history length are scalar launch arguments of mh_select_tokens_warp and
+ * mh_ban_tokens, frozen at capture; here they are read from device memory at kernel entry, so a replay after the host has changed nothing
+ * but the two counters is the launch for the new position.  Same kernels, same arithmetic: at equal step / length the results are
+ * bit-identical to the scalar entry points'.
+ * mh_select_tokens_dev: mh_select_tokens_warp with step = *step_base + step_off (step_base: one int64 on the device, not NULL).  The token
+ * goes to out[r] and, when ids != NULL, also to ids[r * ld_ids + *len_base + len_off] (len_base: one int32 on the device, not NULL then;
+ * ids int64 with ids_cols >= 1 columns per row, ld_ids >= ids_cols when rows > 1; a cell whose column falls outside [0, ids_cols) is not
+ * written; out and ids must not overlap).  out_u as mh_select_tokens.
+ * mh_ban_tokens_dev: mh_ban_tokens with len_r = *len_base + len0 + r * len_step (len_base not NULL; len0 may be negative); begin_index and
+ * min_total compare against len_r.  ids_cols: the valid columns of an ids row (ld_ids = 0 or >= ids_cols); a row whose len_r falls outside
+ * [0, ids_cols] reads and writes nothing (ids = NULL, allowed as in mh_ban_tokens: outside [0, 2^31 - 1]).
+ * Refused (MH_ERR_ARG, nothing launched): a NULL counter, V < 1, rows < 1, a row stride below V, and what the scalar forms refuse. */
+int mh_select_tokens_dev(const float* logits, int64_t ldl, int rows, int V, int do_sample, float temperature, int top_k, float top_p,
+                         float min_p, float epsilon_cutoff, uint64_t seed, const int64_t* step_base, int64_t step_off, int64_t* out,
+                         float* out_u, int64_t* ids, int64_t ld_ids, int64_t ids_cols, const int32_t* len_base, int len_off, void* stream);
+int mh_ban_tokens_dev(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int64_t ids_cols,
+                      const int32_t* len_base, int len0, int len_step, int ngram, const int64_t* words, const int32_t* word_off, int n_words,
+                      const int64_t* always, int n_always, const int64_t* begin, int n_begin, int begin_index, const int64_t* eos, int n_eos,
+                      int min_total, void* stream);
 /* Classifier-free guidance for decoder-only generation (transformers UnbatchedClassifierFreeGuidanceLogitsProcessor, the first processor
  * of its chain): for `rows` row pairs, out[r, i] = lu_i + scale * (lc_i - lu_i) for i < V, lc = log_softmax(cond[r, :V]) and lu =
  * log_softmax(uncond[r, :V]) in fp32 (l_i = (x_i - max) - log sum exp(x - max)).  cond and uncond are separate pointers with their own row

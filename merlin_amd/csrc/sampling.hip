@@ -7,6 +7,8 @@
 //   mh_select_tokens   argmax (do_sample=0) or temperature -> top-k -> top-p -> multinomial (inverse CDF in index order; the
 //                      uniform comes from a counter-based generator keyed on (seed, step, row): no host RNG traffic, replayable)
 //   mh_select_tokens_warp  the same kernel with two more warpers behind top-p: min_p, then epsilon_cutoff
+//   mh_select_tokens_dev / mh_ban_tokens_dev  the same two kernels with the step number and the history length read from device
+//                      counters at kernel entry: launches that a captured graph replays for a new position (the draft chain)
 //   mh_guidance_mix    classifier-free guidance: log_softmax of a conditional and an unconditional row mixed into the guided scores,
 //                      in front of the bans and the selection
 //   mh_log_softmax_rows  fp32 log-probabilities for beam search
@@ -72,9 +74,14 @@ struct BlockRed {
 // Logits are finite or -inf (mh_ban_tokens), with at least one finite value per row when sampling.  A -inf has zero mass in every
 // pass (expf(-inf - gm) = 0 for a finite gm) and is never picked: a top-k that asks for more tokens than are finite gets the key of
 // -inf as its threshold, which the KEY_FINITE floor below raises again.  do_sample == 0 on a row of -inf only: 0, like argmax.
+// Device-resident counters (mh_select_tokens_dev; NULL from the scalar entry points): step_base, read once at entry, is added to `step`;
+// ids (with len_base) is a second destination, cell ids[row * ld_ids + *len_base + len_off], written only when that column lies in
+// [0, ids_cols).  A captured launch then selects the next position after the host has changed nothing but the two counters.
 __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__ logits, int64_t ldl, int V, int do_sample,
                                                        float inv_t, int top_k, float top_p, float min_p, float eps, uint64_t seed,
-                                                       int64_t step, int64_t* __restrict__ out, float* __restrict__ out_u) {
+                                                       int64_t step, int64_t* __restrict__ out, float* __restrict__ out_u,
+                                                       const int64_t* __restrict__ step_base, int64_t* __restrict__ ids, int64_t ld_ids,
+                                                       int64_t ids_cols, const int32_t* __restrict__ len_base, int len_off) {
   __shared__ float fs[4];
   __shared__ int is[4];
   __shared__ float chunk_sum[256];
@@ -82,6 +89,14 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
   BlockRed red{fs, is};
   const int row = blockIdx.x, tid = threadIdx.x;
   const float* x = logits + (int64_t)row * ldl;
+  if (step_base) step += *step_base;
+  auto emit = [&](int64_t tok) {  // (thread 0 only)
+    out[row] = tok;
+    if (ids) {
+      const int64_t col = (int64_t)*len_base + len_off;
+      if (col >= 0 && col < ids_cols) ids[(int64_t)row * ld_ids + col] = tok;
+    }
+  };
   // contiguous chunk per thread: the CDF runs in index order
   const int C = (V + 255) / 256, i0 = tid * C, i1 = min(V, i0 + C);
 
@@ -99,7 +114,7 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
     __syncthreads();
     if ((tid & 63) == 0) is[tid >> 6] = cand;
     __syncthreads();
-    if (tid == 0) out[row] = min(min(is[0], is[1]), min(is[2], is[3]));
+    if (tid == 0) emit(min(min(is[0], is[1]), min(is[2], is[3])));
     return;
   }
   // ---- top-k threshold: the largest key K with count{key >= K} >= k  (bisection over the 32-bit ordered key space)
@@ -189,7 +204,7 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
       acc += __expf(z - gm);
       if (acc > target) { pick = i; break; }
     }
-    out[row] = pick >= 0 ? pick : lastk;
+    emit(pick >= 0 ? pick : lastk);
     if (out_u) out_u[row] = u;
   }
 }
@@ -201,15 +216,23 @@ __global__ __launch_bounds__(256) void select_tokens_k(const float* __restrict__
 //                 first k - 1 (transformers' SequenceBiasLogitsProcessor skips a word longer than the context, k = len + 1 included)
 //   always:       banned;   begin: banned when len == begin_index;   eos: banned while len < min_total
 // A target outside [0, V) is skipped (it still compares as history).
+// len_base (mh_ban_tokens_dev; NULL from the scalar entry point): a device-resident length added to every row's len; begin_index and
+// min_total compare against the sum.  A row whose length then falls outside [0, ids_cols] (no ids: outside int) reads and writes nothing.
 __global__ __launch_bounds__(256) void ban_tokens_k(float* __restrict__ logits, int64_t ldl, int V, const int64_t* __restrict__ ids,
                                                     int64_t ld_ids, int len0, int len_step, int ngram, const int64_t* __restrict__ words,
                                                     const int32_t* __restrict__ word_off, int n_words, const int64_t* __restrict__ always,
                                                     int n_always, const int64_t* __restrict__ begin, int n_begin, int begin_index,
-                                                    const int64_t* __restrict__ eos, int n_eos, int min_total) {
+                                                    const int64_t* __restrict__ eos, int n_eos, int min_total,
+                                                    const int32_t* __restrict__ len_base, int64_t ids_cols) {
   const int row = blockIdx.x, tid = threadIdx.x;
   float* x = logits + (int64_t)row * ldl;
   const int64_t* h = ids + (int64_t)row * ld_ids;
-  const int len = len0 + row * len_step;
+  int len = len0 + row * len_step;
+  if (len_base) {
+    const int64_t l = (int64_t)len + *len_base;
+    if (l < 0 || l > (ids ? ids_cols : (int64_t)0x7fffffff)) return;  // (without a history only the length-keyed clauses look at it)
+    len = (int)l;
+  }
   auto ban = [&](int64_t t) {
     if (t >= 0 && t < (int64_t)V) x[t] = -INFINITY;
   };
@@ -378,7 +401,8 @@ extern "C" int mh_select_tokens(const float* logits, int64_t ldl, int rows, int 
   if (!logits || !out || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
   if (do_sample && (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0)) return MH_ERR_ARG;
   hipLaunchKernelGGL(select_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, do_sample,
-                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, 0.f, 0.f, seed, step, out, out_u);
+                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, 0.f, 0.f, seed, step, out, out_u, (const int64_t*)nullptr,
+                     (int64_t*)nullptr, (int64_t)0, (int64_t)0, (const int32_t*)nullptr, 0);
   MH_LAUNCH_CHECK();
 }
 
@@ -389,7 +413,22 @@ extern "C" int mh_select_tokens_warp(const float* logits, int64_t ldl, int rows,
   if (do_sample && (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0)) return MH_ERR_ARG;
   if (do_sample && (!(min_p >= 0.f) || min_p > 1.0f || !(epsilon_cutoff >= 0.f) || !(epsilon_cutoff < 1.0f))) return MH_ERR_ARG;
   hipLaunchKernelGGL(select_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, do_sample,
-                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, min_p, epsilon_cutoff, seed, step, out, out_u);
+                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, min_p, epsilon_cutoff, seed, step, out, out_u,
+                     (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (int64_t)0, (const int32_t*)nullptr, 0);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_select_tokens_dev(const float* logits, int64_t ldl, int rows, int V, int do_sample, float temperature, int top_k,
+                                    float top_p, float min_p, float epsilon_cutoff, uint64_t seed, const int64_t* step_base,
+                                    int64_t step_off, int64_t* out, float* out_u, int64_t* ids, int64_t ld_ids, int64_t ids_cols,
+                                    const int32_t* len_base, int len_off, void* stream) {
+  if (!logits || !out || !step_base || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
+  if (do_sample && (!(temperature > 0.f) || !(top_p > 0.f) || top_p > 1.0f || top_k < 0)) return MH_ERR_ARG;
+  if (do_sample && (!(min_p >= 0.f) || min_p > 1.0f || !(epsilon_cutoff >= 0.f) || !(epsilon_cutoff < 1.0f))) return MH_ERR_ARG;
+  if (ids && (!len_base || ids_cols < 1 || (rows > 1 && ld_ids < ids_cols))) return MH_ERR_ARG;
+  hipLaunchKernelGGL(select_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, do_sample,
+                     do_sample ? 1.0f / temperature : 1.0f, top_k, top_p, min_p, epsilon_cutoff, seed, step_off, out, out_u, step_base, ids,
+                     ld_ids, ids_cols, len_base, len_off);
   MH_LAUNCH_CHECK();
 }
 
@@ -403,7 +442,23 @@ extern "C" int mh_ban_tokens(float* logits, int64_t ldl, int rows, int V, const 
   if ((ngram > 0 || n_words > 0) && !ids) return MH_ERR_ARG;
   if ((n_words > 0 && (!words || !word_off)) || (n_always > 0 && !always) || (n_begin > 0 && !begin) || (n_eos > 0 && !eos)) return MH_ERR_ARG;
   hipLaunchKernelGGL(ban_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, ids, ld_ids, len0, len_step, ngram, words,
-                     word_off, n_words, always, n_always, begin, n_begin, begin_index, eos, n_eos, min_total);
+                     word_off, n_words, always, n_always, begin, n_begin, begin_index, eos, n_eos, min_total, (const int32_t*)nullptr,
+                     (int64_t)0);
+  MH_LAUNCH_CHECK();
+}
+
+extern "C" int mh_ban_tokens_dev(float* logits, int64_t ldl, int rows, int V, const int64_t* ids, int64_t ld_ids, int64_t ids_cols,
+                                 const int32_t* len_base, int len0, int len_step, int ngram, const int64_t* words, const int32_t* word_off,
+                                 int n_words, const int64_t* always, int n_always, const int64_t* begin, int n_begin, int begin_index,
+                                 const int64_t* eos, int n_eos, int min_total, void* stream) {
+  if (!logits || !len_base || rows <= 0 || V <= 0 || ldl < V) return MH_ERR_ARG;
+  if (len_step < 0 || ld_ids < 0 || ids_cols < 0 || ngram < 0 || n_words < 0 || n_always < 0 || n_begin < 0 || n_eos < 0) return MH_ERR_ARG;
+  if ((int64_t)(len0 < 0 ? -(int64_t)len0 : len0) + (int64_t)(rows - 1) * len_step > 0x3fffffff) return MH_ERR_ARG;
+  if ((ngram > 0 || n_words > 0) && !ids) return MH_ERR_ARG;
+  if (ids && ld_ids != 0 && ld_ids < ids_cols) return MH_ERR_ARG;
+  if ((n_words > 0 && (!words || !word_off)) || (n_always > 0 && !always) || (n_begin > 0 && !begin) || (n_eos > 0 && !eos)) return MH_ERR_ARG;
+  hipLaunchKernelGGL(ban_tokens_k, dim3(rows), dim3(256), 0, as_stream(stream), logits, ldl, V, ids, ld_ids, len0, len_step, ngram, words,
+                     word_off, n_words, always, n_always, begin, n_begin, begin_index, eos, n_eos, min_total, len_base, ids_cols);
   MH_LAUNCH_CHECK();
 }
 

@@ -32,6 +32,14 @@ beside the conditional one, and the step's scores become lu + g (lc - lu) of the
 the warpers and the selection.  With a KV cache the two sequences are the two rows of ONE cache (engine.pair_cache), so a step streams the
 weights once: a B = 2 decode step (or a [2, T] verify step) plus one mix launch.  _resolve_guidance, _uncond_context and _guided_ref are
 the host side as pure functions.
+
+Speculative decoding has ONE loop (_draft_loop: draft, verify in one multi-row step, keep the agreeing prefix plus one) and two drafters:
+prompt lookup (_NgramDrafter, prompt_lookup_num_tokens) and a draft model (_ModelDrafter, assistant_model / num_assistant_tokens:
+transformers' assisted decoding under this module's contract - the plain path's token stream, not rejection sampling).  The draft model's k
+steps with their bans and selections can be one replayable graph (assistant_chain_graph=True: engine.capture_draft_graph on
+mh_ban_tokens_dev / mh_select_tokens_dev, whose step number and history length are device counters; the default replays a single-step
+graph per draft step - the two measured as a tie).  _resolve_assistant, _assisted_caches and _drafts_that_fit are its host side as pure
+functions.
 """
 from __future__ import annotations
 
@@ -195,7 +203,7 @@ _DEFAULTS = dict(max_new_tokens=None, max_length=None, eos_token_id=None, pad_to
                  top_p=1.0, num_beams=1, length_penalty=1.0, early_stopping=False, use_cache=True, prompt_lookup_num_tokens=None,
                  max_matching_ngram_size=2, no_repeat_ngram_size=0, bad_words_ids=None, min_new_tokens=0, suppress_tokens=None,
                  begin_suppress_tokens=None, min_p=None, epsilon_cutoff=0.0, guidance_scale=None, negative_prompt_ids=None,
-                 negative_prompt_attention_mask=None)
+                 negative_prompt_attention_mask=None, assistant_model=None, num_assistant_tokens=None)
 # options that are accepted only at the value that leaves the implemented modes unchanged (anything else is a decoding mode the
 # reference's scripts never reach: refuse it instead of silently returning something different)
 _NEUTRAL = dict(repetition_penalty=(1.0, None), num_return_sequences=(1, None), num_beam_groups=(1, None),
@@ -204,8 +212,7 @@ _NEUTRAL = dict(repetition_penalty=(1.0, None), num_return_sequences=(1, None), 
                 output_attentions=(False, None), output_hidden_states=(False, None), logits_processor=(None,), prefix_allowed_tokens_fn=(None,),
                 encoder_no_repeat_ngram_size=(0, None), diversity_penalty=(0.0, None), eta_cutoff=(0.0, None),
                 renormalize_logits=(False, None), forced_bos_token_id=(None,), forced_eos_token_id=(None,), sequence_bias=(None,),
-                assistant_model=(None,), synced_gpus=(False, None),
-                bos_token_id=None, use_beam_search=None, num_assistant_tokens=None, trust_remote_code=None)
+                synced_gpus=(False, None), bos_token_id=None, use_beam_search=None, trust_remote_code=None)
 
 
 def _resolve_options(generation_config, kw):
@@ -321,6 +328,56 @@ def _resolve_guidance(opt, negative_images=None, session=None, input_ids=None, a
     return dict(scale=g, ids=neg, images=negative_images)
 
 
+def _resolve_assistant(opt, assistant, model, session=None, input_ids=None, attention_mask=None):
+    """Assisted decoding of one call (assistant_model is set), from the resolved options: -> k, the tokens drafted per round
+    (num_assistant_tokens; None: 5).  Everything that cannot be served is refused here by name, before any device work: first what needs no
+    tensor, then the prompt's shape, last the two models' vocabularies.  A pure function of host data."""
+    k = opt["num_assistant_tokens"]
+    k = 5 if k is None else k
+    if not _is_int(k) or not 1 <= k <= 15:
+        raise ValueError(f"num_assistant_tokens = {k!r}: the verify step takes 1..15 drafted tokens (16 rows with the token before them)")
+    if opt["prompt_lookup_num_tokens"] is not None:
+        raise ValueError("`assistant_model` and `prompt_lookup_num_tokens` are two sources of drafts: pick one")
+    if opt["num_beams"] > 1:
+        raise ValueError("`assistant_model` drafts for greedy search and sampling: it cannot be combined with num_beams > 1")
+    if not opt["use_cache"]:
+        raise ValueError("assisted generate requires `use_cache=True`")
+    if opt["guidance_scale"] is not None:
+        raise ValueError("`assistant_model` cannot be combined with `guidance_scale`: the draft model follows the conditional sequence alone")
+    if session is not None:
+        raise ValueError("`assistant_model` cannot be combined with session=: the draft model keeps no cache between calls")
+    if getattr(assistant, "engine", None) is None or getattr(assistant, "config", None) is None:
+        raise ValueError(f"`assistant_model` has to be a merlin_amd model (with .engine and .config), but is {type(assistant).__name__}")
+    if input_ids.shape[0] != 1:
+        raise ValueError("assisted generate is only supported for batch_size = 1")
+    if attention_mask is not None and not bool(torch.as_tensor(attention_mask).to(torch.bool).all()):
+        raise ValueError("`assistant_model` takes an un-padded prompt (attention_mask with zeros)")
+    va, vt = getattr(assistant.config, "vocab_size", None), model.config.vocab_size
+    if va != vt:
+        raise ValueError(f"`assistant_model` has vocab_size = {va}, the model {vt}: a draft model has to share the vocabulary")
+    return k
+
+
+def _assisted_caches(n, c, a):
+    """The cache bookkeeping of one round of assisted decoding, as a pure function.  Before the round the sequence has n tokens and both
+    caches hold the keys of seq[:n - 1].  The draft model was fed c tokens (seq[n - 1], d_1 .. d_{c-1}) and proposed d_1 .. d_c; the
+    target verified [seq[n - 1], d_1 .. d_c] and a <= c drafts were accepted, so a + 1 tokens are emitted.  -> (target length, draft
+    length, owed): the target keeps the last token and the accepted drafts, n + a rows = all but the last token of the new sequence; the
+    draft cache is truncated to the same length, but holds only n - 1 + c rows - when a == c it is `owed` = 1 key short (d_c was never
+    fed to it) and the next round feeds it that token first."""
+    if not (n >= 1 and 1 <= c and 0 <= a <= c):
+        raise ValueError(f"_assisted_caches(n={n}, c={c}, a={a})")
+    target = n + a
+    draft = min(n - 1 + c, target)
+    return target, draft, target - draft
+
+
+def _drafts_that_fit(n, k, max_len):
+    """How many of a round's k drafts are used when the sequence has n tokens: the verify step emits one token more than it accepts, so
+    c + 1 <= max_len - n.  0: only one token is left, a plain step."""
+    return max(0, min(k, max_len - n - 1))
+
+
 def _uncond_context(negative_ids, prompt_ids, new_tokens):
     """The unconditional sequence of a guided step, as a list of ints: the negative prompt (None: the prompt's last token, transformers'
     default) followed by every token generated so far."""
@@ -419,6 +476,9 @@ class _Call:
     stats: dict = None           # engine.last_generate_stats of the call (greedy search and sampling)
     lookup: int = None           # prompt_lookup_num_tokens and, with it, max_matching_ngram_size
     max_ngram: int = None
+    assistant: object = None     # assistant_model and, with it, num_assistant_tokens (None: 5)
+    n_assist: int = None
+    chain_graph: bool = False    # the draft's k steps of a round as one graph replay (assistant_chain_graph)
     num_beams: int = 1
     length_penalty: float = 1.0
     early_stopping: object = False
@@ -428,7 +488,7 @@ class _Call:
 @torch.no_grad()
 def generate(model, input_ids, images=None, attention_mask=None, generation_config=None, stopping_criteria=None, streamer=None,
              use_graph=True, fp8_weights=False, fp8_kv=False, fp4_weights=False, share_prompt_kv=False, seed=None, session=None, negative_images=None,
-             fp4_prefill=False, **kw):
+             fp4_prefill=False, assistant_chain_graph=False, **kw):
     """transformers' `GenerationMixin.generate` for the modes the reference reaches (module docstring).  `streamer` follows HF's
     protocol (`put(prompt ids)`, `put(next tokens)` every step, `end()`): serve/cli.py:93-104 passes a TextStreamer.  Every
     other HF option is either implemented, accepted at its neutral value, or refused by name - nothing is silently dropped.
@@ -473,7 +533,27 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
     launch), use_cache=False runs two forwards per token; composes with use_graph, fp8_kv, fp8_weights, fp4_weights, the bans, min_p,
     epsilon_cutoff, streamer and stopping criteria (both see the conditional ids only) and prompt_lookup_num_tokens <= 7 (2 (k + 1) <= 16
     verify rows).  Refused by name: num_beams > 1, session=, batch_size > 1, a padded prompt or negative prompt, and a negative prompt or
-    negative_images while guidance is off.  engine.last_generate_stats["guided_steps"]: the steps whose scores were mixed."""
+    negative_images while guidance is off.  engine.last_generate_stats["guided_steps"]: the steps whose scores were mixed.
+    Assisted decoding - assistant_model=draft (a second merlin_amd model with the same vocab_size; any depth, width or head count the
+    decode kernels take), num_assistant_tokens=k (1..15; None: 5; a generation_config's value counts like the keyword): every round the
+    draft model proposes k tokens - its own decode steps on its own 16-bit cache, the call's bans and the call's selection with the plain
+    path's key (seed, token number, row 0) after each - and the model verifies them with the last token in ONE step of k + 1 rows
+    (engine.verify_step) and keeps the agreeing prefix plus one: the speculative contract of prompt_lookup_num_tokens, not rejection
+    sampling.  The output is the plain path's token stream whatever the draft proposes (greedy: exact match; sampling: draft and model share
+    the uniform of a position).  The draft gets `images` if it has a vision tower, else it reads the same ids text-only.  With use_graph
+    every draft step is a replay of the draft's single-step graph followed by the eager ban and selection launches; without it the steps
+    run eagerly.  assistant_chain_graph=True (needs use_graph and assistant_model; refused otherwise): the k draft steps, bans and
+    selections of a round are ONE graph replay instead (engine.capture_draft_graph: mh_ban_tokens_dev / mh_select_tokens_dev read the token
+    number and the length from two device counters).  It is opt-in because it measured as a tie - within 3 % either way of the per-step arm
+    at k = 3, 5, 7 on one MI355X with 67 M and 297 M parameter drafts (profiles/decode_assisted_bench.txt): a draft step's GPU time exceeds
+    what the host spends enqueueing it, so there is no host time left to save.  All arms emit the same tokens.  Greedy and sampling;
+    composes with use_graph, fp8_kv,
+    fp8_weights, fp4_weights (fp4_prefill) on the model - the draft runs 16-bit -, the bans, min_p, epsilon_cutoff, streamer and stopping
+    criteria.  Refused by name: num_beams > 1, batch_size > 1, a padded prompt, use_cache=False, guidance_scale, session=,
+    prompt_lookup_num_tokens beside it, another vocab_size, k outside 1..15, an assistant without .engine / .config.
+    engine.last_generate_stats gains "draft_steps" (assisted calls only): the draft model's decode steps, catch-up steps included (after a
+    fully accepted round the draft cache is one key short) and, in the chain graph, the steps of a round near max_length that ran unused.
+    None: every path runs and launches as without it."""
     o = _resolve_options(generation_config, kw)
     max_new_tokens, max_length, eos_token_id, pad_token_id = o["max_new_tokens"], o["max_length"], o["eos_token_id"], o["pad_token_id"]
     do_sample, temperature, top_k, top_p = o["do_sample"], o["temperature"], o["top_k"], o["top_p"]
@@ -512,6 +592,11 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
             raise ValueError(f"prompt_lookup_num_tokens = {lookup!r}: the verify step takes 1..15 drafted tokens (16 rows with the token before them)")
         if not isinstance(max_ngram, int) or max_ngram <= 0:
             raise ValueError("Invalid max_matching_ngram_size or num_output_tokens")
+    assistant, n_assist = o["assistant_model"], None
+    if assistant_chain_graph and (assistant is None or not use_graph):
+        raise ValueError("assistant_chain_graph=True captures the draft model's steps of a round into one graph: it needs `assistant_model` and use_graph=True")
+    if assistant is not None:
+        n_assist = _resolve_assistant(o, assistant, model, session, input_ids, attention_mask)  # (refusals by name, before any device work)
     cfg = model.config
     eos_ids = _as_list(cfg.eos_token_id if eos_token_id is None else eos_token_id)
     pad = pad_token_id if pad_token_id is not None else (cfg.pad_token_id if cfg.pad_token_id is not None else (eos_ids[0] if eos_ids else 0))
@@ -535,10 +620,13 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         if do_sample and (o["min_p"] is not None or o["epsilon_cutoff"] > 0.0):
             sel.update(min_p=o["min_p"], epsilon_cutoff=o["epsilon_cutoff"])
         stats = dict(plain_steps=0, verify_steps=0, drafted=0, accepted=0)
+        if assistant is not None:  # (a key of assisted calls only) the draft model's decode steps
+            stats["draft_steps"] = 0
     call = _Call(model=model, images=images, attention_mask=None if beams else attention_mask,  # (beam search: all ones, as checked)
                  max_len=max_len, eos_ids=eos_ids, pad=pad, stop=_Stopper(max_len, eos_ids, stopping_criteria), sel=sel, streamer=streamer,
                  use_graph=use_graph, fp8_weights=bool(fp8_weights), fp4_weights=bool(fp4_weights), fp4_prefill=bool(fp4_prefill), fp8_kv=bool(fp8_kv), session=session,
                  bans=_ban_plan(o, eos_ids), guide=guide, stats=stats, lookup=lookup, max_ngram=None if lookup is None else max_ngram,
+                 assistant=assistant, n_assist=n_assist, chain_graph=bool(assistant_chain_graph),
                  num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping, share_prompt_kv=bool(share_prompt_kv))
     if beams:
         return _beam_search(call, input_ids)
@@ -548,6 +636,8 @@ def generate(model, input_ids, images=None, attention_mask=None, generation_conf
         model.engine.last_generate_stats = stats
     if lookup is not None:
         out = _sample_lookup(call, input_ids)
+    elif assistant is not None:
+        out = _sample_assisted(call, input_ids)
     elif not use_cache:
         out = _sample_recompute(call, input_ids)
     else:
@@ -644,6 +734,7 @@ class _Stepper:
     def capture(self, T=0):
         """The decode step as one replayable HIP graph on self.cache and, T >= 1 (the lookup loop), the [rows, T] verify step as another."""
         c = self.call
+        self.T = T
         if c.use_graph and self.logits0.is_cuda and c.max_len - self.P > 2:
             self.graph, self.g_tok, self.g_logits = self.eng.capture_decode_graph(self.cache, **self.weights)
             if T:
@@ -684,7 +775,7 @@ class _Stepper:
         """One verify step of T rows per cache row on `last` [1] followed by the c drafted tokens draft[:, :c] -> scores [1, T, >= V]; does
         not advance the cache.  A short draft is padded to the step's T rows; their scores are not looked at."""
         call, guide = self.call, self.call.guide
-        toks = self.v_tok if self.vgraph is not None else torch.empty(self.cache.B, call.lookup + 1, dtype=torch.int64, device=last.device)
+        toks = self.v_tok if self.vgraph is not None else torch.empty(self.cache.B, self.T, dtype=torch.int64, device=last.device)
         toks[:, 0] = last
         toks[:, 1:] = call.pad
         toks[:, 1:1 + c] = draft[:, :c]
@@ -777,20 +868,18 @@ def _accept(draft, selected, room, stops):
     return out, a, stopped
 
 
-def _sample_lookup(call, input_ids):
-    """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
-    (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
-    once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
-    one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step.
-    guide: the steps run on the paired cache with the same tokens in both rows ([2, T] verify rows, 2 T <= 16), row pair t is mixed into
-    conditional row t before the bans and the selection, and both sequences keep the same accepted count."""
-    c, st = call, _Stepper(call)
-    k, max_len, stats, sel, stop = c.lookup, c.max_len, c.stats, c.sel, c.stop
-    P, V, T = input_ids.shape[1], st.V, k + 1
-    logits = st.prefill(input_ids, max_len - P + k)  # k rows of room for a rejected draft's tail
-    st.capture(T)
-    # (with bans: k cells more, a draft is written behind the sequence before it is verified)
-    seq = st.ids_buffer(max_len + (k if c.bans is not None else 0))
+def _draft_loop(seq, P, max_len, stop, streamer, stats, first, drafter, target):
+    """The speculative loop, one sequence, with everything that touches a model behind two objects - the lookup drafter and the model
+    drafter differ in `drafter` alone; tests drive it with pure functions on a CPU ids buffer.  seq int64 [1, cells]: the ids buffer holding
+    the P prompt tokens; first: the token selected from the prefill's scores, as a list.
+      drafter.propose(n) -> (d, handle): d >= 0 drafted tokens behind seq[:n] (0: none; never more than fit below max_len with the one
+          token a verify step adds) and whatever target.verify needs to find them;  drafter.commit(n, d, a): a of them were accepted;
+          drafter.steps: decoder steps it ran (a drafter without a model: 0).
+      target.plain(n) -> [token number n - P]: one decode step on seq[0, n - 1], its bans and selection;
+      target.verify(n, handle, d) -> (the d + 1 tokens selected from ONE verify step on seq[0, n - 1] and the drafts, selected[t]
+          conditioned on draft[:t]; the d drafts), both as lists;  target.advance(m): the step's first m rows are keys now.
+    Every round emits the agreeing prefix plus one (_accept) - up to a stop, never beyond max_len.  Selection being keyed by position, the
+    token stream is the plain path's whatever the drafter proposes.  -> the sequence's length; stats counts the rounds."""
     n = P  # valid length of seq
 
     def emit(cand, draft):
@@ -804,35 +893,186 @@ def _sample_lookup(call, input_ids):
 
         out, a, stopped = _accept(draft, cand, max_len - n, stops)
         n = base + len(out)
-        if c.streamer is not None:
-            c.streamer.put(torch.tensor([out], dtype=torch.int64))
+        if streamer is not None:
+            streamer.put(torch.tensor([out], dtype=torch.int64))
         return out, a, stopped
 
-    st.ban(logits, P)
-    first = _select(logits, V, sel, 0)
-    out, _, stopped = emit(first.tolist(), [])
+    out, _, stopped = emit(first, [])
     while not stopped and n < max_len:
-        emitted = n - P
-        draft_dev, cnt = O.ngram_draft(seq, n, c.max_ngram, k, max_len)
-        d = int(cnt[0])
-        last = seq[:, n - 1]
+        d, handle = drafter.propose(n)
         if d == 0:
-            logits = st.step(last)
+            cand = target.plain(n)
             stats["plain_steps"] += 1
-            st.ban(logits, n)
-            out, _, stopped = emit(_select(logits, V, sel, emitted).tolist(), [])
+            out, _, stopped = emit(cand, [])
             continue
-        logits = st.verify(last, draft_dev, d)
-        if c.bans is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
-            seq[0, n:n + d] = draft_dev[0, :d]
-            st.ban(logits[0], n, len_step=1, ld_ids=0)
-        picked = O.select_tokens_multi(logits, V, step0=emitted, **sel)[:, 0]  # [T]
-        both = torch.cat([picked, draft_dev[0]]).tolist()  # one transfer
-        out, a, stopped = emit(both[:d + 1], both[T:T + d])
-        st.cache.advance(a + 1)  # the last token and the a accepted drafts are keys now; the stale rows behind them get overwritten
+        before = n
+        picked, draft = target.verify(n, handle, d)
+        out, a, stopped = emit(picked, draft)
+        target.advance(a + 1)  # the last token and the a accepted drafts are keys now; the stale rows behind them get overwritten
+        drafter.commit(before, d, a)
         stats["verify_steps"] += 1
         stats["drafted"] += d
         stats["accepted"] += min(a, len(out))  # (a draft token that agreed beyond a stop or max_length was not emitted)
+    if "draft_steps" in stats:
+        stats["draft_steps"] = drafter.steps
+    return n
+
+
+class _StepTarget:
+    """_draft_loop's target on a _Stepper: the decode and the verify step of the call's model with the bans and the selection."""
+
+    def __init__(self, st, seq, k):
+        self.st, self.seq, self.k = st, seq, k
+
+    def plain(self, n):
+        st, c = self.st, self.st.call
+        logits = st.step(self.seq[:, n - 1])
+        st.ban(logits, n)
+        return _select(logits, st.V, c.sel, n - st.P).tolist()
+
+    def verify(self, n, draft_dev, d):
+        st, c, seq, T = self.st, self.st.call, self.seq, self.k + 1
+        logits = st.verify(seq[:, n - 1], draft_dev, d)
+        if c.bans is not None:  # row t is conditioned on seq[:n] + draft[:t]: the draft goes behind the sequence (emit overwrites those cells)
+            seq[0, n:n + d] = draft_dev[0, :d]
+            st.ban(logits[0], n, len_step=1, ld_ids=0)
+        picked = O.select_tokens_multi(logits, st.V, step0=n - st.P, **c.sel)[:, 0]  # [T]
+        both = torch.cat([picked, draft_dev[0]]).tolist()  # one transfer
+        return both[:d + 1], both[T:T + d]
+
+    def advance(self, m):
+        self.st.cache.advance(m)
+
+
+class _NgramDrafter:
+    """Prompt lookup: up to k tokens from the sequence itself (mh_ngram_draft; _prompt_lookup is its restatement).  No model, no state."""
+    steps = 0
+
+    def __init__(self, seq, k, max_ngram, max_len):
+        self.seq, self.k, self.max_ngram, self.max_len = seq, k, max_ngram, max_len
+
+    def propose(self, n):
+        draft_dev, cnt = O.ngram_draft(self.seq, n, self.max_ngram, self.k, self.max_len)
+        return int(cnt[0]), draft_dev
+
+    def commit(self, n, d, a):
+        pass
+
+
+class _ModelDrafter:
+    """A draft model (generate(assistant_model=...)): k decode steps of its own engine on its own 16-bit cache, each followed by the call's
+    bans (history seq[:n] + draft[:i]) and the target's own selection with key (seed, emitted + i, row 0).  tok int64 [k + 1] holds
+    [seq[n - 1], d_1 .. d_k]: step i feeds tok[i] and selects tok[i + 1].
+    chain=True: the k steps are ONE graph replay (engine.capture_draft_graph) - per round the host writes tok[0] and the two device
+    counters (emitted, n: one 16-byte copy from pinned memory) and replays; the chain always runs its k steps, a round near max_length
+    uses the first drafts that fit.  chain=False: the same steps one by one through the scalar entry points (the decode step itself
+    replayed from a graph when graph=True).  `fed`: the draft cache's length, kept on the host (_assisted_caches)."""
+
+    def __init__(self, call, seq, k, chain, graph):
+        self.call, self.seq, self.k, self.chain, self.steps = call, seq, k, bool(chain), 0
+        self.graph_steps = bool(graph) and not self.chain
+        self.eng, self.V = call.assistant.engine, call.model.config.vocab_size
+        self.sgraph = self.cgraph = None
+
+    def prefill(self, input_ids, tables):
+        """The prompt into the draft's cache (with the call's images if the draft has a vision tower, else text-only on the same ids),
+        room for the new tokens and k rows of a rejected draft's tail; then the captures."""
+        c, k, eng = self.call, self.k, self.eng
+        P = input_ids.shape[1]
+        tower = getattr(c.assistant.get_model(), "vision_tower", None) if hasattr(c.assistant, "get_model") else None
+        _, self.cache = eng.prefill(input_ids, None, c.images if tower is not None else None, c.max_len - P + k)
+        dev = self.cache.lens.device
+        self.fed, self.P, self.tables = P, P, tables
+        if self.chain:
+            self.counters = torch.zeros(2, dtype=torch.int64, device=dev)  # [emitted, n]; n is read as int32 (the low word)
+            self.host = torch.zeros(2, dtype=torch.int64).pin_memory()
+            self._set_counters(P + 1)
+            self.cgraph, self.tok = eng.capture_draft_graph(self.cache, k, c.sel, tables, self.seq, (self.counters[:1], self.counters[1:].view(torch.int32)))
+        else:
+            self.tok = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+        if self.chain or self.graph_steps:  # the single step: every step of the per-step arm, the catch-up step of the chain arm
+            self.sgraph, self.s_tok, self.s_logits = eng.capture_decode_graph(self.cache)
+
+    def _set_counters(self, n):
+        self.host[0], self.host[1] = n - self.P, n
+        self.counters.copy_(self.host, non_blocking=True)
+
+    def _step(self, token):
+        """One decode step of the draft on token int64 [1] -> its scores."""
+        self.steps += 1
+        self.fed += 1
+        if self.sgraph is not None:
+            self.s_tok.copy_(token)
+            self.sgraph.replay()
+            return self.s_logits
+        return self.eng.decode_step(token, self.cache)
+
+    def propose(self, n):
+        c, k, seq, tok = self.call, self.k, self.seq, self.tok
+        d = _drafts_that_fit(n, k, c.max_len)
+        if d == 0:
+            return 0, None
+        while self.fed < n - 1:  # a key the last round left owed (its last draft was accepted, and never fed)
+            self._step(seq[0, self.fed:self.fed + 1])
+        tok[:1].copy_(seq[0, n - 1:n])
+        if self.chain:
+            self._set_counters(n)
+            self.cgraph.replay()
+            self.steps += k
+            self.fed += k
+        else:
+            for i in range(d):
+                logits = self._step(tok[i:i + 1])
+                if self.tables is not None:
+                    O.ban_tokens(logits, self.V, seq, len0=n + i, **self.tables)
+                tok[i + 1:i + 2] = O.select_tokens(logits, self.V, step=n - self.P + i, **c.sel)
+                if self.tables is not None:  # the next step's ban reads the draft behind the sequence
+                    seq[0, n + i:n + i + 1] = tok[i + 1:i + 2]
+        return d, tok[None, 1:]
+
+    def commit(self, n, d, a):
+        keep = min(self.fed, _assisted_caches(n, d, a)[0])
+        self.cache.truncate(keep)
+        self.fed = keep
+
+
+def _sample_lookup(call, input_ids):
+    """Greedy search / sampling with prompt-lookup drafts (one sequence): every step drafts up to k tokens from the sequence itself
+    (mh_ngram_draft), runs them with the last token through ONE verify step of k + 1 rows (engine.verify_step: the weights are streamed
+    once), selects all k + 1 rows with the plain path's RNG key - row t as token number emitted + t - and keeps the agreeing prefix plus
+    one (_accept).  Selection being keyed by position, the token stream is the plain path's.  No draft: the plain decode step.
+    guide: the steps run on the paired cache with the same tokens in both rows ([2, T] verify rows, 2 T <= 16), row pair t is mixed into
+    conditional row t before the bans and the selection, and both sequences keep the same accepted count."""
+    c, st = call, _Stepper(call)
+    k, max_len = c.lookup, c.max_len
+    P = input_ids.shape[1]
+    logits = st.prefill(input_ids, max_len - P + k)  # k rows of room for a rejected draft's tail
+    st.capture(k + 1)
+    # (with bans: k cells more, a draft is written behind the sequence before it is verified)
+    seq = st.ids_buffer(max_len + (k if c.bans is not None else 0))
+    st.ban(logits, P)
+    first = _select(logits, st.V, c.sel, 0).tolist()
+    n = _draft_loop(seq, P, max_len, c.stop, c.streamer, c.stats, first, _NgramDrafter(seq, k, c.max_ngram, max_len), _StepTarget(st, seq, k))
+    return st.finish(n)
+
+
+def _sample_assisted(call, input_ids):
+    """Greedy search / sampling with a draft model (one sequence): _sample_lookup's loop with _ModelDrafter in the drafter's place.  Every
+    round the draft model proposes k tokens (fewer near max_length), the target verifies them with the last token in one step of k + 1
+    rows and keeps the agreeing prefix plus one.  Both caches get k spare rows; the ids buffer k spare cells (the drafts are written
+    behind the sequence before they are verified).  call.chain_graph: the draft steps of a round as one graph (where the call uses graphs at all)."""
+    c, st = call, _Stepper(call)
+    k, max_len = c.n_assist, c.max_len
+    P = input_ids.shape[1]
+    logits = st.prefill(input_ids, max_len - P + k)
+    st.capture(k + 1)
+    seq = st.ids_buffer(max_len + k)
+    graphs = st.graph is not None  # (the stepper's own decision: use_graph, a device, more than two new tokens)
+    drafter = _ModelDrafter(c, seq, k, chain=graphs and c.chain_graph, graph=graphs)
+    drafter.prefill(input_ids, st.tables)
+    st.ban(logits, P)
+    first = _select(logits, st.V, c.sel, 0).tolist()
+    n = _draft_loop(seq, P, max_len, c.stop, c.streamer, c.stats, first, drafter, _StepTarget(st, seq, k))
     return st.finish(n)
 
 

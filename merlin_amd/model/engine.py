@@ -1592,6 +1592,45 @@ class HipEngine:
             logits = self.verify_step(tok, cache, fp8=fp8, fp4=fp4)
         return g, tok, logits
 
+    def draft_chain(self, cache, tok, k, sel, ban_tables, seq, counters):
+        """The body capture_draft_graph captures, on the current stream: k times [decode step on tok[i] (16-bit weights) -> the call's bans
+        (mh_ban_tokens_dev, history seq[0, :n + i]) -> selection with key (seed, emitted + i, row 0) (mh_select_tokens_dev)], the token
+        written to tok[i + 1] - which step i + 1 feeds - and to seq[0, n + i], which the next step's ban reads (stream order).  emitted
+        (int64) and n (int32) are the device counters `counters` = (step_base, len_base).  Advances the cache by k."""
+        V = self.model.config.vocab_size
+        step_base, len_base = counters
+        for i in range(k):
+            logits = self.decode_step(tok[i:i + 1], cache)
+            if ban_tables is not None:
+                O.ban_tokens_dev(logits, V, seq, len_base, len0=i, **ban_tables)
+            O.select_tokens_dev(logits, V, step_base, i, out=tok[i + 1:i + 2], ids=seq, len_base=len_base, len_off=i, **sel)
+
+    def capture_draft_graph(self, cache, k, sel, ban_tables, seq, counters):
+        """The draft chain of assisted decoding (generate(assistant_model=...)) as ONE replayable HIP graph bound to `cache`, this
+        (draft) engine's one-sequence 16-bit cache: draft_chain's k steps.  -> (graph, tok int64 [k + 1]): the caller writes the
+        sequence's last token to tok[0] and the two counters, replays, and reads the k drafted tokens from tok[1:] (tok is also the
+        verify step's input row).  sel: the selection's keyword arguments; ban_tables: generation._ban_tables of the call or None; seq
+        int64 [1, cells]: the call's ids buffer; counters = (emitted int64 [1], n int32 [1]) on the device.  The cache advances by k
+        inside the graph; the caller truncates it to what was accepted.  Captured on one stream, no parallel branches
+        (capture_verify_graph).  The eager warm-up writes cache rows at and behind the current length, tok[1:] and k cells of seq behind
+        the counter's n: all of them scratch until the next replay rewrites them; the cache's length is restored."""
+        if cache.B != 1 or cache.fp8 or cache.rpos is not None or not 1 <= k <= 15:
+            raise ValueError("capture_draft_graph takes a one-sequence 16-bit cache without padding and 1 <= k <= 15")
+        dev = self.arena.flat.device
+        tok = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+        keep = cache.lens.clone()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self.draft_chain(cache, tok, k, sel, ban_tables, seq, counters)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        cache.lens.copy_(keep)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.draft_chain(cache, tok, k, sel, ban_tables, seq, counters)
+        cache.lens.copy_(keep)  # (capture does not execute)
+        return g, tok
+
     # standalone sub-module calls (reference module surface; not used by the fused forward)
     def tower_forward_public(self, images):
         self.ensure_arena()

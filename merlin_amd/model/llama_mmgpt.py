@@ -280,7 +280,13 @@ class MMGPTLlamaForCausalLM(nn.Module):
         un-padded prompt per call; for evaluation loops over one image and for multi-turn chat),
         guidance_scale / negative_prompt_ids / negative_prompt_attention_mask (transformers' classifier-free guidance for decoder-only
         models: every step's scores are mixed from the prompt's and a negative prompt's log-softmaxes; both sequences share one B = 2 KV
-        cache) and negative_images (the images of the negative prompt's spans)."""
+        cache), negative_images (the images of the negative prompt's spans) and
+        assistant_model / num_assistant_tokens (transformers' assisted decoding with this package's speculative contract: a second, small
+        model of this package with the same vocabulary drafts k = 1..15 tokens per round (default 5), this model verifies them in one
+        multi-row step and keeps the agreeing prefix plus one - the plain path's token stream, greedy or sampled, in fewer passes over
+        the large weights; one un-padded prompt, use_cache; composes with the weight and cache formats, the bans, streamer and stopping
+        criteria; refused with beams, batches, sessions, guidance, prompt_lookup_num_tokens or another vocabulary;
+        assistant_chain_graph=True: a round's k draft steps as one graph replay - measured as a tie with the default, see generation.generate)."""
         from ..generation import generate as _generate
 
         return _generate(self, input_ids, images=images, **kwargs)

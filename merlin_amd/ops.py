@@ -647,6 +647,60 @@ def ban_tokens(logits, V=None, ids=None, len0=0, len_step=0, ld_ids=None, ngram=
     return logits
 
 
+def _dev_counter(t, dtype, device):
+    """A device-resident counter of the *_dev launches: one element of `dtype` on `device` (a view into a larger buffer is fine)."""
+    assert isinstance(t, torch.Tensor) and t.dtype == dtype and t.numel() >= 1 and t.device == device, "a device counter: one element of the given type"
+    return t
+
+
+def ban_tokens_dev(logits, V, ids, len_base, len0=0, len_step=0, ld_ids=None, ngram=0, words=None, word_off=None, always=None, begin=None,
+                   begin_index=-1, eos=None, min_total=0):
+    """ban_tokens with the history length on the device (mh_ban_tokens_dev): row r conditions on the first len_base[0] + len0 + r * len_step
+    entries of its ids row, len_base int32 [>= 1] on the logits' device, read at kernel entry - a captured launch follows the counter.
+    Same kernel as ban_tokens: bit-identical at equal length.  A row whose length falls outside [0, ids.shape[1]] is left alone."""
+    R = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    _dev_counter(len_base, torch.int32, logits.device)
+    ld = cols = 0
+    if ids is not None:
+        assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and ids.device == logits.device
+        ld, cols = (ids.stride(0) if ld_ids is None else int(ld_ids)), ids.shape[1]
+        assert ld == 0 or (ld == ids.stride(0) and ids.shape[0] >= R)
+    n_words = 0
+    if words is not None:
+        assert words.dtype == torch.int64 and word_off.dtype == torch.int32 and words.is_contiguous() and word_off.is_contiguous()
+        n_words = word_off.numel() - 1
+    for t in (always, begin, eos):
+        assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.device == logits.device)
+    cnt = lambda t: 0 if t is None else t.numel()  # noqa: E731
+    L.call("mh_ban_tokens_dev", logits, logits.stride(0), R, V, ids, ld, cols, len_base, int(len0), int(len_step), int(ngram), words, word_off, n_words,
+           always, cnt(always), begin, cnt(begin), int(begin_index), eos, cnt(eos), int(min_total), _stream())
+    return logits
+
+
+def select_tokens_dev(logits, V, step_base, step_off=0, out=None, ids=None, len_base=None, len_off=0, do_sample=False, temperature=1.0, top_k=0,
+                      top_p=1.0, seed=0, return_u=False, min_p=None, epsilon_cutoff=0.0):
+    """select_tokens with the step number on the device (mh_select_tokens_dev): row r is drawn with the key (seed, step_base[0] + step_off, r),
+    step_base int64 [>= 1] on the logits' device, read at kernel entry.  out int64 [R] (default: a new tensor) gets the tokens; ids int64
+    [>= R, cols] (optional, with len_base int32 [>= 1]) gets them too, at column len_base[0] + len_off of every row - nowhere when that
+    column is outside the row.  Same kernel as select_tokens: the same tokens and uniforms at equal step."""
+    R = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    _dev_counter(step_base, torch.int64, logits.device)
+    if out is None:
+        out = torch.empty(R, dtype=torch.int64, device=logits.device)
+    assert out.dtype == torch.int64 and out.numel() >= R and out.is_contiguous() and out.device == logits.device
+    ld = cols = 0
+    if ids is not None:
+        assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and ids.device == logits.device and ids.shape[0] >= R
+        _dev_counter(len_base, torch.int32, logits.device)
+        ld, cols = ids.stride(0), ids.shape[1]
+    u = torch.empty(R, dtype=torch.float32, device=logits.device) if return_u else None
+    L.call("mh_select_tokens_dev", logits, logits.stride(0), R, V, int(do_sample), temperature, top_k, top_p, float(min_p or 0.0), float(epsilon_cutoff or 0.0),
+           seed & 0xFFFFFFFFFFFFFFFF, step_base, int(step_off), out, u, ids, ld, cols, len_base, int(len_off), _stream())
+    return (out, u) if return_u else out
+
+
 _splitk_ws = {}
 SPLITK_WS_MIN = 256 * 65536  # floats: one round of 256 tiles of fp32 partials (the most mh_gemm_splitk_max ever asks for)
 
