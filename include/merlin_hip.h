@@ -244,7 +244,9 @@ int mh_quick_gelu_fwd(const void* x, void* y, int64_t n, int dt, void* stream);
 int mh_quick_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, int dt, void* stream);
 /* y = a + b (n elements, 16-bit) */
 int mh_add(const void* a, const void* b, void* y, int64_t n, int dt, void* stream);
-/* generic dtype conversion src(dt_src) -> dst(dt_dst), n elements */
+/* generic dtype conversion src(dt_src) -> dst(dt_dst), n elements, round to nearest even (fp32 -> fp16 overflows to inf from 65520);
+ * subnormal inputs and results are converted like any other value, never flushed to zero; a NaN stays a NaN (its payload is not kept).
+ * MH_ERR_DTYPE (nothing written) when either code is not MH_BF16 / MH_F16 / MH_F32 */
 int mh_convert(const void* src, int dt_src, void* dst, int dt_dst, int64_t n, void* stream);
 
 /* ---- RoPE (rotate-half, theta) on the fused qkv buffer [T, 3, H, D] in place -------------
@@ -609,7 +611,11 @@ int mh_conv3x3_col2im(const void* dcols, void* dx, int N, int G, int C, int stri
  * err[0] != 0 on <im_start>/<im_end> count mismatch (base_mmgpt.py:116-118), err[1] != 0 when
  * <im_end> is not at start+P+1 (base_mmgpt.py:125-126); err[2], err[3] = (sample, position).
  * Feature row of patch j of global image g is g*rows_per_img + row0 + j (rows_per_img=577,row0=1
- * lets the projector run on the tower output with its CLS rows in place: no drop-CLS copy). */
+ * lets the projector run on the tower output with its CLS rows in place: no drop-CLS copy).
+ * A sample that raises an error gets no feature row at all (its src row is all -1); with several bad samples err[2], err[3] are those
+ * of one of them.  LIMIT: at most 1024 images are placed per sample.  A sample in which both the number of <im_start> tokens and the
+ * number of its images exceed 1024 is refused like a misplaced <im_end>: err[1] != 0, err[2] = sample, err[3] = position of the first
+ * <im_start> that was not honoured (the 1025th).  Exactly 1024 images are fine.  MH_ERR_ARG when rows_per_img < row0 + P. */
 int mh_splice_index(const int64_t* ids, const int32_t* img_offset, int32_t* src, int32_t* err,
                     int B, int S, int P, int64_t im_patch, int64_t im_start, int64_t im_end,
                     int rows_per_img, int row0, void* stream);

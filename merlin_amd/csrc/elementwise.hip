@@ -637,6 +637,8 @@ extern "C" int mh_add(const void* a, const void* b, void* y, int64_t n, int dt, 
 }
 extern "C" int mh_convert(const void* src, int dt_src, void* dst, int dt_dst, int64_t n, void* stream) {
   if (!src || !dst || n <= 0) return MH_ERR_ARG;
+  const auto known = [](int dt) { return dt == MH_BF16 || dt == MH_F16 || dt == MH_F32; };  // (load_any / store_any read any other code as fp16)
+  if (!known(dt_src) || !known(dt_dst)) return MH_ERR_DTYPE;
   hipLaunchKernelGGL(convert_k, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), src, dt_src, dst, dt_dst, n);
   MH_LAUNCH_CHECK();
 }

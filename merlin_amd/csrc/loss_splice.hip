@@ -21,12 +21,13 @@ __device__ __forceinline__ int64_t shifted_label(const int64_t* labels, int64_t 
 }
 
 __global__ __launch_bounds__(256) void ce_fwd_k(const float* __restrict__ logits, int64_t ldl, const int64_t* __restrict__ labels,
-                                                float* __restrict__ row_loss, float* __restrict__ lse_out, int S, int V) {
+                                                float* __restrict__ row_loss, float* __restrict__ lse_out, int S, int V, int vec4) {
+  // vec4: every row starts on a 16-byte boundary (base pointer and ldl both allow it, decided by mh_ce_fwd); else element by element
   __shared__ float sm[4], ss[4];
   const int64_t t = blockIdx.x;
   const float* row = logits + t * ldl;
   float m = -INFINITY, s = 0.f;
-  const int nv4 = ((ldl & 3) == 0) ? (V >> 2) : 0;
+  const int nv4 = vec4 ? (V >> 2) : 0;
   for (int i = threadIdx.x; i < nv4; i += 256) {
     const float4 x = ((const float4*)row)[i];
     const float mx = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
@@ -116,6 +117,7 @@ __global__ __launch_bounds__(256) void splice_index_k(const int64_t* __restrict_
   __shared__ int cnt_start[256], cnt_end[256], cnt_patch[256];
   __shared__ int start_pos[MAX_STARTS];
   __shared__ int tot[3];
+  __shared__ int over_pos;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int64_t* row = ids + (int64_t)b * S;
   int32_t* srow = src + (int64_t)b * S;
@@ -149,11 +151,16 @@ __global__ __launch_bounds__(256) void splice_index_k(const int64_t* __restrict_
   {
     int k = cnt_start[tid];
     for (int p = p0; p < p1; ++p)
-      if (row[p] == im_start) { if (k < MAX_STARTS) start_pos[k] = p; ++k; }
+      if (row[p] == im_start) {
+        if (k < MAX_STARTS) start_pos[k] = p;
+        else if (k == MAX_STARTS) over_pos = p;  // the first start beyond the table (exactly one thread sees it)
+        ++k;
+      }
   }
   __syncthreads();
   const int n_img = img_offset[b + 1] - img_offset[b];
-  const int n_use = min(min(tot[0], n_img), MAX_STARTS);  // zip(): extra images / starts are ignored
+  const int n_zip = min(tot[0], n_img);  // zip(): extra images / starts are ignored
+  const int n_use = min(n_zip, MAX_STARTS);
   for (int k = 0; k < n_use; ++k) {
     const int p = start_pos[k];
     const int endp = p + P + 1;
@@ -161,6 +168,10 @@ __global__ __launch_bounds__(256) void splice_index_k(const int64_t* __restrict_
       if (tid == 0) { atomicExch(&err[1], 1); err[2] = b; err[3] = p; }
       return;
     }
+  }
+  if (n_zip > MAX_STARTS) {  // an image this table cannot place: refuse the sample like a misplaced <im_end>, never keep its token embeddings
+    if (tid == 0) { atomicExch(&err[1], 1); err[2] = b; err[3] = over_pos; }
+    return;
   }
   const int base = img_offset[b];
   for (int i = tid; i < n_use * P; i += 256) {
@@ -354,7 +365,8 @@ extern "C" int mh_ce_fwd(const float* logits, int64_t ldl, const int64_t* labels
                          int B, int S, int V, void* stream) {
   if (!logits || !labels || !row_loss || !lse || !out2 || B <= 0 || S <= 0 || V <= 0) return MH_ERR_ARG;
   const int64_t T = (int64_t)B * S;
-  hipLaunchKernelGGL(ce_fwd_k, dim3((unsigned)T), dim3(256), 0, as_stream(stream), logits, ldl, labels, row_loss, lse, S, V);
+  const int vec4 = ((ldl & 3) == 0 && aligned16(logits)) ? 1 : 0;
+  hipLaunchKernelGGL(ce_fwd_k, dim3((unsigned)T), dim3(256), 0, as_stream(stream), logits, ldl, labels, row_loss, lse, S, V, vec4);
   hipLaunchKernelGGL(ce_reduce_k, dim3(1), dim3(1024), 0, as_stream(stream), (const float*)row_loss, labels, out2, T, S, V);
   MH_LAUNCH_CHECK();
 }

@@ -451,6 +451,38 @@ def test_cross_entropy_rows_with_minus_inf_logits(ops, V, ldl):
     _hold_ce(ops, f"-inf logits V={V} ldl={ldl}", logits, labels, V, Vpad, 1.0)
 
 
+IDLE_REDUCERS = list(range(100, 200)) + list(range(1000, 1024))  # threads of the 1024-thread reduction that get no scored row
+
+
+def _ce_many_rows(V, ldl, Bn, S, offset=0):
+    """More rows than the reduction has threads (T = Bn * S around and beyond 1024, 2048): thread i of it sums rows i, i + 1024, ...  Every row
+    of the threads in IDLE_REDUCERS is ignored (row t is scored against the flat label t + 1), the others keep a random label.
+    offset: the logits are a view that starts `offset` floats into their buffer."""
+    T = Bn * S
+    g = torch.Generator().manual_seed(V + T)
+    buf = (torch.randn(T * ldl + 4, generator=g) * 3).to(dev())
+    logits = buf[offset:offset + T * ldl].view(T, ldl)
+    labels = torch.randint(0, V, (Bn, S), generator=g)
+    t = torch.arange(T - 1)
+    labels.view(-1)[1:][torch.isin(t % 1024, torch.tensor(IDLE_REDUCERS))] = -100
+    return logits, labels.to(dev())
+
+
+@pytest.mark.parametrize("V,Bn,S,offset", [(103, 1, 1024, 0), (103, 1, 1025, 0), (103, 3, 700, 0), (103, 2, 2049, 0), (32003, 1, 1100, 0),
+                                           (103, 3, 700, 1)])
+def test_cross_entropy_more_rows_than_reducer_threads(ops, V, Bn, S, offset):
+    """The final reduction's strided loop over T > 1024 rows (second and third pass, threads with and without a row in the last pass, threads
+    with nothing to add), and, offset = 1, logits whose rows are 4 bytes off a 16-byte boundary although ldl % 4 == 0: the 16-byte loads of
+    the row pass would be misaligned there, so mh_ce_fwd takes them only when the base pointer allows it too."""
+    Vpad = (V + 63) // 64 * 64
+    logits, labels = _ce_many_rows(V, Vpad, Bn, S, offset)
+    assert Vpad % 4 == 0 and logits.data_ptr() % 16 == 4 * offset
+    sh = N.shifted_labels(labels).cpu()
+    scored = (sh >= 0).nonzero().flatten() % 1024
+    assert set(scored.tolist()) == set(range(min(1024, Bn * S - 1))) - set(IDLE_REDUCERS)  # (the very last row is never scored)
+    _hold_ce(ops, f"V={V} T={Bn}x{S} offset={offset}", logits, labels, V, Vpad, 0.5 if offset else 1.0)
+
+
 # ---- optimizer ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", list(N.ADAMW_CASES))
